@@ -7,7 +7,16 @@ fp32 accumulate, synthetic 4-class label maps + styles (BASELINE.json metric; co
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  Besides the driver contract it carries
+Rank 0 prints ONE JSON line: `value` (images/s) and `ms_per_step` of the timed steps, the losses of the last one, the
+configuration.  A plain run does nothing else: it sets up, warms up, times --steps steps, writes --dump-outputs, prints.
+--dump-outputs DIR: what the last timed step handed its caller (the generated batch and every loss; a fixed seeded sample of
+an array above DUMP_SAMPLE elements) as DIR/<name>.npy, float32.  That step starts from the state the run was set up with
+(weights, spectral-norm vectors, Adam moments and step), restored untimed before it, on the batch the rotation gives it: its
+inputs are the same in every run with the same arguments.  (The steps before it sum gradients with float atomics, and Adam's
+sign flips of near-zero gradients carry that rounding into the weights, further with every step: a state they hand on
+differs from run to run.)
+--full adds the measurements beside the headline, none of them inside the timed region:
+  ms_per_step_median : a per-step-synchronised pass over the same number of steps;
   roofline     : the dominant kernel (by GPU time: the patch-resident 3x3 conv kernel, MFMA-bound): algorithmic FLOPs
                  of its launches / their HIP-event durations, measured live; `kernels` lists every conv kernel the same way;
   roofline_hbm : the dominant HBM-bound entry point the same way, against 8 TB/s;
@@ -17,7 +26,8 @@ Rank 0 prints ONE JSON line.  Besides the driver contract it carries
                  launches skip nothing), `eager` the same steps as individual launches instead of hipGraph replays (the mode
                  the overlapped multi-GPU exchange runs in), `secondary` SURVEY 8(d)'s secondary metric: G-only forward
                  images/s of config 2 (fp32, eval mode) with its fraction of the fp32 MFMA peak, and the bf16 inference
-                 rate (netE + netG + post-processing).  Rank 0, N=1 only; none of them is inside the timed region.
+                 rate (netE + netG + post-processing).  Rank 0, N=1 only;
+  exchange     : --gpus N > 1, the exposed cost of the gradient exchange (the same steps with the collectives off).
 """
 import argparse
 import json
@@ -112,7 +122,7 @@ def cpu_step_seconds(opt_kwargs, hw, batch, threads, warm, timed, budget_s):
 def cpu_baseline(opt_kwargs, hw, batch, budget_s=100.0, extras=False):
     """SURVEY 8(d) / BASELINE.md 4: the CPU restatement runs the identical G+D step (same shapes -- batch 8 -- fp32, same synthetic
     inputs) on this box's host cores: 1 warm-up + 3 timed iterations (median; ~18 s each on the GPU box), and the 8-thread figure
-    SURVEY 6's survey numbers were taken at (one un-warmed iteration) -- both in the DEFAULT run since round 5 (VERDICT r4 #7:
+    SURVEY 6's survey numbers were taken at (one un-warmed iteration) -- both in the --full run (since round 5; VERDICT r4 #7:
     the 30-s cap of round 4 left a single timed iteration).  Thread count: measured on the GPU box's 2 x 64-core EPYC 9575F
     (profiles/r02/cpu_baseline_sweep.txt: 54 / 28 / 19.0 / 18.5 / 21 s per step at 128 / 64 / 32 / 16 / 8 threads) the step is
     fastest at 16-32 threads and 3x slower on all 128 physical cores (oneDNN across two sockets), so `cores` =
@@ -246,6 +256,47 @@ def _git_head():
 
 BATCH_SEEDS = (1234, 77, 2024, 5)          # the timed loop's batches (rank r: + r)
 TRAIN_GFLOP_PER_SAMPLE = {(256, 256): 1239.4, (640, 384): 4528.9}     # G step + D step, ngf = ndf = 64
+DUMP_SAMPLE = 1 << 22       # --dump-outputs: elements per array kept whole; a larger one is written as a fixed seeded sample of this many
+
+
+class TrainState:
+    """Everything a G+D step hands on to the next: the networks' parameters and buffers (spectral-norm u / v), the Adam moments
+    and the device step counter.  Taken once after set-up; restore() copies it back in place (the hipGraphs keep their pointers)."""
+
+    def __init__(self, trainer):
+        self.trainer = trainer
+        self.opts = (trainer.optimizer_G, trainer.optimizer_D)
+        self.saved = [t.detach().clone() for t in self._live()]
+        self.steps = [o.step_count for o in self.opts]
+
+    def _live(self):
+        # looked up at every use: the first forward moves each network's spectral-norm u / v into one arena and the module
+        # buffers become views of it (spectral.SpectralBank), so tensors taken before it are no longer the ones the step reads
+        m = self.trainer.pix2pix_model
+        return [v for net in (m.netG, m.netD, m.netE) for v in net.state_dict().values()] + \
+               [t for o in self.opts for t in (o.flat_m, o.flat_v, o.hyper)]
+
+    def restore(self):
+        with torch.no_grad():
+            for t, s in zip(self._live(), self.saved):
+                t.copy_(s)
+        for o, n in zip(self.opts, self.steps):
+            o.step_count = n
+
+
+def dump_outputs(trainer, dirname):
+    """--dump-outputs: the generated batch and every loss of the last step as float32 .npy files (2 MB at the defaults)."""
+    os.makedirs(dirname, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach().float()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.flatten()[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + '.npy'), t.cpu().numpy())
+    save('generated', trainer.get_latest_generated())
+    for k, v in trainer.get_latest_losses().items():
+        save('loss_' + k.replace('/', '_'), v)
 
 
 def secondary_train_steps(args, dev_index):
@@ -294,11 +345,15 @@ def main():
     ap.add_argument('--size', type=int, default=256)
     ap.add_argument('--ngf', type=int, default=64)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--cpu-baseline-extras', action='store_true', help='also time the CPU oracle on 8 threads and on all physical cores')
-    ap.add_argument('--no-kernel-events', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also measure what stands beside the headline: per-step median, kernel '
+                                                        'events and rooflines, single_batch / dense_labels / eager / secondary, '
+                                                        'cpu_baseline, the exchange cost (off: the headline alone)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip cpu_baseline')
+    ap.add_argument('--cpu-baseline-extras', action='store_true', help='--full: also time the CPU oracle on all physical cores')
+    ap.add_argument('--no-kernel-events', action='store_true', help='--full: skip the per-launch events (roofline, kernels)')
     ap.add_argument('--no-graphs', action='store_true', help='launch eagerly instead of replaying hipGraphs')
-    ap.add_argument('--no-extras', action='store_true', help='skip the dense_labels / eager / secondary measurements')
+    ap.add_argument('--no-extras', action='store_true', help='--full: skip the single_batch / dense_labels / eager / secondary measurements')
     ap.add_argument('--exchange', default='overlap', choices=['after_backward', 'overlap'],
                     help='--gpus > 1: all-reduce each gradient group of the G arena as soon as the backward has finished it (the '
                          'G step replays as one hipGraph segment per group, the collective of group k runs beside segment k+1; '
@@ -329,6 +384,7 @@ def main():
     with contextlib.redirect_stdout(io.StringIO()):
         trainer = Pix2PixTrainer(opt)
     fill_weights(trainer.pix2pix_model)
+    initial = TrainState(trainer) if args.dump_outputs else None
     # FOUR batches, resident in HBM before timing, taken in rotation (what train.py runs -- the label-sparse launches'
     # rectangle lists, class tables and uniform fractions differ from batch to batch; the first one alone is `single_batch` below)
     datas = [make_data(args.batch, args.size, seed + rank, dev) for seed in BATCH_SEEDS]
@@ -348,31 +404,44 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
+    elapsed, t0 = 0.0, time.perf_counter()
+    for i in range(args.steps):
+        if initial is not None and i == args.steps - 1:
+            # --dump-outputs: the last timed step starts from the set-up state, so what it computes does not carry the rounding
+            # of the steps before it (module docstring); the restore is outside the timed region
+            torch.cuda.synchronize()
+            elapsed += time.perf_counter() - t0
+            initial.restore()
+            torch.cuda.synchronize()
+            if world > 1:
+                torch.distributed.barrier()
+            t0 = time.perf_counter()
         step()
     torch.cuda.synchronize()
     if world > 1:
         torch.distributed.barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed += time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     # did the timed steps really run as hipGraph replays? (a failed capture falls back to eager launches and clears the option)
     graphs_ran = bool(trainer.use_graphs and trainer.graph_G is not None and trainer.graph_D is not None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, args.dump_outputs)
     # SURVEY 8(d) quotes the steady-state MEDIAN: a second, per-step-synchronised pass over the same number of steps gives
     # the distribution (the contract's `value` stays the whole-region mean above; the per-step syncs cost a launch gap each)
     per_step = []
-    for _ in range(args.steps):
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        step()
-        torch.cuda.synchronize()
-        per_step.append((time.perf_counter() - t1) * 1e3)
+    if args.full:
+        for _ in range(args.steps):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            step()
+            torch.cuda.synchronize()
+            per_step.append((time.perf_counter() - t1) * 1e3)
     # Beside the headline (rank 0's line only, one GPU only, never inside the timed region above):
     extras = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         def step_single():
             trainer.run_generator_one_step(dict(data))
             trainer.run_discriminator_one_step(dict(data))
@@ -402,7 +471,7 @@ def main():
     # only rank 0 records events.
     prof_steps = 0
     prof = ops.LaunchProfiler()
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         trainer.opt.hip_graphs = False
         step()
         torch.cuda.synchronize()
@@ -435,7 +504,7 @@ def main():
     #  what the gradient exchange costs the step: the same K steps with the collectives switched off (FlatGradSync.noop:
     # the replicas' weights drift apart from here on -- nothing below depends on them), and each group's exchange on its own
     exchange = None
-    if world > 1 and sdist.exchange_active():
+    if args.full and world > 1 and sdist.exchange_active():
         trainer.opt.hip_graphs = not args.no_graphs
         trainer.sync_G.noop = trainer.sync_D.noop = True
         for _ in range(2):
@@ -472,7 +541,8 @@ def main():
                        'graph_segments_G': (len(trainer.graph_G.segments) if graphs_ran else 0)},
             'losses': losses,
         }
-        out['ms_per_step_median'] = float(np.median(per_step))
+        if per_step:
+            out['ms_per_step_median'] = float(np.median(per_step))
         prof = prof.summary()
         if prof:
             peak = MFMA_PEAK_BF16 if args.dtype == 'bf16' else MFMA_PEAK_F32
@@ -556,7 +626,7 @@ def main():
                                           'gbs_pmc': (traffic_of(k)[0] * v['launches'] / (v['ms'] * 1e-3) / 1e9) if traffic_of(k)[0] else None}))
                               for k, v in prof.items()}
         out.update(extras)
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             del trainer
             torch.cuda.empty_cache()
             out['secondary'] = secondary_metrics(args, dev_index, data)
@@ -566,7 +636,7 @@ def main():
             out['config']['exchange'] = exchange_desc        # payload, algorithm, bucket size, NCCL_ALGO / NCCL_PROTO as set
         if exchange is not None:
             out['exchange'] = exchange
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(opt_kwargs, args.size, args.batch, extras=args.cpu_baseline_extras)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -734,7 +734,7 @@ def test_bench_two_ranks_dry_run(exchange):
     if 'debug_sync' in opts:
         env['S2E_DEBUG_SYNC'] = '1'
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--ngf', '16',
-                          '--batch', '2', '--exchange', exchange] + extra, env=env, capture_output=True, text=True, timeout=600, cwd=root)
+                          '--batch', '2', '--exchange', exchange, '--full'] + extra, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, out.stdout[-2000:]                       # rank 0 prints ONE line
@@ -745,6 +745,43 @@ def test_bench_two_ranks_dry_run(exchange):
     assert d['config']['graph_segments_G'] == (6 if exchange == 'overlap' else 1), d['config']
     ex = d['config']['exchange']
     assert ex['payload'] == ('bf16' if extra else 'fp32') and ex['algorithm'] == ('direct' if extra else 'allreduce') and ex['groups'] == 6, ex
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run prints the headline alone (nothing of --full), times exactly --steps steps, and --dump-outputs
+    writes the last timed step's outputs as float32 .npy files: the generated batch and the losses of the line.  That step starts
+    from the set-up state, so two runs with the same arguments write the same outputs up to the rounding of one step's
+    float-atomic sums (without the restore the steps before it carry their rounding into the weights, further every step)."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'S2E_DIST_BACKEND', 'S2E_DETERMINISTIC')}
+    runs = []
+    for tag in ('a', 'b'):
+        dump = tmp_path / tag
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '6', '--warmup', '2', '--ngf', '16',
+                              '--batch', '2', '--dump-outputs', str(dump)], env=env, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, out.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d['steps'] == 6 and d['value'] > 0 and d['unit'] == 'images/s' and d['higher_is_better'] is True and d['dtype'] == 'bf16'
+        assert abs(d['value'] - 2 / (d['ms_per_step'] / 1e3)) <= 1e-6 * d['value'], d
+        for k in ('roofline', 'kernels', 'ms_per_step_median', 'single_batch', 'dense_labels', 'eager', 'secondary', 'cpu_baseline'):
+            assert k not in d, k
+        files = sorted(os.listdir(dump))
+        assert files == sorted(['generated.npy'] + ['loss_%s.npy' % k.replace('/', '_') for k in d['losses']]), files
+        arrs = {f: np.load(os.path.join(dump, f)) for f in files}
+        for f, a in arrs.items():
+            assert a.dtype == np.float32 and np.isfinite(a).all(), f
+        assert arrs['generated.npy'].shape == (2, 1, 256, 256)      # (output_nc = 1: grey-level eye images)
+        for k, v in d['losses'].items():
+            np.testing.assert_allclose(float(arrs['loss_%s.npy' % k.replace('/', '_')].mean()), v, rtol=1e-6)
+        runs.append(arrs)
+    # the generator's output is tanh in [-1, 1], computed in bf16 (one ulp near 1: 2^-8)
+    np.testing.assert_allclose(runs[0]['generated.npy'], runs[1]['generated.npy'], rtol=0, atol=1e-2)
+    for f in runs[0]:
+        if f.startswith('loss_'):
+            np.testing.assert_allclose(runs[0][f], runs[1][f], rtol=1e-3, atol=1e-4, err_msg=f)
 
 
 def test_bench_refuses_more_ranks_than_gpus():

@@ -18,12 +18,12 @@ PMC="--steps 2 --warmup 1 --no-graphs --no-cpu-baseline --no-kernel-events --no-
 cd "$R"
 # the same command under the kernel trace first (its per-family kernel time is quoted by the bench line), then the bench line as the
 # driver runs it (cpu_baseline legs included)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o kt -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras \
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -o kt -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras \
     > "$O/${P}_bench_under_rocprof.json" 2>/dev/null
 cp /tmp/kt/*/*kernel_stats.csv "$O/${P}_kernel_stats.csv" 2>/dev/null || cp /tmp/kt/*kernel_stats.csv "$O/${P}_kernel_stats.csv"
 python3 tools/rocprof_family_ms.py "$O/${P}_kernel_stats.csv" "$O/kernel_ms_per_step.json" > /dev/null
 mkdir -p profiles/r06 && cp "$O/kernel_ms_per_step.json" profiles/r06/kernel_ms_per_step.json
-python3 bench.py --steps 50 --warmup 10 > "$O/${P}_bench.json" 2> "$O/${P}_bench.err"
+python3 bench.py --steps 50 --warmup 10 --full > "$O/${P}_bench.json" 2> "$O/${P}_bench.err"
 python3 tools/profile_step.py > "$O/${P}_per_shape_in_step.log" 2>/dev/null
 (cd tools && python3 bench_spade_fused.py > "../$O/${P}_spade_fused_microbench.log" 2>/dev/null)
 python3 tools/bench_inference.py > "$O/${P}_inference.log" 2>/dev/null
