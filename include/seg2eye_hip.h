@@ -159,6 +159,8 @@ int s2e_conv2d_wgrad(int dtype, const void* x, const void* gy, float* dw, float*
  * (discriminator.py:84-96) and the 8x8 maps each ran as a 30-160 us launch that fills the chip badly and ends with a tail, plus a
  * reduction launch for the split ones; here their workgroups run side by side (csrc/conv_wgrad.hip, conv_wgrad_multi_kernel), followed
  * by ONE reduction launch for all jobs that store partial tiles.  Same sums as s2e_conv2d_wgrad job by job (dw / dbias ACCUMULATED).
+ * Jobs may share dw and / or dbias (any overlap of the Cout x KH*KW*Cin and Cout float ranges): every job's sum is added; where
+ * several jobs add into one element the result depends on their order in the last bit.
  * bf16, Cin and Cout multiples of 8, shapes s2e_conv2d_wgrad would run in its generic kernel (s2e_conv2d_wgrad_multi_supported).
  * workspace: s2e_conv2d_wgrad_multi_workspace_bytes(jobs) (uninitialised; less or none: those jobs add with fp32 atomics). */
 typedef struct s2e_wgrad_multi_job {

@@ -384,6 +384,26 @@ int s2e_c8s2_wgrad_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n
         const bool tiles = ws && workspace_bytes >= (size_t)(base / C8W_MAX_JOBS + 1) * 512 * C8W_TILE * sizeof(float) && total_wg <= 512.0;
         double work = 0.0;
         for (int i = 0; i < n; ++i) work += (double)jobs[idx[base + i]].d.N * jobs[idx[base + i]].d.Ho * jobs[idx[base + i]].d.Wo;
+        // a job's share of the chunk's workgroups goes by its pixels, at least 1, at most its rows.  With partial tiles the shares must
+        // not sum past the chunk's 512 tiles of workspace (nor past S2E_C8W_WGS below that): the floor of 1 can lift a chunk of one big
+        // and three tiny jobs to 511 + 1 + 1 + 1 -- the excess comes off the largest share
+        int shares[C8W_MAX_JOBS], sum = 0;
+        for (int i = 0; i < n; ++i) {
+            const s2e_conv_desc* d = &jobs[idx[base + i]].d;
+            const int rows = d->N * d->Ho;
+            int share = (int)((tiles ? total_wg : total_wg / 4) * ((double)d->N * d->Ho * d->Wo) / work);
+            shares[i] = share < 1 ? 1 : (share > rows ? rows : share);
+            sum += shares[i];
+        }
+        if (tiles) {
+            const int budget = (int)total_wg > n ? (int)total_wg : n;     // (<= 512: total_wg <= 512 and n <= C8W_MAX_JOBS)
+            while (sum > budget) {
+                int big = 0;
+                for (int i = 1; i < n; ++i) if (shares[i] > shares[big]) big = i;
+                --shares[big];
+                --sum;
+            }
+        }
         int blocks = 0;
         for (int i = 0; i < n; ++i) {
             const s2e_wgrad_multi_job& J = jobs[idx[base + i]];
@@ -396,8 +416,7 @@ int s2e_c8s2_wgrad_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n
             p.G = ceil_div(d->Wo, 16); p.pitch = 32 * p.G + 8; p.rows = d->N * d->Ho;
             p.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * 16);
             p.gy_bytes = (unsigned)((long)d->N * d->Ho * d->Wo * 128);
-            int share = (int)((tiles ? total_wg : total_wg / 4) * ((double)d->N * d->Ho * d->Wo) / work);
-            share = share < 1 ? 1 : (share > p.rows ? p.rows : share);
+            const int share = shares[i];
             if (tiles) p.part = (float*)(ws + ((size_t)(base / C8W_MAX_JOBS) * 512 + blocks) * C8W_TILE * sizeof(float));
             b.first[i] = blocks;
             blocks += share;

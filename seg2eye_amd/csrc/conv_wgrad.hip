@@ -293,7 +293,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_multi_kernel(const WgMulti 
 // by the four waves of a workgroup (wave g takes splits g, g + 4, ...; eight loads in flight), combined through LDS as
 // (g0 + g1) + (g2 + g3).  Workgroups stride over the items: at most 2048 of them however many tiles there are (a 128-tile dW
 // would otherwise launch 32768 tiny workgroups), and a ONE-tile dW with 512 splits still spreads over 256 items.
-__device__ __forceinline__ void wgrad_reduce_body(const WgradParams& p, int splits, int items, int blk, int nblk, float (*red)[64]) {
+// atomic: another job of the same launch reduces into an overlapping dw / dbias range (s2e_conv2d_wgrad_multi's jobs may share them):
+// the final adds are fp32 atomics instead of read-modify-writes.
+__device__ __forceinline__ void wgrad_reduce_body(const WgradParams& p, int splits, int items, int blk, int nblk, float (*red)[64],
+                                                  bool atomic = false) {
     const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
     const size_t stride = (size_t)p.tiles_co * p.tiles_k * 16384;   // one split further
     for (int item = blk; item < items; item += nblk) {
@@ -317,7 +320,10 @@ __device__ __forceinline__ void wgrad_reduce_body(const WgradParams& p, int spli
             const int r = frag & 15, ni = (frag >> 4) & 1, mi = (frag >> 5) & 1, wave = frag >> 6;
             const int co = tco * 128 + (wave >> 1) * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
             const int k = tk * 128 + (wave & 1) * 64 + ni * 32 + (lane & 31);
-            if (co < p.Cout && k < p.Ktot) p.dw[(size_t)co * p.Ktot + k] += tot;
+            if (co < p.Cout && k < p.Ktot) {
+                if (atomic) atomicAdd(p.dw + (size_t)co * p.Ktot + k, tot);
+                else p.dw[(size_t)co * p.Ktot + k] += tot;
+            }
         }
         __syncthreads();
     }
@@ -342,7 +348,11 @@ __device__ __forceinline__ void wgrad_reduce_body(const WgradParams& p, int spli
         for (; j < P; j += 4) a += at(j);
         red[g][lane] = a;
         __syncthreads();
-        if (g == 0 && co < p.Cout) p.dbias[co] += (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+        if (g == 0 && co < p.Cout) {
+            const float tot = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+            if (atomic) atomicAdd(p.dbias + co, tot);
+            else p.dbias[co] += tot;
+        }
     }
 }
 
@@ -350,14 +360,15 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const WgradParam
     __shared__ float red[4][64];
     wgrad_reduce_body(p, splits, items, blockIdx.x, gridDim.x, red);
 }
-// the reductions of a multi-job launch's split jobs, side by side
-struct WgMultiRed { int n; int first[WGM_MAX_JOBS + 1]; int job[WGM_MAX_JOBS]; };
+// the reductions of a multi-job launch's split jobs, side by side; atomic[k]: reduction k's dw or dbias overlaps another's
+struct WgMultiRed { int n; int first[WGM_MAX_JOBS + 1]; int job[WGM_MAX_JOBS]; int atomic[WGM_MAX_JOBS]; };
 __global__ __launch_bounds__(256) void conv_wgrad_reduce_multi_kernel(const WgMulti b, const WgMultiRed r) {
     __shared__ float red[4][64];
     int k = 0;
     while (k + 1 < r.n && (int)blockIdx.x >= r.first[k + 1]) ++k;
     const int jb = r.job[k];
-    wgrad_reduce_body(b.j[jb], b.splits[jb], b.j[jb].tiles_k * b.j[jb].tiles_co * 256, (int)blockIdx.x - r.first[k], r.first[k + 1] - r.first[k], red);
+    wgrad_reduce_body(b.j[jb], b.splits[jb], b.j[jb].tiles_k * b.j[jb].tiles_co * 256, (int)blockIdx.x - r.first[k], r.first[k + 1] - r.first[k], red,
+                      r.atomic[k] != 0);
 }
 
 // ------------------------------------------------------------------------------------ bf16 LDS-DMA variant
@@ -655,6 +666,11 @@ extern "C" int s2e_conv2d_wgrad(int dtype, const void* x, const void* gy, float*
 }
 
 // ---- every generic weight gradient of a backward pass in one launch (+ one for the partial-tile reductions): conv_wgrad_multi_kernel
+// do the fp32 ranges [a, a + na) and [b, b + nb) share an element?  (NULL: no range)
+static bool ranges_overlap(const float* a, size_t na, const float* b, size_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
+}
 static bool wgrad_multi_ok(int dtype, const s2e_conv_desc* d) {
     if (!d || dtype != S2E_BF16 || d->transposed || (d->stride != 1 && d->stride != 2)) return false;
     if (d->Cin % 8 != 0 || d->Cout % 8 != 0) return false;
@@ -770,6 +786,16 @@ extern "C" int s2e_conv2d_wgrad_multi(int dtype, const s2e_wgrad_multi_job* jobs
         }
         b.first[n] = blocks;
         r.first[r.n] = rblocks;
+        // jobs may share dw / dbias (the sums accumulate): the multi kernel's atomics are safe, but the reductions run side by side with
+        // plain read-modify-writes -- a reduction whose dw or dbias range overlaps another's of this launch adds with atomics instead
+        for (int a = 0; a < r.n; ++a)
+            for (int c = 0; c < r.n; ++c) {
+                const WgradParams& pa = b.j[r.job[a]];
+                const WgradParams& pc = b.j[r.job[c]];
+                if (c != a && (ranges_overlap(pa.dw, (size_t)pa.Cout * pa.Ktot, pc.dw, (size_t)pc.Cout * pc.Ktot) ||
+                               ranges_overlap(pa.dbias, (size_t)pa.Cout, pc.dbias, (size_t)pc.Cout)))
+                    r.atomic[a] = 1;
+            }
         conv_wgrad_multi_kernel<<<blocks, 256, 0, st>>>(b);
         S2E_CHECK_LAUNCH("conv_wgrad_multi_kernel");
         if (r.n) {

@@ -411,8 +411,17 @@ int s2e_wgrad_flat_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n
             p.splits = ceil_div(p.nslabs, p.per_split);
             p.nblk = units[i] * p.splits;
             p.flags = noepi ? atoi(getenv("S2E_WF_NOEPI")) & 7 : 0;
+            // (another job whose dW range overlaps this one's: compared as address ranges, not only as pointers)
             bool shared = false;
-            for (int k = 0; k < n_all; ++k) shared = shared || (k != base + i && jobs[idx[k]].dw == jobs[idx[base + i]].dw);
+            const char* lo = (const char*)p.dw;
+            const char* hi = lo + (size_t)p.Cout * p.Ktot * sizeof(float);
+            for (int k = 0; k < n_all && !shared; ++k) {
+                if (k == base + i) continue;
+                const s2e_conv_desc& dk = jobs[idx[k]].d;
+                const char* klo = (const char*)jobs[idx[k]].dw;
+                const char* khi = klo + (size_t)dk.Cout * dk.KH * dk.KW * dk.Cin * sizeof(float);
+                shared = klo < hi && lo < khi;
+            }
             if (p.splits == 1 && !shared) p.flags |= 8;
             b.first[i] = blocks;
             blocks += (p.nblk + 7) & ~7;

@@ -243,6 +243,21 @@ class _ZeroScope:
 
 
 # ------------------------------------------------------------------------------ deferred weight-gradient re-layout
+def _overlap(a, b):
+    """Do tensors a and b share a byte of the same storage?  (The byte range of a strided tensor: from its first element to its
+    last, gaps included -- conservative for interleaved views.)"""
+    if a.numel() == 0 or b.numel() == 0:
+        return False
+
+    def span(t):
+        lo = t.data_ptr()
+        n = t.numel() if t.is_contiguous() else sum((k - 1) * s for k, s in zip(t.shape, t.stride())) + 1
+        return lo, lo + n * t.element_size()
+    alo, ahi = span(a)
+    blo, bhi = span(b)
+    return alo < bhi and blo < ahi and a.untyped_storage().data_ptr() == b.untyped_storage().data_ptr()
+
+
 class GradSink:
     """Inside a ZeroPool scope (a trainer step) the per-layer "packed dW -> OIHW gradient arena" conversions -- plain
     re-layout, or the spectral-norm chain rule dW_orig = (dW - <dW, W_sn> u v^T)/sigma -- are not launched one by one
@@ -400,13 +415,13 @@ class GradSink:
 
     @staticmethod
     def is_pinned(t):
-        """Is `t` the output gradient of a weight-gradient job queued in the open trainer step (not launched yet)?  Whoever would
-        modify it in place (ModulateFn's relay) must write elsewhere: the queue holds the tensor itself, not a copy."""
+        """Does `t` share memory with the output gradient of a weight-gradient job queued in the open trainer step (not launched yet)?
+        Whoever would modify it in place (ModulateFn's relay) must write elsewhere: the queue holds the tensor itself, not a copy.
+        A view at another offset, a reshaped alias or any overlapping slice of that tensor's storage counts; a disjoint slice does not."""
         pool = ZeroPool.active()
         if pool is None or t is None:
             return False
-        p = t.data_ptr()
-        return any(j[1].data_ptr() == p for j in pool.sink.wg) or any(j[1].data_ptr() == p for j in pool.sink.gwg)
+        return any(_overlap(t, j[1]) for j in pool.sink.wg) or any(_overlap(t, j[1]) for j in pool.sink.gwg)
 
     @staticmethod
     def push_gwg(x, gy, dw, dbias, desc_key, gy_shared=False):

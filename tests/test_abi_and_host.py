@@ -123,6 +123,35 @@ def test_round6_planners_are_host_only():
     assert L.s2e_shard_sum(bf, 1, 1, 8, 100, None) == -1                                  # shard bytes not a multiple of 16
 
 
+def test_wgrad_multi_c8_workspace_and_argument_errors_are_host_only():
+    """s2e_conv2d_wgrad_multi's c8 jobs (the PatchGAN's 8-channel first layer, conv_c8.hip) take 512 partial tiles of 64 x 128 + 64
+    floats per chunk of 4 jobs, whatever the jobs' sizes; a job with a null operand is refused, naming the job, before any launch."""
+    from seg2eye_amd import _lib
+    if os.environ.get('S2E_CONV_C8', '1') == '0' or os.environ.get('S2E_DETERMINISTIC', '0') not in ('', '0'):
+        pytest.skip('c8 kernel switched off in this environment')
+    L = _lib.lib()
+    bf = _lib.S2E_BF16
+    tile = (64 * 128 + 64) * 4
+    shapes = [(16, 128, 128), (1, 2, 2), (2, 33, 47), (1, 1, 40), (3, 17, 9), (1, 64, 64), (16, 256, 256), (1, 3, 5), (2, 20, 20)]
+    for n in (4, 5, 9):
+        jobs = (_lib.WgradMultiJob * n)()
+        for j, (b, h, w) in zip(jobs, shapes):
+            j.d = _lib.ConvDesc(b, h, w, 8, h // 2 + 1, w // 2 + 1, 64, 4, 4, 2, 2, 0, 0, 0, 0)
+            assert L.s2e_conv2d_wgrad_multi_kind(bf, ctypes.byref(j.d)) == 6
+        assert L.s2e_conv2d_wgrad_multi_workspace_bytes(bf, ctypes.byref(jobs), n) == -(-n // 4) * 512 * tile
+        # (every pointer of every job is NULL: nothing could be launched even if the check were missing)
+        assert L.s2e_conv2d_wgrad_multi(bf, ctypes.byref(jobs), n, None, 0, None) == -1
+        assert b'null pointer in job 0' in L.s2e_last_error()
+    # mixed table: a generic, a flat (4x4 stride 2) and a c8 job, all without operands
+    jobs = (_lib.WgradMultiJob * 3)()
+    for j, a in zip(jobs, ((4, 64, 64, 64, 32, 32, 128, 3, 3, 2, 1, 0, 0, 0, 0), (16, 129, 129, 64, 65, 65, 128, 4, 4, 2, 2, 0, 0, 0, 0),
+                           (16, 128, 128, 8, 65, 65, 64, 4, 4, 2, 2, 0, 0, 0, 0))):
+        j.d = _lib.ConvDesc(*a)
+    assert L.s2e_conv2d_wgrad_multi(bf, ctypes.byref(jobs), 3, None, 0, None) == -1
+    assert b'null pointer' in L.s2e_last_error()
+    assert L.s2e_conv2d_wgrad_multi(bf, ctypes.byref(jobs), 4097, None, 0, None) == -1          # more than 4096 jobs
+
+
 def test_pack_block_map_is_host_only():
     """s2e_pack_block_map is pure host code: grid of a forward pack = rows_pad/4 x ceil(cin_pad/64), of a
     transposed pack = ceil(cout/64) x ceil(rows_pad/8); triples are {job, bx, by}."""
