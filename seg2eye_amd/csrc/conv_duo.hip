@@ -772,8 +772,8 @@ int duo_cu_count() {
     return n;
 }
 
-// S2E_CONV_DUO = the work items (rectangle x 128-channel tile) a launch must have for this kernel to take it (default 512: one per
-// workgroup of the 2-per-CU grid); 0 = never (conv_patch.hip runs everything, for A/B runs).
+// S2E_CONV_DUO = the work items (rectangle x 128-channel tile) a launch must have for this kernel to take it (default 256: one per
+// CU, half the 2-per-CU grid); 0 = never (conv_patch.hip runs everything, for A/B runs).
 int duo_min_items() {
     static const int n = [] { const char* e = getenv("S2E_CONV_DUO"); return e ? atoi(e) : 256; }();
     return n;

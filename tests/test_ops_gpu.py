@@ -1154,8 +1154,9 @@ def test_wgrad_sink_fresh_arena_view_used_at_two_shapes(order):
 def test_patch_conv_kernels_match_torch_at_bench_shapes(duo):
     """The two patch-resident 3x3 kernels at the bench's shapes against torch's own convolution in fp32 (tools/check_duo.py):
     forward with bias + residual + LeakyReLU, data-gradient with the ReLU mask, and the fused [gamma | beta] conv + SPADE+Style
-    modulation, dense and through an odd-length rectangle list.  S2E_CONV_DUO=512 (the default): csrc/conv_duo.hip, two
-    workgroups per CU, takes them; =0: csrc/conv_patch.hip runs the same checks (it keeps every shape the duo plan declines)."""
+    modulation, dense and through an odd-length rectangle list.  S2E_CONV_DUO=512 (twice the default threshold of 256 work items):
+    csrc/conv_duo.hip, two workgroups per CU, takes the shapes with at least that many; =0: csrc/conv_patch.hip runs the same checks
+    (it keeps every shape the duo plan declines)."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, S2E_CONV_DUO=duo)
