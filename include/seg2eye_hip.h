@@ -549,6 +549,16 @@ int s2e_fc_head_bwd(int dtype, const void* x, const float* W, const float* dy, v
  * With beta1 == 0 and weight_decay == 0 (the reference's TTUR default) m_t = g_t*grad_scale whatever m was: the kernel then neither
  * reads nor writes m (same bits in p and v, 20 instead of 28 bytes per parameter); a caller that saves m forms it from g. */
 int s2e_adam_flat(float* p, const float* g, float* m, float* v, long n, float* hyper, void* stream);
+/* The same step with an exponential moving average of the parameters kept in a fifth arena (an extension: the reference keeps
+ * none).  p, v and m get exactly the bits s2e_adam_flat gives them from the same inputs -- both branches, vector body and scalar
+ * tail -- and hyper is used and ticked in the same way.  ema_hyper: 2 fp32 in DEVICE memory {decay, start_step}, read by the launch
+ * (graph-capturable; a changed decay or a resumed step count needs no host branch).  With t = hyper[4] + 1, the step this launch
+ * performs:  t <= start_step: ema = p_new (ema is not read);  otherwise ema = decay * ema + (1 - decay) * p_new, in fp32, in that
+ * written form.  8 more bytes per parameter than s2e_adam_flat (28 at beta1 == 0 and weight_decay == 0, else 36) and no launch of
+ * its own.  ema must be 16-byte aligned like the other arenas and must not overlap them; S2E_ERR_ARG on a null pointer, a
+ * misaligned arena or n <= 0, before any launch. */
+int s2e_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float* hyper, const float* ema_hyper,
+                      void* stream);
 
 /* ------------------------------------------------------------------ data-parallel gradient exchange (new: the reference is single-GPU;
  * its only multi-GPU hook is the nn.DataParallel wrap of models/networks/__init__.py:46-47)

@@ -211,6 +211,89 @@ extern "C" int s2e_adam_flat(float* p, const float* g, float* m, float* v, long 
     return S2E_OK;
 }
 
+// ---- the same step with an exponential moving average of the parameters folded in (optim.FlatAdam(ema_decay=...)).
+// The Adam expressions are adam_flat_kernel's, term for term and in its order, in all four places (both branches, vector body and
+// scalar tail): p, v and m come out with the bits that kernel gives.  The average costs its own read and write (8 bytes per
+// parameter: 28 instead of 20 at beta1 = 0, 36 instead of 28 otherwise) -- the new p is in registers when it is needed.
+// ema_hyper (DEVICE memory, like hyper) = {decay, start_step}: the launch that performs step t = hyper[4] + 1 copies (ema = p_new,
+// ema is not read) while t <= start_step and averages afterwards, ema = decay * ema + (1 - decay) * p_new.
+__device__ __forceinline__ float ema_of(float e, float pn, float decay, float one_minus) { return decay * e + one_minus * pn; }
+
+__global__ __launch_bounds__(256) void adam_flat_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+        float* __restrict__ v, float* __restrict__ ema, long n, const float* __restrict__ hyper, const float* __restrict__ ema_hyper) {
+    const float lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], t = hyper[4] + 1.f, grad_scale = hyper[5];
+    const float wd = hyper[6];
+    const float bc1 = 1.f - powf(beta1, t), bc2 = 1.f - powf(beta2, t);
+    const float lr_bc1 = lr / bc1, rsqrt_bc2 = 1.f / sqrtf(bc2);
+    const float decay = ema_hyper[0], one_minus = 1.f - decay;
+    const bool copy = t <= ema_hyper[1];                    // (uniform over the launch)
+    const long nv = n / 4;
+    if (beta1 == 0.f && wd == 0.f) {
+        for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+            f32x4_t pp = ((f32x4_t*)p)[i], gg = ((const f32x4_t*)g)[i], vv = ((f32x4_t*)v)[i], ee = pp;
+            if (!copy) ee = ((f32x4_t*)ema)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float gr = gg[j] * grad_scale + wd * pp[j];
+                const float mj = beta1 * 0.f + (1.f - beta1) * gr;
+                vv[j] = beta2 * vv[j] + (1.f - beta2) * gr * gr;
+                pp[j] -= lr_bc1 * mj / (sqrtf(vv[j]) * rsqrt_bc2 + eps);
+                ee[j] = copy ? pp[j] : ema_of(ee[j], pp[j], decay, one_minus);
+            }
+            ((f32x4_t*)p)[i] = pp; ((f32x4_t*)v)[i] = vv; ((f32x4_t*)ema)[i] = ee;
+        }
+        if (blockIdx.x == 0)
+            for (long i = nv * 4 + threadIdx.x; i < n; i += blockDim.x) {
+                const float gr = g[i] * grad_scale + wd * p[i];
+                const float vi = beta2 * v[i] + (1.f - beta2) * gr * gr;
+                v[i] = vi;
+                float pi = p[i];
+                pi -= lr_bc1 * ((1.f - beta1) * gr) / (sqrtf(vi) * rsqrt_bc2 + eps);
+                p[i] = pi;
+                ema[i] = copy ? pi : ema_of(ema[i], pi, decay, one_minus);
+            }
+        return;
+    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+        f32x4_t pp = ((f32x4_t*)p)[i], gg = ((const f32x4_t*)g)[i], mm = ((f32x4_t*)m)[i], vv = ((f32x4_t*)v)[i], ee = pp;
+        if (!copy) ee = ((f32x4_t*)ema)[i];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float gr = gg[j] * grad_scale + wd * pp[j];
+            mm[j] = beta1 * mm[j] + (1.f - beta1) * gr;
+            vv[j] = beta2 * vv[j] + (1.f - beta2) * gr * gr;
+            pp[j] -= lr_bc1 * mm[j] / (sqrtf(vv[j]) * rsqrt_bc2 + eps);
+            ee[j] = copy ? pp[j] : ema_of(ee[j], pp[j], decay, one_minus);
+        }
+        ((f32x4_t*)p)[i] = pp; ((f32x4_t*)m)[i] = mm; ((f32x4_t*)v)[i] = vv; ((f32x4_t*)ema)[i] = ee;
+    }
+    if (blockIdx.x == 0)
+        for (long i = nv * 4 + threadIdx.x; i < n; i += blockDim.x) {
+            const float gr = g[i] * grad_scale + wd * p[i];
+            const float mi = beta1 * m[i] + (1.f - beta1) * gr;
+            const float vi = beta2 * v[i] + (1.f - beta2) * gr * gr;
+            m[i] = mi; v[i] = vi;
+            float pi = p[i];
+            pi -= lr_bc1 * mi / (sqrtf(vi) * rsqrt_bc2 + eps);
+            p[i] = pi;
+            ema[i] = copy ? pi : ema_of(ema[i], pi, decay, one_minus);
+        }
+}
+
+extern "C" int s2e_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float* hyper, const float* ema_hyper,
+                                 void* stream) {
+    if (!p || !g || !m || !v || !ema || !hyper || !ema_hyper || n <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_adam_flat_ema: bad argument");
+    if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15)
+        S2E_FAIL(S2E_ERR_ARG, "s2e_adam_flat_ema: arenas must be 16-byte aligned");
+    const long nv = n / 4 + 1;
+    const int grid = (int)((nv + 255) / 256 < 4096 ? (nv + 255) / 256 : 4096);      // (s2e_adam_flat's grid)
+    adam_flat_ema_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p, g, m, v, ema, n, hyper, ema_hyper);
+    S2E_CHECK_LAUNCH("adam_flat_ema_kernel");
+    adam_tick_kernel<<<1, 1, 0, (hipStream_t)stream>>>(hyper);      // after every block has read hyper[4]
+    S2E_CHECK_LAUNCH("adam_tick_kernel");
+    return S2E_OK;
+}
+
 // ---- data-parallel gradient exchange, 'direct' form (seg2eye_amd/distributed.py): the owner of a bucket shard adds the P copies the
 // all-to-all delivered, in rank order, fp32 accumulation, ONE rounding to the payload dtype -- every replica gets the same bits from the
 // all-gather that follows.  recv: [world][shard] elements; out: [shard].  One 16-byte vector per thread.

@@ -180,6 +180,17 @@ def adam_flat_step(p, g, m, v, hyper, skips_m=False):
         nbytes=float((5 if skips_m else 7) * 4 * p.numel()))
 
 
+def adam_flat_ema_step(p, g, m, v, ema, hyper, ema_hyper, skips_m=False):
+    """adam_flat_step with the exponential moving average of p kept in `ema` by the same launch (s2e_adam_flat_ema): p, v, m get
+    the bits adam_flat_step gives them.  ema_hyper: 2-float DEVICE tensor {decay, start_step}; the step t = completed steps + 1
+    copies p into ema while t <= start_step and averages afterwards, ema = decay * ema + (1 - decay) * p."""
+    _need(p, g, m, v, ema, hyper, ema_hyper)
+    LaunchProfiler.run('adam', 0.0, lambda: L.check(
+        L.lib().s2e_adam_flat_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), _p(ema_hyper), _stream()), 's2e_adam_flat_ema'),
+        # adam_flat_step's bytes + the average's own read and write: 7 floats per parameter without the first moment, 9 with it
+        nbytes=float((7 if skips_m else 9) * 4 * p.numel()))
+
+
 def openeds_error(produced, target):
     """Per-image OpenEDS error of two batches in [-1, 1] (models/networks/loss.py:135-155 `calculate_mse_for_tensors`):
     both mapped to 0..255 with the reference's int truncation, then sqrt(sum d^2) / (H*W).  -> fp32 (N,), no gradient."""

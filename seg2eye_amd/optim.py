@@ -25,14 +25,20 @@ def _arena_view(flat, off, p, cl):
 
 
 class FlatAdam:
-    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, never_updated=(), channels_last=None):
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, never_updated=(), channels_last=None,
+                 ema_decay=None, ema_start=0):
         """channels_last (default: on, S2E_WEIGHTS_CL): a conv weight whose input-channel count is a multiple of 8 is stored
         [Cout][KH][KW][Cin] in the arenas -- the order the MFMA kernels' packed matrices and weight gradients use -- and exposed
         as a (Cout, Cin, KH, KW) view: state_dict values, shapes and every element-wise use are unchanged, while the
         weight-gradient kernels accumulate straight into `.grad` and the packs read rows instead of gathering.
         never_updated: parameters that are in the optimizer but never receive a gradient (netE.fc_var: `logvar` enters no
         loss, pix2pix_model.py:307-314).  torch.optim.Adam SKIPS a parameter whose .grad is None -- no moment update and, what
-        matters, no weight decay -- so they are laid out at the END of the arenas and the Adam launch stops before them."""
+        matters, no weight decay -- so they are laid out at the END of the arenas and the Adam launch stops before them.
+        ema_decay (default None: off, nothing is allocated and step() is the plain launch): keep an exponential moving average of
+        the parameters in a fifth arena `flat_ema`, updated by the Adam launch itself (s2e_adam_flat_ema: 8 more bytes per
+        parameter, no second pass over p).  It starts as a copy of flat_p -- so the never-updated tail holds its parameters from
+        the first moment on --; step t (1-based, this optimizer's own count) copies p into it while t <= ema_start and averages
+        afterwards, ema = decay * ema + (1 - decay) * p.  `ema_views()` are the per-parameter views."""
         skip = {id(p) for p in never_updated}
         seen, plist = set(), []
         for p in list(params) + [p for p in never_updated]:
@@ -84,6 +90,34 @@ class FlatAdam:
         self.hyper = torch.tensor([float(lr), self.betas[0], self.betas[1], self.eps, 0.0, 1.0, float(weight_decay)],
                                   dtype=torch.float32, device=dev)
         self._hyper_host = (float(lr), 1.0)
+        if ema_decay is not None:
+            if not 0.0 <= float(ema_decay) < 1.0 or int(ema_start) < 0:
+                raise ValueError('FlatAdam: ema_decay must lie in [0, 1) and ema_start must not be negative')
+            self.ema_decay, self.ema_start = float(ema_decay), int(ema_start)
+            self.flat_ema = self.flat_p.clone()
+            # device-resident {decay, start_step}: read by the launch, like `hyper`
+            self.ema_hyper = torch.tensor([self.ema_decay, float(self.ema_start)], dtype=torch.float32, device=dev)
+
+    @property
+    def has_ema(self):
+        return 'flat_ema' in self.__dict__
+
+    def ema_views(self):
+        """The averaged value of every parameter, in `params` order: views into flat_ema of the parameter's logical shape and --
+        channels-last slices included -- strides, exactly as the parameters are views into flat_p."""
+        if not self.has_ema:
+            raise RuntimeError('FlatAdam.ema_views: this optimizer keeps no average (ema_decay=None)')
+        return [_arena_view(self.flat_ema, off, p, cl) for p, off, cl in zip(self.params, self.offsets, self.cl)]
+
+    def swap_ema(self):
+        """Exchange the CONTENTS of flat_p and flat_ema (the parameters alias flat_p and captured graphs hold its address, so
+        the arenas stay where they are).  Twice = nothing, bit for bit."""
+        if not self.has_ema:
+            raise RuntimeError('FlatAdam.swap_ema: this optimizer keeps no average (ema_decay=None)')
+        with torch.no_grad():
+            tmp = self.flat_p.clone()
+            self.flat_p.copy_(self.flat_ema)
+            self.flat_ema.copy_(tmp)
 
     def zero_grad(self, set_to_none=False):
         self.flat_g.zero_()
@@ -115,8 +149,12 @@ class FlatAdam:
         self.sync_hyper(grad_scale)
         self.step_count += 1
         k = self.numel_active
-        ops.adam_flat_step(self.flat_p[:k], self.flat_g[:k], self.flat_m[:k], self.flat_v[:k], self.hyper,
-                           skips_m=self.betas[0] == 0.0 and self._wd == 0.0)
+        skips_m = self.betas[0] == 0.0 and self._wd == 0.0
+        if self.has_ema:
+            ops.adam_flat_ema_step(self.flat_p[:k], self.flat_g[:k], self.flat_m[:k], self.flat_v[:k], self.flat_ema[:k], self.hyper,
+                                   self.ema_hyper, skips_m=skips_m)
+        else:
+            ops.adam_flat_step(self.flat_p[:k], self.flat_g[:k], self.flat_m[:k], self.flat_v[:k], self.hyper, skips_m=skips_m)
         self._g_is_last_step = True
 
     def _layout(self):
@@ -142,11 +180,15 @@ class FlatAdam:
         """`m_valid`: False when the saved first moment is NOT the optimizer's -- beta1 == 0 / no weight decay steps leave
         flat_m untouched, and outside the window between step() and the next zero_grad() the gradient it would be formed from is
         gone.  Harmless for a resume at beta1 == 0 (the next step overwrites m); a run resumed with another beta1 (--no_TTUR: 0.5)
-        must not trust an invalid m: load_state_dict then starts it from zeros."""
+        must not trust an invalid m: load_state_dict then starts it from zeros.
+        With an average (ema_decay) the state also carries `ema`, the flat_ema arena in the layout of m and v."""
         skipped = self.betas[0] == 0.0 and self._wd == 0.0 and self.step_count > 0
         valid = (not skipped) or bool(self.__dict__.get('_g_is_last_step', False))
-        return {'step': self.step_count, 'm': self._first_moment(), 'v': self.flat_v, 'lr': self.param_groups[0]['lr'], 'layout': self._layout(),
-                'm_valid': valid}
+        sd = {'step': self.step_count, 'm': self._first_moment(), 'v': self.flat_v, 'lr': self.param_groups[0]['lr'], 'layout': self._layout(),
+              'm_valid': valid}
+        if self.has_ema:
+            sd['ema'] = self.flat_ema                        # (same layout as m and v; absent without an average)
+        return sd
 
     def load_state_dict(self, sd, trust_param_order=False):
         """Moments saved by another FlatAdam.  With a `layout` that carries `shapes` the parameter signature must match; the
@@ -178,9 +220,17 @@ class FlatAdam:
                 raise ValueError('FlatAdam.load_state_dict: layout-less state of another total length')
             return self._load_torch_order(sd)
         self.step_count = int(sd['step'])
-        self.flat_m.copy_(sd['m'])
-        self.flat_v.copy_(sd['v'])
+        for flat, key in self._state_arenas(sd):
+            flat.copy_(sd[key])
         self._finish_load(sd)
+
+    def _state_arenas(self, sd):
+        """(arena, state key) pairs a load fills: m, v and -- when this optimizer keeps an average and the state carries one -- ema
+        (a state without `ema` leaves the average as it is)."""
+        pairs = [(self.flat_m, 'm'), (self.flat_v, 'v')]
+        if self.has_ema and 'ema' in sd:
+            pairs.append((self.flat_ema, 'ema'))
+        return pairs
 
     def _finish_load(self, sd):
         if not sd.get('m_valid', True) and not (self.betas[0] == 0.0 and self._wd == 0.0):
@@ -194,7 +244,7 @@ class FlatAdam:
         """Same parameters (signature checked by the caller), other memory order: copied per parameter through views."""
         with torch.no_grad():
             for i, p in enumerate(self.params):
-                for flat, key in ((self.flat_m, 'm'), (self.flat_v, 'v')):
+                for flat, key in self._state_arenas(sd):
                     src = _arena_view(sd[key].to(flat.device), offsets[i], p, cl_flags[i])
                     _arena_view(flat, self.offsets[i], p, self.cl[i]).copy_(src)
         self._finish_load(sd)
@@ -207,7 +257,7 @@ class FlatAdam:
         with torch.no_grad():
             for i, p in enumerate(self.params):
                 n = p.numel()
-                for flat, key in ((self.flat_m, 'm'), (self.flat_v, 'v')):
+                for flat, key in self._state_arenas(sd):
                     _arena_view(flat, self.offsets[i], p, self.cl[i]).copy_(sd[key][off:off + n].view(p.shape))
                 off += (n + _ALIGN - 1) // _ALIGN * _ALIGN
         self._finish_load(sd)

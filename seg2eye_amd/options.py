@@ -32,6 +32,9 @@ _DEFAULTS = dict(
     no_overlap_allreduce=False,  # data parallel: exchange all gradients after the backward instead of group by group during it
     grad_dtype='fp32',         # data parallel: what travels in the gradient exchange ('fp32' | 'bf16': half the bytes, distributed.FlatGradSync)
     grad_exchange='allreduce',  # 'allreduce' (the backend's all-reduce) | 'direct' (all-to-all + owner sum + all-gather over the xGMI mesh)
+    ema_decay=0.0,             # > 0: exponential moving average of netG + netE's weights, kept by the Adam launch (optim.FlatAdam); 0 = off
+    ema_start=0,               # optimizer steps during which the average just copies the weights (counted from a resume, like the moments)
+    use_ema=False,             # test.py: load <epoch>_net_{G,E}_ema.pth instead of the live weights
 )
 
 
@@ -107,6 +110,12 @@ _CLI = [  # (name, type or 'flag', default, choices)
     ('grad_dtype', _S, 'fp32', ['fp32', 'bf16']), ('grad_exchange', _S, 'allreduce', ['allreduce', 'direct']),
     ('synthetic_size', _I, 64, None),        # samples per epoch of the synthetic dataset
 ]
+_CLI_TRAIN_BUILD = [
+    ('ema_decay', _F, 0.0, None), ('ema_start', _I, 0, None),        # averaged generator weights; 0 = off
+]
+_CLI_TEST_BUILD = [
+    ('use_ema', 'flag', False, None),                                 # score / generate with the averaged weights' checkpoint files
+]
 _CLI_TRAIN = [
     ('display_freq', _I, 5000, None), ('print_freq', _I, 500, None), ('save_latest_freq', _I, 5000, None),
     ('save_epoch_freq', _I, 1, None), ('full_val_freq', _I, 50000, None), ('no_html', 'flag', False, None), ('tf_log', 'flag', False, None),
@@ -127,7 +136,7 @@ _CLI_TEST = [
 
 def build_parser(is_train=True):
     ap = argparse.ArgumentParser(description='seg2eye_amd %s options (flag-compatible with the reference)' % ('train' if is_train else 'test'))
-    for name, typ, default, choices in _CLI + (_CLI_TRAIN if is_train else _CLI_TEST):
+    for name, typ, default, choices in _CLI + (_CLI_TRAIN + _CLI_TRAIN_BUILD if is_train else _CLI_TEST + _CLI_TEST_BUILD):
         if not is_train and name in ('serial_batches', 'no_flip'):
             default = True                                 # options/test_options.py: parser.set_defaults(serial_batches=True, no_flip=True)
         if typ == 'flag':
@@ -148,6 +157,8 @@ def parse(argv=None, is_train=True):
             setattr(opt, k, v)
     if not is_train:
         opt.continue_train = False
+    if not 0.0 <= opt.ema_decay < 1.0 or opt.ema_start < 0:
+        raise ValueError('--ema_decay must lie in [0, 1) (0 = off) and --ema_start must not be negative')
     # train.py replays each step as hipGraphs BY DEFAULT (round 4: the replayed step is 15 % faster than ~900 individual launches
     # on a slow host, and the overlapped gradient exchange replays graph segments); --no_hip_graphs launches eagerly.  A failed
     # capture falls back to eager launches by itself, a batch of another shape runs eagerly for that step.  (--hip_graphs is

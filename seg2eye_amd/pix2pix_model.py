@@ -115,7 +115,10 @@ class Pix2PixModel(nn.Module):
             beta1, beta2, G_lr, D_lr = opt.beta1, opt.beta2, opt.lr, opt.lr
         else:
             beta1, beta2, G_lr, D_lr = 0.0, 0.9, opt.lr / 2, opt.lr * 2
-        optimizer_G = FlatAdam(G_params, lr=G_lr, betas=(beta1, beta2), weight_decay=opt.weight_decay, never_updated=dead)
+        # --ema_decay: the average of netG + netE (only: D keeps none) lives in optimizer G's fifth arena, kept by its Adam launch
+        ema = float(getattr(opt, 'ema_decay', 0.0) or 0.0)
+        optimizer_G = FlatAdam(G_params, lr=G_lr, betas=(beta1, beta2), weight_decay=opt.weight_decay, never_updated=dead,
+                               ema_decay=ema if ema > 0 else None, ema_start=int(getattr(opt, 'ema_start', 0) or 0))
         bounds, k = [0], 0
         for cnt in self._arena_groups_G:
             k += cnt
@@ -126,10 +129,14 @@ class Pix2PixModel(nn.Module):
                                weight_decay=opt.weight_decay) if opt.isTrain else None
         return optimizer_G, optimizer_D
 
-    def save(self, epoch):
+    def save(self, epoch, ema_of=None):
+        """ema_of ({id(parameter): averaged value}, from the trainer when --ema_decay is on): also `<epoch>_net_{G,E}_ema.pth`."""
         checkpoint.save_network(self.netG, 'G', epoch, self.opt)
         checkpoint.save_network(self.netD, 'D', epoch, self.opt)
         checkpoint.save_network(self.netE, 'E', epoch, self.opt)
+        if ema_of is not None:
+            checkpoint.save_network_ema(self.netG, 'G', epoch, self.opt, ema_of)
+            checkpoint.save_network_ema(self.netE, 'E', epoch, self.opt, ema_of)
 
     # ------------------------------------------------------------------ helpers
     def device(self):
@@ -140,8 +147,10 @@ class Pix2PixModel(nn.Module):
         netD = networks.define_D(opt) if opt.isTrain else None
         netE = networks.define_E(opt)
         if not opt.isTrain or opt.continue_train:
-            checkpoint.load_network(netG, 'G', opt.which_epoch, opt)
-            checkpoint.load_network(netE, 'E', opt.which_epoch, opt)
+            # test.py --use_ema: the averaged weights' files (same keys; a missing file is an error that names it)
+            tag = '_ema' if (not opt.isTrain and getattr(opt, 'use_ema', False)) else ''
+            checkpoint.load_network(netG, 'G' + tag, opt.which_epoch, opt)
+            checkpoint.load_network(netE, 'E' + tag, opt.which_epoch, opt)
             if opt.isTrain:
                 checkpoint.load_network(netD, 'D', opt.which_epoch, opt)
         return netG, netD, netE

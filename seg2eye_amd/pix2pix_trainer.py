@@ -1,6 +1,7 @@
 """Pix2PixTrainer (reference trainers/pix2pix_trainer.py:8-88): owns the model and the two optimizers,
 runs one G step / one D step, LR decay, save.  Multi-GPU: when torch.distributed is initialised the
 flat gradient arenas are sum-all-reduced (RCCL) between backward and the Adam launch."""
+import contextlib
 import os
 
 from .distributed import FlatGradSync, broadcast_buffers, broadcast_flat, exchange_active, world_size
@@ -70,8 +71,12 @@ class Pix2PixTrainer:
                     print('seg2eye_amd: --norm_G %s with %d replicas exchanges batch statistics inside the step: the steps run '
                           'as individual launches (no hipGraphs)' % (opt.norm_G, world_size()), file=sys.stderr)
                 self.opt.hip_graphs = False
+            if self.optimizer_G.has_ema and opt.continue_train:
+                self._load_ema()
             broadcast_flat(self.optimizer_G.flat_p)          # identical replicas at step 0: parameters ...
             broadcast_flat(self.optimizer_D.flat_p)
+            if self.optimizer_G.has_ema:
+                broadcast_flat(self.optimizer_G.flat_ema)    # ... their average (from here on every replica computes the same one) ...
             self.sync_replica_buffers()                      # ... and spectral-norm u, v / BatchNorm running statistics
 
     def sync_replica_buffers(self):
@@ -153,6 +158,8 @@ class Pix2PixTrainer:
 
     def run_generator_one_step(self, data):
         """trainers/pix2pix_trainer.py:26-35.  With opt.hip_graphs the body is one graph replay."""
+        if self.__dict__.get('_in_ema_scope'):
+            raise RuntimeError('a generator step inside ema_scope() would train the averaged weights')
         self._train_mode()
         if self.use_graphs and self._stage_inputs(data):     # (captures on first use; turns graphs off if that fails)
             self.graph_G.replay(self.sync_G.launch)          # (segment k, then group k's exchange beside segment k+1)
@@ -311,7 +318,65 @@ class Pix2PixTrainer:
         return self.generated
 
     def save(self, epoch):
-        self.pix2pix_model_on_one_gpu.save(epoch)
+        self.pix2pix_model_on_one_gpu.save(epoch, ema_of=self._ema_of() if self.has_ema else None)
+
+    # ---- averaged generator weights (--ema_decay) ------------------------------------------
+    @property
+    def has_ema(self):
+        return bool(self.opt.isTrain and self.optimizer_G.has_ema)
+
+    def _ema_of(self):
+        """{id(parameter): its averaged value} over optimizer G's parameters (netG + netE)."""
+        og = self.optimizer_G
+        return {id(p): e for p, e in zip(og.params, og.ema_views())}
+
+    def _load_ema(self):
+        """--continue_train: `<which_epoch>_net_{G,E}_ema.pth` into the average when both exist; otherwise the average restarts
+        from the loaded live weights (flat_ema is a copy of flat_p at construction).  Either way --ema_start counts from the
+        resume: it is compared with the optimizer's own step count, which restarts at 0 like the moments."""
+        from . import checkpoint
+        m, opt = self.pix2pix_model, self.opt
+        if checkpoint.ema_files_exist(opt.which_epoch, opt):
+            ema_of = self._ema_of()
+            checkpoint.load_ema(m.netG, 'G', opt.which_epoch, opt, ema_of)
+            checkpoint.load_ema(m.netE, 'E', opt.which_epoch, opt, ema_of)
+        else:
+            print('seg2eye_amd: no averaged checkpoint (%s_net_{G,E}_ema.pth) to resume from: the average restarts from the '
+                  'loaded weights' % opt.which_epoch, flush=True)
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """Inside: netG / netE's parameters hold the averaged values; on exit the live ones again, bit for bit.
+        The CONTENTS of flat_p and flat_ema are exchanged (the parameters alias flat_p and captured graphs hold its address).
+        Nothing derived from the weights outlives the exchange: sigma and the weight packs are recomputed from the masters at
+        the top of every forward (spectral.sn_begin, packing.PackPlan.run), the SPADE prepass and the style bank keep addresses,
+        not values.  Buffers outside the arena -- spectral-norm u|v, BatchNorm running statistics -- are shared with the live
+        network; since a pass may run in TRAIN mode here (train.py's validation does) and would move them, they are snapshotted
+        on entry and put back on exit, as `_capture` does around its warm-up passes: a pass on the averaged weights leaves no
+        trace in the live training state.  Not re-entrant; no optimizer step inside."""
+        if not self.has_ema:
+            raise RuntimeError('ema_scope: this trainer keeps no averaged weights (--ema_decay 0)')
+        if self.__dict__.get('_in_ema_scope'):
+            raise RuntimeError('ema_scope is not re-entrant')
+        import torch
+        from .spectral import ensure_bank
+        m = self.pix2pix_model
+        nets = (m.netG, m.netE)
+        bufs = [b.uv_arena for b in (ensure_bank(net) for net in nets) if b is not None]
+        bufs += [t for net in nets for mod in net.modules()
+                 if isinstance(mod, torch.nn.modules.batchnorm._BatchNorm) and mod.track_running_stats
+                 for t in (mod.running_mean, mod.running_var, mod.num_batches_tracked)]
+        snap = [t.clone() for t in bufs]
+        self.optimizer_G.swap_ema()
+        self._in_ema_scope = True
+        try:
+            yield self
+        finally:
+            self._in_ema_scope = False
+            self.optimizer_G.swap_ema()
+            with torch.no_grad():
+                for t, s0 in zip(bufs, snap):
+                    t.copy_(s0)
 
     def update_learning_rate(self, epoch):
         """Constant for niter epochs, then linear to 0 over niter_decay, keeping TTUR's 1/2 : 2 ratio

@@ -6,6 +6,7 @@
     `mse/<key>/full/relative`;
   * otherwise: writes one uint8 `.npy` of shape (1, 640, 400) per sample under
     `<checkpoints_dir>/<name>/<results_dir>/<dataset_key>/` plus `pred_npy_list.txt` (util/tester.py:193-219).
+`--use_ema` loads `<which_epoch>_net_{G,E}_ema.pth` -- the averaged weights a `train.py --ema_decay` run saved -- instead.
 Data: `--dataset_mode synthetic` (the OpenEDS H5 pipeline is SURVEY 8 f4)."""
 import sys
 

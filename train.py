@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Training entry point, flag-compatible with the reference's train.py (train.py:23-116): same option names and defaults
 (seg2eye_amd/options.py), same loop -- G step when `i % D_steps_per_G == 0`, then the D step -- same LR schedule,
-same checkpoint files (`<checkpoints_dir>/<name>/<epoch>_net_{G,D,E}.pth`, reference state-dict keys) and `iter.txt`
+same checkpoint files (`<checkpoints_dir>/<name>/<epoch>_net_{G,D,E}.pth`, reference state-dict keys; with `--ema_decay d` also
+`<epoch>_net_{G,E}_ema.pth`, the averaged generator weights, which the validation passes then score) and `iter.txt`
 resume record, same validation passes -- every `--display_freq` samples a quick one (`--validation_limit` samples), every
 `--full_val_freq` samples a full one, on the train and validation splits, scored with the OpenEDS metric on the device
 (seg2eye_amd/tester.py).  Not carried over (out of scope): the visualizer / TF logging, source-tree copy.
@@ -10,6 +11,7 @@ Data: `--dataset_mode synthetic` (default) or `openeds` (an H5 file at `--dataro
     python train.py --name run1 --batchSize 8 --aspect_ratio 1.0 --niter 1 --niter_decay 0
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 train.py ...
 """
+import contextlib
 import sys
 import traceback
 
@@ -54,16 +56,24 @@ class TrainingRun:
         head = '(epoch: %d, iters: %d, time: %.3f) ' % (self.epoch, c.total_steps_so_far, c.time_per_iter)
         print(head + ' '.join('%s: %.3f' % (name, float(v.float().mean())) for name, v in losses.items()), flush=True)
 
+    def _weights(self):
+        """The weights a validation pass scores: the averaged ones (--ema_decay; trainer.ema_scope exchanges them in and restores
+        the live ones and every buffer the pass moved) or the model as it is."""
+        if self.testers and self.trainer.has_ema:            # (rank 0 only: its arenas are exchanged and restored locally)
+            print('validating the averaged weights (ema_decay %g)' % self.opt.ema_decay, flush=True)
+            return self.trainer.ema_scope()
+        return contextlib.nullcontext()
+
     def quick_validation(self):
         # (the reference validates the model as it is: train mode.  solo: only rank 0 is here -- no per-layer exchange)
-        with torch.no_grad(), dist.solo():
+        with torch.no_grad(), dist.solo(), self._weights():
             for t in self.testers:
                 t.run_partial_modes(model=self.trainer.pix2pix_model, epoch=self.epoch, n_steps=self.counter.total_steps_so_far,
                                     log=True, visualize_images=False, limit=self.opt.validation_limit)
         self.trainer.sync_replica_buffers()                      # rank 0's train-mode pass advanced its u, v / BN statistics
 
     def full_validation(self):
-        with torch.no_grad(), dist.solo():
+        with torch.no_grad(), dist.solo(), self._weights():
             for t in self.testers:
                 t.run(self.trainer.pix2pix_model, mode='full', epoch=self.epoch, n_steps=self.counter.total_steps_so_far,
                       log=True, write_error_log=self.opt.write_error_log)
