@@ -7,7 +7,8 @@ import torch
 from .. import _lib as L
 from .. import packing
 from .._lib import ConvDesc, ACT_NONE, ACT_LRELU, ACT_TANH, AUX_NONE, AUX_LRELU_GRAD
-from .core import GradSink, IN_EPS, LaunchProfiler, ZeroPool, _cl_dense, _cl_rows, _dt, _grad_dst, _need, _p, _stream, colsum
+from .core import IN_EPS, LaunchProfiler, ZeroPool, _cl_dense, _cl_rows, _dt, _grad_dst, _need, _p, _stream, colsum, memo
+from .sink import GradSink
 
 
 # ------------------------------------------------------------------------------ raw launchers
@@ -63,7 +64,9 @@ def packed_weight(w, dtype, cin_pad, transposed, sigma, plan, generation=None, s
     return pack_weight(w, dtype, cin_pad, transposed, sigma, plane)
 
 
-_PLANE_MODES = {}
+def _plane_query(shape):
+    d = ConvDesc(*shape)
+    return int(L.lib().s2e_conv2d_plane_supported(L.S2E_BF16, C.byref(d)))
 
 
 def plane_mode(x_dtype, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, transposed, in_act=ACT_NONE, out_act=ACT_NONE, aux_mode=AUX_NONE,
@@ -73,11 +76,7 @@ def plane_mode(x_dtype, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, trans
     if x_dtype != torch.bfloat16 or (has_res and aux_mode != AUX_NONE):
         return 0
     key = (n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, int(transposed), in_act, out_act, aux_mode)
-    v = _PLANE_MODES.get(key)
-    if v is None:
-        d = ConvDesc(*key)
-        v = _PLANE_MODES[key] = int(L.lib().s2e_conv2d_plane_supported(L.S2E_BF16, C.byref(d)))
-    return v
+    return memo('plane', key, _plane_query, key)
 
 
 # profiler families = the kernel s2e_conv2d / s2e_conv2d_wgrad choose for the shape (S2E_KERNEL_GENERIC / SMALL / PATCH)
@@ -100,16 +99,15 @@ def _conv_plan(wgrad, dt, *shape):
             _CONV_PLANS.clear()
         ent = _CONV_PLANS[key] = (d, wsb)
     return ent
-_CONV_STATS_SLOTS = {}
 
 
 def _conv_stats_slots(dt, d, *shape):
     """s2e_conv2d_stats_slots, memoised per shape."""
-    key = (dt,) + shape
-    v = _CONV_STATS_SLOTS.get(key)
-    if v is None:
-        v = _CONV_STATS_SLOTS[key] = int(L.lib().s2e_conv2d_stats_slots(dt, C.byref(d)))
-    return v
+    return memo('stats_slots', (dt,) + shape, _stats_slots_query, dt, d)
+
+
+def _stats_slots_query(dt, d):
+    return int(L.lib().s2e_conv2d_stats_slots(dt, C.byref(d)))
 
 
 def conv2d_raw(x, wp, bias, residual, aux, out_hw_c, kh, kw, stride, pad, transposed=False,
@@ -163,15 +161,14 @@ def conv2d_raw(x, wp, bias, residual, aux, out_hw_c, kh, kw, stride, pad, transp
     return y
 
 
-def conv2d_wgrad_raw(x, gy, kh, kw, stride, pad, in_act=ACT_NONE, want_bias=False, dbias_out=None, dw_out=None, gy_shared=False,
-                     defer_ok=False):
+def conv2d_wgrad_raw(x, gy, kh, kw, stride, pad, in_act=ACT_NONE, want_bias=False, dbias_out=None, dw_out=None, defer_ok=False):
     """-> (dw, db): dw (Cout, KH*KW*Cin) fp32 in packed order; db (Cout) fp32 or None.  Both live in one
     zero-filled buffer (ZeroPool scratch when the bias gradient is not returned).  dbias_out: an fp32 (Cout) tensor to ACCUMULATE the bias
     gradient into instead (e.g. the parameter's slice of the gradient arena); then db is None.
     dw_out: an fp32 (Cout, KH*KW*Cin) row-major tensor to ACCUMULATE the weight gradient into instead of a fresh zeroed buffer
     (the gradient of a parameter stored channels-last: _cl_rows(p.grad)); returned as dw.
     Inside a trainer step the patch-resident 3x3 shapes are QUEUED (GradSink.push_wgrad): dw / dbias_out then receive the sums at
-    the step's next flush.  gy_shared: gy is also handed on as another tensor's gradient (see push_wgrad).
+    the step's next flush; the queue then holds gy itself (whoever would add to it in place asks GradSink.is_pinned).
     defer_ok: the caller reads dw / db only through jobs queued in the same GradSink (or not at all before the flush: an arena slice):
     a generic shape may then be queued too (GradSink.push_gwg: every generic weight gradient of a backward as one launch)."""
     _need(x, gy, dbias_out, dw_out)
@@ -190,10 +187,9 @@ def conv2d_wgrad_raw(x, gy, kh, kw, stride, pad, in_act=ACT_NONE, want_bias=Fals
         dw, db = ZeroPool.take(cout * k, torch.float32, x.device).view(cout, k), None
     dbp = db if own_b else dbias_out
     if (kh == 3 and kw == 3 and stride == 1 and pad == 1 and in_act == ACT_NONE and not own_b and ho == hi and wo == wi
-            and GradSink.push_wgrad(x, gy, dw, dbp, gy_shared=gy_shared)):
+            and GradSink.push_wgrad(x, gy, dw, dbp)):
         return dw, db                                        # accumulated at the step's next flush, with every other queued layer
-    if defer_ok and not own_b and GradSink.push_gwg(x, gy, dw, dbp, (n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, 0, in_act, ACT_NONE, AUX_NONE),
-                                                    gy_shared=gy_shared):
+    if defer_ok and not own_b and GradSink.push_gwg(x, gy, dw, dbp, (n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, 0, in_act, ACT_NONE, AUX_NONE)):
         return dw, db
     d, wsb = _conv_plan(True, _dt(x), n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, 0, in_act, ACT_NONE, AUX_NONE)
     ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device) if wsb else None
@@ -350,7 +346,6 @@ class Conv2dFn(torch.autograd.Function):
                             True, ACT_NONE, ACT_NONE, am, plane=pm > 0)
         want_b = has_bias and ctx.needs_input_grad[2]
         wdst = ctx.wdst
-        shared = bool(has_res and ctx.needs_input_grad[3])   # g goes on as the residual's gradient (and may be added to in place there)
         direct = ctx.needs_input_grad[1] and wdst is not None and cx == cin and cin % 8 == 0 and _cl_dense(wdst)
         if direct and sigma is not None and not GradSink.inplace_allowed(wdst):
             direct = False                                   # (the chain rule must ACCUMULATE here: packed scratch, below)
@@ -360,8 +355,7 @@ class Conv2dFn(torch.autograd.Function):
             # the parameter's gradient lies in the packed order (channels-last arena, or any 1x1 conv; Cin % 8 == 0 -- a 1-channel
             # weight is "channels-last" too, but the in-place kernels work on 16-byte groups of one tap): the kernel accumulates
             # straight into it; spectral norm's chain rule is then applied in place (queued: one launch pair per step)
-            _, gb = conv2d_wgrad_raw(x, g, kh, kw, stride, pad, in_act, want_b, ctx.bdst if want_b else None, dw_out=_cl_rows(wdst),
-                                     gy_shared=shared, defer_ok=True)
+            _, gb = conv2d_wgrad_raw(x, g, kh, kw, stride, pad, in_act, want_b, ctx.bdst if want_b else None, dw_out=_cl_rows(wdst), defer_ok=True)
             if sigma is not None:
                 GradSink.push_inplace(_cl_rows(wdst), weight, u, v, sigma, cout, cin, kh * kw)
         elif ctx.needs_input_grad[1]:
@@ -369,7 +363,7 @@ class Conv2dFn(torch.autograd.Function):
             if wdst is not None and not wdst.is_contiguous():
                 wdst = None                                  # (a channels-last .grad fed a channel-padded input: through autograd)
             # (with a .grad to accumulate into, the packed dW is read by jobs queued in the step's GradSink only: it may be queued itself)
-            dwp, gb = conv2d_wgrad_raw(x, g, kh, kw, stride, pad, in_act, want_b, bdst, gy_shared=shared, defer_ok=wdst is not None)
+            dwp, gb = conv2d_wgrad_raw(x, g, kh, kw, stride, pad, in_act, want_b, bdst, defer_ok=wdst is not None)
             w_oihw = weight.detach() if weight.is_contiguous() else weight.detach().contiguous()
             if sigma is None:
                 if wdst is not None:
@@ -387,7 +381,7 @@ class Conv2dFn(torch.autograd.Function):
         elif want_b:
             gb = colsum(g)
         if has_res and ctx.needs_input_grad[3]:
-            gres = g
+            gres = g                                         # (a queued weight-gradient job still reads g: GradSink.is_pinned)
         return gx, gw, gb, gres, None, None, None, None, None, None, None, None
 
 

@@ -2,15 +2,16 @@
 [gamma | beta] branch with its label-sparse forward and backward, the modulation (two-launch and fused into the conv), plain InstanceNorm."""
 import ctypes as C
 
-import numpy as np
 import torch
 
 from .. import _lib as L
 from .. import packing
 from .._lib import NORM_SPADE_STYLE_BATCH, NORM_ACCUMULATE_DX, ACT_NONE, AUX_NONE, AUX_RELU_MASK, NORM_SPADE_STYLE
 from . import switches
-from .core import (GradSink, IN_EPS, LaunchProfiler, ZeroPool, _adjacent, _byref, _cl_dense, _cl_rows, _dt, _grad_dst, _need, _p, _span2, _stream)
-from .conv import _CONV_STATS_SLOTS, _conv_plan, _unpack_dw, conv2d_raw, conv2d_wgrad_raw, packed_weight, unpack_weight_grad_into
+from .core import (IN_EPS, LaunchProfiler, ZeroPool, _adjacent, _byref, _cl_dense, _cl_rows, _dt, _grad_dst, _need, _p, _span2, _stream,
+                   device_job_table, memo)
+from .sink import GradSink
+from .conv import _conv_plan, _unpack_dw, conv2d_raw, conv2d_wgrad_raw, packed_weight, unpack_weight_grad_into
 
 
 def in_stats(x, return_sums=False):
@@ -113,12 +114,9 @@ class SpadePrepass:
                 entries.append((w_sh.data_ptr(), h, w, off, (n, h, w, cout)))
                 off += (n * h * w * cout * esz + 255) // 256 * 256
                 plan['pins'] += [(w_sh, w_sh.data_ptr())] + ([(b_sh, b_sh.data_ptr())] if b_sh is not None else [])   # (the objects the ops were handed: a re-homed Parameter shows here)
-            nb = lib.s2e_label_conv_block_map(dt, C.byref(jobs), len(rec['conv']), n, None)
-            bm = np.zeros(3 * nb, dtype=np.int32)
-            lib.s2e_label_conv_block_map(dt, C.byref(jobs), len(rec['conv']), n, bm.ctypes.data)
-            plan['conv'] = dict(jobs=torch.from_numpy(np.frombuffer(bytes(jobs), dtype=np.uint8).copy()).to(dev),
-                                map=torch.from_numpy(bm).to(dev), nb=int(nb), bytes=off, entries=entries,
-                                ncls=rec['conv'][0][0].shape[1])
+            jobs_dev, map_dev, nb = device_job_table(
+                jobs, lambda bm: lib.s2e_label_conv_block_map(dt, C.byref(jobs), len(rec['conv']), n, bm), 3, dev)
+            plan['conv'] = dict(jobs=jobs_dev, map=map_dev, nb=nb, bytes=off, entries=entries, ncls=rec['conv'][0][0].shape[1])
         if rec['table']:
             jobs = (L.ClassTableJob * len(rec['table']))()
             off, entries = 0, []
@@ -128,11 +126,9 @@ class SpadePrepass:
                 entries.append((wp.data_ptr(), off, (ncls, 5, 5, 2 * c)))
                 off += ncls * 25 * 2 * c * 4
                 plan['pins'] += [(w_sh, w_sh.data_ptr()), (b_sh, b_sh.data_ptr()), (wp, wp.data_ptr()), (b_f, b_f.data_ptr())]
-            nb = lib.s2e_class_table_block_map(C.byref(jobs), len(rec['table']), None)
-            bm = np.zeros(2 * nb, dtype=np.int32)
-            lib.s2e_class_table_block_map(C.byref(jobs), len(rec['table']), bm.ctypes.data)
-            plan['table'] = dict(jobs=torch.from_numpy(np.frombuffer(bytes(jobs), dtype=np.uint8).copy()).to(dev),
-                                 map=torch.from_numpy(bm).to(dev), nb=int(nb), bytes=off, entries=entries, ncls=rec['table'][0][6])
+            jobs_dev, map_dev, nb = device_job_table(
+                jobs, lambda bm: lib.s2e_class_table_block_map(C.byref(jobs), len(rec['table']), bm), 2, dev)
+            plan['table'] = dict(jobs=jobs_dev, map=map_dev, nb=nb, bytes=off, entries=entries, ncls=rec['table'][0][6])
         return plan
 
     def _run(self, plan, label, dtype):
@@ -330,11 +326,7 @@ def _sparse_bwd_lists(ctx, g, h, w, cch, nh, ncls):
         return None
     n = g.shape[0]
     d, _ = _conv_plan(False, _dt(g), n, h, w, 2 * cch, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK)
-    key = ('rects_supported', n, h, w, cch, nh)
-    ok = _CONV_STATS_SLOTS.get(key)
-    if ok is None:
-        ok = _CONV_STATS_SLOTS[key] = bool(L.lib().s2e_conv2d_rects_supported(_dt(g), _byref(d)))
-    if not ok:
+    if not memo('rects_supported', (n, h, w, cch, nh), lambda: bool(L.lib().s2e_conv2d_rects_supported(_dt(g), _byref(d)))):
         return None
     ck = ('rects_bwd', cls.data_ptr(), h, w)
     ent = pool.step_cache.get(ck)
@@ -354,10 +346,7 @@ def _sparse_wgrad(g, actv, gb_dst, sp):
     n, h, w, nh = actv.shape
     c2 = g.shape[-1]
     d, _ = _conv_plan(True, _dt(g), n, h, w, nh, h, w, c2, 3, 3, 1, 1, 0, ACT_NONE, ACT_NONE, AUX_NONE)
-    key = ('wgrad_rects_ws', n, h, w, nh, c2)
-    wsb = _CONV_STATS_SLOTS.get(key)
-    if wsb is None:
-        wsb = _CONV_STATS_SLOTS[key] = int(L.lib().s2e_conv2d_wgrad_rects_workspace_bytes(_dt(g), _byref(d)))
+    wsb = memo('wgrad_rects_ws', (n, h, w, nh, c2), lambda: int(L.lib().s2e_conv2d_wgrad_rects_workspace_bytes(_dt(g), _byref(d))))
     dw, db = gb_dst
     if not wsb or db is None or w_strides_differ(dw):
         return False
@@ -434,9 +423,8 @@ def _spade_param_grads(ctx, g, label, w_sh, w_gb, actv):
             's2e_spade_uniform_sums'), nbytes=float(g.numel() * g.element_size() * (1.0 - frac) * 1.27))
         wdst, bdst = ctx.sh_dst
         assert uni_gb is None or tuple(w_gb.stride()) == tuple(uni_gb[0].stride()), 'weight and gradient arenas are laid out alike'
-        ZeroPool.active().sink.uni.append((R, A, w_gb.detach(), w_sh.detach(), ctx.b_sh_f, wdst, bdst,
-                                           uni_gb[0] if uni_gb is not None else None, uni_gb[1] if uni_gb is not None else None, c2, nh, ncls,
-                                           int(g.dtype == torch.bfloat16)))
+        dw_gb, db_gb = uni_gb if uni_gb is not None else (None, None)
+        GradSink.push_uniform(R, A, w_gb.detach(), w_sh.detach(), ctx.b_sh_f, wdst, bdst, dw_gb, db_gb, c2, nh, ncls, g.dtype == torch.bfloat16)
     else:
         c8_rects = None
         dactv = conv2d_raw(g, wpt, None, None, actv, (h, w, nh), 3, 3, 1, 1, True, ACT_NONE, ACT_NONE, AUX_RELU_MASK)

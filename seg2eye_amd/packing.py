@@ -120,7 +120,8 @@ class PackPlan:
             bm_all = np.zeros(3 * max(nb_all, 1), dtype=np.int32)
             if nb_all:
                 lib.s2e_pack_block_map(dt, C.byref(rest), len(jobs) - n_cov, bm_all.ctypes.data)
-            jobs_dev = torch.from_numpy(np.frombuffer(bytes(arr), dtype=np.uint8).copy()).to(dev)
+            from .ops import upload_structs
+            jobs_dev = upload_structs(arr, dev)                  # (two block maps over this one array: filled by hand above)
             map_dev = (torch.from_numpy(bm).to(dev), torch.from_numpy(bm_all).to(dev), n_cov * C.sizeof(L.PackJob))
             max_taps = max(j['w'].shape[2] * j['w'].shape[3] for j in jobs)
             self.tables[dt] = (jobs_dev, map_dev, nb_fwd, nb_all, max_taps, jobs, n_fwd)

@@ -107,8 +107,8 @@ class SpectralBank:
                 for r0 in range(0, rows[i], _BR):
                     for c0 in range(0, cols[i], _BC):
                         bm.append((i, r0, c0))
-        raw = np.frombuffer(bytes(table), dtype=np.uint8).copy()
-        self.table_dev = torch.from_numpy(raw).to(dev)
+        from .ops import upload_structs
+        self.table_dev = upload_structs(table, dev)
         self.block_map = torch.tensor(maps[0], dtype=torch.int32, device=dev)
         self.block_map_t = torch.tensor(maps[1], dtype=torch.int32, device=dev)
         self.rows, self.cols = rows, cols

@@ -197,6 +197,31 @@ def test_ops_refuse_cpu_tensors():
         G(torch.zeros(1, 4, 64, 64), torch.zeros(1, 16))
 
 
+def test_grad_sink_drops_every_queue_of_a_failed_step():
+    """A trainer step that raises leaves nothing queued: a job surviving into the next scope would run there, on tensors of a
+    step that no longer exists (the in-place chain-rule queue used to).  Host bookkeeping only: CPU tensors, no library call."""
+    from seg2eye_amd import ops
+    queues = ('jobs', 'inplace', 'wg', 'gwg', 'c8', 'uni')
+    pool = ops.ZeroPool('cpu')
+    grad, weight = torch.zeros(16, 8, 3, 3), torch.zeros(16, 8, 3, 3)
+    with pytest.raises(ZeroDivisionError):
+        with pool.scope('G'):
+            assert ops.GradSink.push(torch.zeros(16, 72), grad, 16, 8, 9, 8)
+            ops.GradSink.push_inplace(grad.view(16, 72), weight, torch.zeros(16), torch.zeros(72), torch.ones(1), 16, 8, 9)
+            assert len(pool.sink.jobs) == 1 and len(pool.sink.inplace) == 1
+            pool.sink.inplace_done.add(1)
+            pool.sink.wg_done.add(2)
+            1 // 0
+    assert ops.ZeroPool.active() is None
+    assert {q: len(getattr(pool.sink, q)) for q in queues} == {q: 0 for q in queues}
+    with pool.scope('G'):                                    # a scope that ends normally with nothing queued
+        assert pool.sink.inplace_done == set() and pool.sink.wg_done == set()
+    assert ops.ZeroPool.active() is None
+    assert {q: len(getattr(pool.sink, q)) for q in queues} == {q: 0 for q in queues}
+    with pool.scope('D'):
+        assert pool.sink.inplace_done == set() and pool.sink.wg_done == set()
+
+
 def test_state_dict_layout_matches_reference():
     from seg2eye_amd import networks
     from seg2eye_amd.options import default_opt

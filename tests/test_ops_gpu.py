@@ -1145,7 +1145,7 @@ def test_wgrad_sink_fresh_arena_view_used_at_two_shapes(order):
         assert ops.ZeroPool.grad_is_fresh(dw)
         for x, gy in ((a, b) if order == 'queued_then_immediate' else (b, a)):
             ops.conv2d_wgrad_raw(x, gy, 3, 3, 1, 1, ops.ACT_NONE, False, None, dw_out=dw)
-        assert len(pool.sink.wg) == 1 and pool.sink.wg[0][6] is False        # queued, and told to add
+        assert len(pool.sink.wg) == 1 and pool.sink.wg[0].fresh is False       # queued, and told to add
     torch.cuda.synchronize()
     assert float((dw - ref).abs().max()) <= 2e-5 * float(ref.abs().max()) + 1e-6
 
