@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <type_traits>
 #include "../../include/seg2eye_hip.h"
 
@@ -71,6 +72,69 @@ template <typename T> __device__ __forceinline__ float load1(const T* p) { retur
 template <typename T> __device__ __forceinline__ void store1(T* p, float v) { *p = (T)v; }
 
 __device__ __forceinline__ float lrelu02(float v) { return v > 0.f ? v : 0.2f * v; }
+// LeakyReLU(0.2) on 16 B of packed T.  PK (bf16): round each pair with one v_cvt_pk_bf16_f32 (pack2_bf16) instead of pack16's
+// element-wise form; the bits are the same, the instructions are not, and each user keeps the form it was tuned with.
+template <typename T, bool PK = false>
+__device__ __forceinline__ u32x4_t lrelu16(u32x4_t r) {
+    float f[Vec<T>::N];
+    unpack16<T>(r, f);
+#pragma unroll
+    for (int j = 0; j < Vec<T>::N; ++j) f[j] = lrelu02(f[j]);
+    if constexpr (PK) return u32x4_t{pack2_bf16(f[0], f[1]), pack2_bf16(f[2], f[3]), pack2_bf16(f[4], f[5]), pack2_bf16(f[6], f[7])};
+    else return pack16<T>(f);
+}
+
+// ---------------------------------------------------------------- address spaces, LDS-DMA, counted waits
+typedef const __attribute__((address_space(1))) void* gptr_t;            // global
+typedef const __attribute__((address_space(1))) float* gptr_f32_t;
+typedef const __attribute__((address_space(1))) f32x4_t* gptr_f32x4_t;
+typedef __attribute__((address_space(3))) void* lptr_t;                  // LDS
+// 16 zero bytes: the source of the LDS-DMA lanes that are out of bounds (padding taps, rows / channels past the tensor)
+__device__ __attribute__((aligned(16))) const uint32_t s2e_zero16[4] = {0u, 0u, 0u, 0u};
+// LDS-DMA, 16 B per lane: the wave's 1 KiB lands lane-linear at dst (wave-uniform); src is per lane.  (conv_patch.hip calls the
+// builtin itself: through this helper its code changes.)
+__device__ __forceinline__ void lds_dma16(const void* src, void* dst) {
+    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+}
+// all but the newest N vector-memory operations (LDS-DMA included) of this wave are done
+template <int N> __device__ __forceinline__ void wait_vmcnt() {
+    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+    asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory");
+}
+// (the kernels' ladders over a run-time count -- conv_duo, conv_patch, conv_stream, conv_wgrad_flat -- stay with their kernels: their
+// shapes differ, and conv_duo's compiles to other code through a shared recursive form)
+// ds_read_b64_tr_b16, the hardware 4x16 transpose read (lane roles: conv_wgrad.hip)
+__device__ __forceinline__ u32x2_t lds_tr16_b64(const char* p) {
+    s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)p);
+    return __builtin_bit_cast(u32x2_t, v);
+}
+// two bf16 from two LDS addresses into one register: the low half by ds_read_u16 (zero-extended), the high half by
+// ds_read_u16_d16_hi into a second register, OR-ed after the wait.  (A d16_hi read does NOT preserve the other half on
+// this target -- with SRAM ECC the destination's unused half is written as zero -- so the pair cannot share a register.)
+#define S2E_U16_PAIR(lo, hi, addr, off_lo, off_hi) \
+    asm volatile("ds_read_u16 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "n"(off_lo) : "memory"); \
+    asm volatile("ds_read_u16_d16_hi %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(off_hi) : "memory")
+
+// ---------------------------------------------------------------- 32x32 MFMA on 16-B operands
+template <typename T> struct Mfma;
+template <> struct Mfma<bf16_t> {
+    static __device__ __forceinline__ void run(u32x4_t a, u32x4_t b, f32x16_t& acc) {
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a),
+                                                      __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
+    }
+};
+template <> struct Mfma<float> {
+    // lane half h holds 4 consecutive k; MFMA t pairs element t of half 0 with element t of half 1.
+    // A and B use the same (permuted) k order, so the contraction is exact.
+    // (vectors by value + whole-vector bit_cast: see the note at unpack16)
+    static __device__ __forceinline__ void run(u32x4_t a, u32x4_t b, f32x16_t& acc) {
+        const f32x4_t fa = __builtin_bit_cast(f32x4_t, a), fb = __builtin_bit_cast(f32x4_t, b);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0], fb[0], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[1], fb[1], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[2], fb[2], acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[3], fb[3], acc, 0, 0, 0);
+    }
+};
 
 // ---------------------------------------------------------------- wave / block reductions
 __device__ __forceinline__ float wave_sum(float v) {
@@ -119,3 +183,14 @@ static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 // weight gradient's bias sums through the workspace -- so that two runs of a trainer produce the same bits.
 // Costs ~0.5 ms per step; off by default.  (The logged loss VALUES and the bilinear resize's backward still use float atomics.)
 int s2e_deterministic(void);
+
+// compute units of the current device (read once per process); 256 when there is no device (planning calls on a CPU-only machine)
+int s2e_cu_count(void);
+
+// Environment switches (DESIGN.md section 4 lists every one).  Callers keep the value in a function-local static: read once per process.
+static inline int s2e_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+static inline bool s2e_env_flag(const char* name, bool dflt) { return s2e_env_int(name, dflt) != 0; }
+// the value when it is set and >= lo, else the default
+static inline int s2e_env_int_ge(const char* name, int lo, int dflt) { const int v = s2e_env_int(name, dflt); return v >= lo ? v : dflt; }
+static inline long s2e_env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
+static inline double s2e_env_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }

@@ -35,7 +35,6 @@ constexpr int C8_LDS = C8_ROWS * C8_MAXPITCH * 16;      // 47,360 B
 __global__ __launch_bounds__(256, 2) void conv_c8s2_fwd_kernel(const C8Params p) {
     typedef bf16_t T;
     __shared__ __attribute__((aligned(16))) char smem[C8_LDS + 1024];     // (+ the tail of the last 64-pixel piece)
-    typedef __attribute__((address_space(3))) void* lptr_t;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int n = blockIdx.x / p.yblocks, Y0 = (blockIdx.x - n * p.yblocks) * C8_RT;
     const int pitch = p.pitch;
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void conv_c8s2_fwd_kernel(const C8Params p)
         const int c0 = 32 * (m >> 1) + 8 * kq + 4 * (m & 1);
         binit[m] = p.bias ? *(const f32x4_t*)(p.bias + c0) : f32x4_t{0.f, 0.f, 0.f, 0.f};
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
 
     const int Y = Y0 + wave;
@@ -184,10 +183,6 @@ __global__ __launch_bounds__(256, 2) void conv_c8s2_dgrad_kernel(const C8DParams
 // so a lane assembles its 8 pixels with eight ds_read_u16(_d16_hi) at immediate offsets of one address (conv_wgrad_patch.hip's 8-channel
 // kernel does the same at stride 16).  Four waves = 2 (co blocks of 32) x 2 (kernel-row pairs); v_mfma_f32_32x32x16_bf16; 256 persistent
 // workgroups add their [64][128] tiles into dW with fp32 atomics; the bias gradient is one extra MFMA against ones.
-#define S2E_C8_U16_PAIR(lo, hi, addr, off_lo, off_hi) \
-    asm volatile("ds_read_u16 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "n"(off_lo) : "memory"); \
-    asm volatile("ds_read_u16_d16_hi %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(off_hi) : "memory")
-
 struct C8WJob { const void* x; const void* gy; float* dw; float* dbias; float* part; int N, Hi, Wi, Ho, Wo, G, pitch, rows; unsigned x_bytes, gy_bytes; };
 constexpr int C8W_TILE = 64 * 128 + 64;             // a workgroup's partial tile: dW [64][128], then the bias sums
 constexpr int C8W_MAX_JOBS = 4;
@@ -198,7 +193,6 @@ constexpr int C8W_XB = 4 * C8_MAXPITCH * 16 + 1024, C8W_GB = 16 * C8_MAXG * 128,
 __global__ __launch_bounds__(256, 2) void conv_c8s2_wgrad_kernel(const C8WMulti b) {
     typedef bf16_t T;
     __shared__ __attribute__((aligned(16))) char smem[2 * C8W_STAGE];
-    typedef __attribute__((address_space(3))) void* lptr_t;
     int jb = 0;
     while (jb + 1 < b.n && (int)blockIdx.x >= b.first[jb + 1]) ++jb;
     const C8WJob& p = b.j[jb];
@@ -247,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void conv_c8s2_wgrad_kernel(const C8WMulti 
 
     int item = blk;
     if (item < p.rows) stage_slab(item, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     int buf = 0;
     for (; item < p.rows; item += nblk) {
@@ -261,10 +255,10 @@ __global__ __launch_bounds__(256, 2) void conv_c8s2_wgrad_kernel(const C8WMulti 
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 const uint32_t ad = b_lane[c] + stage + (uint32_t)(g << 9);       // 32 pixels of the input row per 16 output pixels
-                S2E_C8_U16_PAIR(B[c][0], Bh[c][0], ad, 0, 32);
-                S2E_C8_U16_PAIR(B[c][1], Bh[c][1], ad, 64, 96);
-                S2E_C8_U16_PAIR(B[c][2], Bh[c][2], ad, 128, 160);
-                S2E_C8_U16_PAIR(B[c][3], Bh[c][3], ad, 192, 224);
+                S2E_U16_PAIR(B[c][0], Bh[c][0], ad, 0, 32);
+                S2E_U16_PAIR(B[c][1], Bh[c][1], ad, 64, 96);
+                S2E_U16_PAIR(B[c][2], Bh[c][2], ad, 128, 160);
+                S2E_U16_PAIR(B[c][3], Bh[c][3], ad, 192, 224);
             }
             asm volatile("s_waitcnt lgkmcnt(0)"
                          : "+v"(A.lo), "+v"(A.hi), "+v"(B[0][0]), "+v"(B[0][1]), "+v"(B[0][2]), "+v"(B[0][3]), "+v"(B[1][0]), "+v"(B[1][1]), "+v"(B[1][2]), "+v"(B[1][3]),
@@ -275,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void conv_c8s2_wgrad_kernel(const C8WMulti 
                 acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8_t, u32x4_t{B[c][0] | Bh[c][0], B[c][1] | Bh[c][1], B[c][2] | Bh[c][2], B[c][3] | Bh[c][3]}), acc[c], 0, 0, 0);
             if (want_bias) accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8_t, ones), accb, 0, 0, 0);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         buf ^= 1;
     }
@@ -314,7 +308,7 @@ __global__ __launch_bounds__(256) void conv_c8s2_wgrad_reduce_kernel(const C8WMu
 }
 
 int c8_on() {
-    static const int v = [] { const char* e = getenv("S2E_CONV_C8"); return e ? atoi(e) : 1; }();
+    static const int v = s2e_env_int("S2E_CONV_C8", 1);
     return v;
 }
 
@@ -375,7 +369,7 @@ size_t s2e_c8s2_wgrad_workspace_bytes(int n_jobs) {
 }
 
 int s2e_c8s2_wgrad_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n_all, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    static const double total_wg = [] { const char* e = getenv("S2E_C8W_WGS"); return e ? atof(e) : 512.0; }();
+    static const double total_wg = s2e_env_double("S2E_C8W_WGS", 512.0);
     char* ws = (char*)workspace;
     for (int base = 0; base < n_all; base += C8W_MAX_JOBS) {
         const int n = n_all - base < C8W_MAX_JOBS ? n_all - base : C8W_MAX_JOBS;

@@ -40,8 +40,6 @@
 
 namespace {
 
-__device__ __attribute__((aligned(16))) const uint32_t duo_zero16[4] = {0u, 0u, 0u, 0u};
-
 struct DuoParams {
     const void* x; const void* w; const float* bias; const void* res; const void* aux; void* y;
     int N, Hi, Wi, Cin, Ho, Wo, Cout, Kpad;
@@ -97,8 +95,6 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(const DuoParams p) {
     // plain: [0, 128) bias of the tile's channels; FUSE: [0, 64) b_gamma, [64, 128) b_beta, [128, 192) s1, [192, 256) s0,
     // [256, 384) {mean, rstd} of the 64 channels; the rest is padding the second piece fills with zeros
     __shared__ __attribute__((aligned(16))) float kcst[2][512];
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    typedef const __attribute__((address_space(1))) void* gptr_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = BN == 128 ? wave >> 1 : wave, wn = BN == 128 ? wave & 1 : 0;
@@ -177,8 +173,8 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(const DuoParams p) {
     // the first piece, + 1024 of the second); a missing bias and the padding lanes read a 16-byte zero page
     auto dma_consts = [&](const Item& q, int cbuf) __attribute__((always_inline)) {
         if (wave != 0) return;
-        const char* s0p = (const char*)duo_zero16;
-        const char* s1p = (const char*)duo_zero16;
+        const char* s0p = (const char*)s2e_zero16;
+        const char* s1p = (const char*)s2e_zero16;
         if constexpr (FUSE) {
             const int arr = lane >> 4, i4 = (lane & 15) * 4, c0 = q.tn * 64;
             const float* sty = p.mstyle + (size_t)q.n * p.msld;
@@ -191,8 +187,8 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(const DuoParams p) {
             const int c = q.tn * BN + lane * 4;
             if (lane * 4 < BN && p.bias && c < p.Cout) s0p = (const char*)(p.bias + c);
         }
-        __builtin_amdgcn_global_load_lds((gptr_t)(const void*)s0p, (lptr_t)&kcst[cbuf][0], 16, 0, 0);
-        if constexpr (FUSE) __builtin_amdgcn_global_load_lds((gptr_t)(const void*)s1p, (lptr_t)&kcst[cbuf][256], 16, 0, 0);
+        lds_dma16(s0p, &kcst[cbuf][0]);
+        if constexpr (FUSE) lds_dma16(s1p, &kcst[cbuf][256]);
     };
     auto prologue = [&](const Item& q, int pbuf, int cbuf) __attribute__((always_inline)) {
         dma_consts(q, cbuf);
@@ -201,10 +197,10 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(const DuoParams p) {
         if (nk > 1) dma_w(1, 1);
     };
     auto wait_keep = [&](int n) __attribute__((always_inline)) {             // all but the n youngest loads have landed
-        if (n == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (n == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else if (n == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        if (n == 0) wait_vmcnt<0>();
+        else if (n == 1) wait_vmcnt<1>();
+        else if (n == 2) wait_vmcnt<2>();
+        else wait_vmcnt<3>();
     };
 
     // ---- fragments.  A rows: wave row wm covers tile rows 128 wm .. + 127.  Fragment address of tap (dy, dx) = a_dx[mi][dx] +
@@ -583,9 +579,9 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(const DuoParams p) {
         stamp(0);
         // the prologue's DMA pieces were issued BEFORE the epilogue's stores: vector-memory operations retire in order, so once at
         // most `st_issued` are outstanding every piece has landed -- the stores themselves stay in flight across the barrier
-        if (st_issued >= 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (st_issued >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (st_issued >= 16) wait_vmcnt<16>();
+        else if (st_issued >= 8) wait_vmcnt<8>();
+        else wait_vmcnt<0>();
         __syncthreads();
         stamp(1);
         if (tile_i & 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);     // (see "priority" at the top)
@@ -763,35 +759,26 @@ __global__ __launch_bounds__(256, 2) void conv_duo_kernel(const DuoParams p) {
     }
 }
 
-int duo_cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 // S2E_CONV_DUO = the work items (rectangle x 128-channel tile) a launch must have for this kernel to take it (default 256: one per
 // CU, half the 2-per-CU grid); 0 = never (conv_patch.hip runs everything, for A/B runs).
 int duo_min_items() {
-    static const int n = [] { const char* e = getenv("S2E_CONV_DUO"); return e ? atoi(e) : 256; }();
+    static const int n = s2e_env_int("S2E_CONV_DUO", 256);
     return n;
 }
 
 template <bool FUSE>
 int duo_launch(DuoParams& p, long rects_upper, hipStream_t st) {
     const long items = rects_upper * p.tiles_n;
-    const int cap = 2 * duo_cu_count();
+    const int cap = 2 * s2e_cu_count();
     const int grid = items < cap ? (int)items : cap;
 #ifdef S2E_DUO_STAMPS
-    static long* const dbg_ptr = [] { const char* e = getenv("S2E_DUO_DBG_PTR"); return e ? (long*)strtoull(e, nullptr, 0) : (long*)nullptr; }();
+    static long* const dbg_ptr = (long*)s2e_env_long("S2E_DUO_DBG_PTR", 0);
     p.dbg = dbg_ptr;
-    static const int abl_env = [] { const char* e = getenv("S2E_DUO_ABL"); return e ? atoi(e) : 0; }();
+    static const int abl_env = s2e_env_int("S2E_DUO_ABL", 0);
     p.abl = abl_env;
 #endif
     // S2E_DUO_MF16=0: the 32x32x16 loop everywhere (A/B switch)
-    static const bool mf16 = [] { const char* e = getenv("S2E_DUO_MF16"); return e ? atoi(e) != 0 : true; }();
+    static const bool mf16 = s2e_env_flag("S2E_DUO_MF16", true);
     if (!FUSE && p.Cout <= 64) conv_duo_kernel<false, 64><<<grid, 256, 0, st>>>(p);
     else if (!mf16) conv_duo_kernel<FUSE><<<grid, 256, 0, st>>>(p);
     else if (FUSE) conv_duo_kernel<true, 128, true><<<grid, 256, 0, st>>>(p);

@@ -34,35 +34,6 @@ struct ConvKParams {
     int cls_tile0[5];                     // S2 kernels: first pixel-tile of each output-parity class (prefix sums)
 };
 
-template <typename T> struct Mfma;
-template <> struct Mfma<bf16_t> {
-    static __device__ __forceinline__ void run(u32x4_t a, u32x4_t b, f32x16_t& acc) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                      __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-    }
-};
-template <> struct Mfma<float> {
-    // lane half h holds 4 consecutive k; MFMA t pairs element t of half 0 with element t of half 1.
-    // A and B use the same (permuted) k order, so the contraction is exact.
-    // (vectors by value + whole-vector bit_cast: see the note at unpack16 in common.h)
-    static __device__ __forceinline__ void run(u32x4_t a, u32x4_t b, f32x16_t& acc) {
-        const f32x4_t fa = __builtin_bit_cast(f32x4_t, a), fb = __builtin_bit_cast(f32x4_t, b);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0], fb[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[1], fb[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[2], fb[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[3], fb[3], acc, 0, 0, 0);
-    }
-};
-
-template <typename T>
-__device__ __forceinline__ u32x4_t apply_lrelu16(u32x4_t r) {
-    float f[Vec<T>::N];
-    unpack16<T>(r, f);
-#pragma unroll
-    for (int j = 0; j < Vec<T>::N; ++j) f[j] = lrelu02(f[j]);
-    return pack16<T>(f);
-}
-
 // VECPATH: Cin is a multiple of the 16-B vector width, so every im2col chunk is one aligned 16-B load.
 // The any-Cin element-wise gather (tiny-K layers only: Cin = 1 or 5) is a separate instantiation so
 // its index arithmetic never bloats the hot kernel.
@@ -71,9 +42,8 @@ __device__ __forceinline__ u32x4_t apply_lrelu16(u32x4_t r) {
 // K-tile the register-staged kernel is LDS-write-bound (64 writes + 128 reads ~ 1340 LDS cycles per CU per
 // K-tile pair vs 1024 MFMA cycles).  LDS-DMA writes lane-linear (M0 base + lane*16), so one instruction
 // fills 8 consecutive 128-B rows; the XOR swizzle moves to the SOURCE side (lane at physical chunk c loads
-// logical chunk c ^ swz(row)), and lanes whose tap reads padding fetch from a 16-byte zero page.
+// logical chunk c ^ swz(row)), and lanes whose tap reads padding fetch from the 16-byte zero page (common.h).
 // GLDS needs VECPATH and no input activation (nothing passes through registers).
-__device__ __attribute__((aligned(16))) const uint32_t g_zero16[4] = {0u, 0u, 0u, 0u};
 
 // S2: stride-2 DATA-GRADIENT by output-parity class.  In a stride-2 transposed conv an output pixel (oy, ox) only sees
 // the taps with ky = oy + pad (mod 2), kx = ox + pad (mod 2): a quarter of a 4x4 kernel.  Walking all taps with a
@@ -273,7 +243,7 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvKParams p)
             });
         }
         if (p.in_act == S2E_ACT_LRELU)
-            static_for<0, 4>([&](auto I) { ra[decltype(I)::value] = apply_lrelu16<T>(ra[decltype(I)::value]); });
+            static_for<0, 4>([&](auto I) { ra[decltype(I)::value] = lrelu16<T>(ra[decltype(I)::value]); });
         static_for<0, NB>([&](auto J) {
             constexpr int j = decltype(J)::value;
             rb[j] = *(const u32x4_t*)(wgt + (size_t)(tn * BN + r0 + 32 * j) * p.Kpad + kt * BK + c * VEC);
@@ -342,8 +312,6 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvKParams p)
         compute((nk - 1) & 1);
         __syncthreads();
     } else {
-        typedef const __attribute__((address_space(1))) void* gptr_t;
-        typedef __attribute__((address_space(3))) void* lptr_t;
         // rows r0 + 32*i of this thread land at LDS row 8*(wave + 4*i) + (lane>>3) = r0 + 32*i: same rows
         auto dma_tile = [&](int kt, int buf) __attribute__((always_inline)) {
             char* base = smem + buf * STAGE;
@@ -353,27 +321,27 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_kernel(const ConvKParams p)
             static_for<0, 4>([&](auto I) {
                 constexpr int i = decltype(I)::value;
                 const bool v = kvalid && ((vmask[i] >> tbit) & 1u);
-                const void* src = v ? (const void*)(xg + (rowoff[i] + koff)) : (const void*)g_zero16;
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + (8 * wave + 32 * i) * 128), 16, 0, 0);
+                const void* src = v ? (const void*)(xg + (rowoff[i] + koff)) : (const void*)s2e_zero16;
+                lds_dma16(src, base + (8 * wave + 32 * i) * 128);
             });
             // weight column of this thread's chunk: linear in k, except in S2 mode where k walks the class's tap subset
             const long kb = S2 ? (kvalid ? (long)(l_ky * p.KW + l_kx) * p.Cin + l_ci : -1L) : (long)kt * BK + c * VEC;
             advance_k();
             static_for<0, NB>([&](auto J) {
                 constexpr int j = decltype(J)::value;
-                const void* src = (S2 && kb < 0) ? (const void*)g_zero16
+                const void* src = (S2 && kb < 0) ? (const void*)s2e_zero16
                                                  : (const void*)(wgt + (size_t)(tn * BN + r0 + 32 * j) * p.Kpad + kb);
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + A_BYTES + (8 * wave + 32 * j) * 128), 16, 0, 0);
+                lds_dma16(src, base + A_BYTES + (8 * wave + 32 * j) * 128);
             });
         };
         dma_tile(kt0, 0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         for (int kt = 0; kt + 1 < nk; ++kt) {
             const int cur = kt & 1;
             dma_tile(kt0 + kt + 1, cur ^ 1);        // DMA into the other buffer while this one is read
             compute(cur);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             __syncthreads();
         }
         compute((nk - 1) & 1);
@@ -564,7 +532,7 @@ static int launch_conv(const ConvKParams& p, hipStream_t st, bool s2 = false) {
         S2E_CHECK_LAUNCH("conv_igemm_kernel (stride-2 class mode)");
         return S2E_OK;
     }
-    static const bool glds = [] { const char* e = getenv("S2E_IGEMM_GLDS"); return e ? atoi(e) != 0 : true; }();
+    static const bool glds = s2e_env_flag("S2E_IGEMM_GLDS", true);
     if (p.Cin % Vec<T>::N == 0) {
         if (glds && p.in_act == S2E_ACT_NONE) conv_igemm_kernel<T, BN, true, true><<<grid, 256, 0, st>>>(p);
         else conv_igemm_kernel<T, BN, true, false><<<grid, 256, 0, st>>>(p);
@@ -577,8 +545,8 @@ static int launch_conv(const ConvKParams& p, hipStream_t st, bool s2 = false) {
 // Stride-2 data-gradients run per output-parity class (conv_igemm_kernel<..., S2 = true>) when the vector LDS-DMA
 // loader applies; S2E_IGEMM_S2CLASS=0 falls back to the masked all-taps walk.
 static bool s2_class_mode(int dtype, const s2e_conv_desc* d) {
-    static const bool on = [] { const char* e = getenv("S2E_IGEMM_S2CLASS"); return e ? atoi(e) != 0 : true; }();
-    static const bool glds = [] { const char* e = getenv("S2E_IGEMM_GLDS"); return e ? atoi(e) != 0 : true; }();
+    static const bool on = s2e_env_flag("S2E_IGEMM_S2CLASS", true);
+    static const bool glds = s2e_env_flag("S2E_IGEMM_GLDS", true);
     const int vec = dtype == S2E_BF16 ? 8 : 4;
     return on && glds && d->transposed && d->stride == 2 && d->in_act == S2E_ACT_NONE && d->Cin % vec == 0 && d->KH >= 2 && d->KW >= 2;
 }

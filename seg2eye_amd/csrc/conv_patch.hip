@@ -33,8 +33,6 @@
 
 namespace {
 
-__device__ __attribute__((aligned(16))) const uint32_t pz_zero16[4] = {0u, 0u, 0u, 0u};
-
 struct PatchParams {
     const void* x; const void* w; const float* bias; const void* res; const void* aux; void* y;
     int N, Hi, Wi, Cin, Ho, Wo, Cout, Kpad;
@@ -58,22 +56,6 @@ struct PatchParams {
     const int* rect_list; const int* rect_count;
     // S2D (stride-2 4x4 pad-2 layers as a 2x2 stride-1 conv over the space-to-depth VIEW of the full-resolution tensor):
     int c_shift;                      // log2 of the full-resolution tensor's channel count C (a power of two >= 64)
-};
-
-template <typename T> struct PMfma;
-template <> struct PMfma<bf16_t> {
-    static __device__ __forceinline__ void run(u32x4_t a, u32x4_t b, f32x16_t& acc) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
-    }
-};
-template <> struct PMfma<float> {           // same k permutation on both operands: exact contraction (see conv_igemm.hip)
-    static __device__ __forceinline__ void run(u32x4_t a, u32x4_t b, f32x16_t& acc) {
-        const f32x4_t fa = __builtin_bit_cast(f32x4_t, a), fb = __builtin_bit_cast(f32x4_t, b);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0], fb[0], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[1], fb[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[2], fb[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[3], fb[3], acc, 0, 0, 0);
-    }
 };
 
 // FUSE: the launch is the [gamma | beta] conv of a SPADE (Cout = 2C, BN = 128).  A Cout tile then pairs 64 gamma rows of
@@ -115,8 +97,6 @@ __global__ __launch_bounds__(512, 1) void conv_patch_kernel(const PatchParams p)
     static_assert(EP_ROWS * BN * 4 <= P_BYTES, "epilogue staging must fit one patch buffer");
     static_assert(2 * P_BYTES + NBS * B_BYTES <= 160 * 1024, "LDS budget");
     __shared__ __attribute__((aligned(16))) char smem[2 * P_BYTES + NBS * B_BYTES];
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
@@ -211,13 +191,14 @@ __global__ __launch_bounds__(512, 1) void conv_patch_kernel(const PatchParams p)
     auto dma_patch = [&](auto R, int chunk, int buf) __attribute__((always_inline)) -> int {
         constexpr int r = decltype(R)::value;
         if (r * NW + wave >= NPIECE) return 0;        // wave-uniform
+        // (the bare builtin here and in dma_w, not lds_dma16: through the helper this kernel's scheduling and register allocation change)
         const void* src;
         if constexpr (S2D == 1) {
             const int k0 = (chunk0 + chunk) * BK, qq = k0 >> p.c_shift, c0 = k0 & (p.Cin - 1);
             const long off = (long)((qq >> 1) * p.Wi + (qq & 1)) * p.Cin + c0;
-            src = ((aval[r] >> qq) & 1) ? (const void*)(xg + aoff[r] + off) : (const void*)pz_zero16;
+            src = ((aval[r] >> qq) & 1) ? (const void*)(xg + aoff[r] + off) : (const void*)s2e_zero16;
         } else {
-            src = aoff[r] >= 0 ? (const void*)(xg + aoff[r] + chunk * BK) : (const void*)pz_zero16;
+            src = aoff[r] >= 0 ? (const void*)(xg + aoff[r] + chunk * BK) : (const void*)s2e_zero16;
         }
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + buf * P_BYTES + (r * NW + wave) * 1024), 16, 0, 0);
         return 1;
@@ -253,12 +234,12 @@ __global__ __launch_bounds__(512, 1) void conv_patch_kernel(const PatchParams p)
         if (PD > 1 && nk > 1) dma_w(1, 1);
     };
     auto wait_keep = [&](int n) __attribute__((always_inline)) {             // all but the n youngest loads have landed
-        if (n == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (n == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-        else if (n == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else if (n == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else if (n == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+        if (n == 0) wait_vmcnt<0>();
+        else if (n == 1) wait_vmcnt<1>();
+        else if (n == 2) wait_vmcnt<2>();
+        else if (n == 3) wait_vmcnt<3>();
+        else if (n == 4) wait_vmcnt<4>();
+        else wait_vmcnt<5>();
     };
     static_assert(NBJ + PPT <= 5, "wait_keep covers up to 5 loads per tap");
 
@@ -318,7 +299,7 @@ __global__ __launch_bounds__(512, 1) void conv_patch_kernel(const PatchParams p)
 #pragma unroll
         for (int mi = 0; mi < TM; ++mi)
 #pragma unroll
-            for (int ni = 0; ni < TN; ++ni) PMfma<T>::run(fa[set][mi], fb[set][ni], acc[mi][ni]);
+            for (int ni = 0; ni < TN; ++ni) Mfma<T>::run(fa[set][mi], fb[set][ni], acc[mi][ni]);
     };
 
     constexpr int TPR = BN / VEC, RPP = NT / TPR;
@@ -523,7 +504,7 @@ __global__ __launch_bounds__(512, 1) void conv_patch_kernel(const PatchParams p)
     int pb = 0;                                       // patch buffer of the current tile's chunk 0
     prologue(pb);
     for (;;) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         int next_rect = -1;                               // label-sparse launch: the next tile's rectangle, requested a tile ahead
         if constexpr (FUSE) { if (p.rect_list && tile_id + G < n_tiles) next_rect = p.rect_list[(tile_id + G) / p.tiles_n]; }
@@ -603,9 +584,9 @@ double s2e_patch_rectangle(const s2e_conv_desc* d, int ks, int* tw_out, int* th_
 }
 
 int s2e_conv_patch_plan(int dtype, const s2e_conv_desc* d, s2e_patch_plan* plan) {
-    static const int min_tiles = [] { const char* e = getenv("S2E_CONV_PATCH"); return e ? atoi(e) : 224; }();
-    static const bool allow_split = [] { const char* e = getenv("S2E_CONV_PATCH_SPLIT"); return e ? atoi(e) != 0 : true; }();
-    static const bool allow_k4 = [] { const char* e = getenv("S2E_CONV_PATCH_K4"); return e ? atoi(e) != 0 : true; }();
+    static const int min_tiles = s2e_env_int("S2E_CONV_PATCH", 224);
+    static const bool allow_split = s2e_env_flag("S2E_CONV_PATCH_SPLIT", true);
+    static const bool allow_k4 = s2e_env_flag("S2E_CONV_PATCH_K4", true);
     s2e_patch_plan local;
     if (!plan) plan = &local;
     plan->tw = plan->th = 0; plan->splits = 1; plan->bn = 0;
@@ -615,7 +596,7 @@ int s2e_conv_patch_plan(int dtype, const s2e_conv_desc* d, s2e_patch_plan* plan)
     plan->s2d = 0;
     if (dtype == S2E_BF16 && ks == 4 && d->KW == 4 && d->stride == 2 && d->pad == 2 && d->in_act == S2E_ACT_NONE) {
         // the PatchGAN's 4x4 stride-2 pad-2 layers through the space-to-depth view (S2D, see the kernel)
-        static const bool allow_s2d = [] { const char* e = getenv("S2E_CONV_PATCH_S2D"); return e ? atoi(e) != 0 : true; }();
+        static const bool allow_s2d = s2e_env_flag("S2E_CONV_PATCH_S2D", true);
         const int C = d->transposed ? d->Cout : d->Cin;          // channels of the full-resolution tensor
         const int Hf = d->transposed ? d->Ho : d->Hi, Wf = d->transposed ? d->Wo : d->Wi;
         const int Hh = d->transposed ? d->Hi : d->Ho, Wh = d->transposed ? d->Wi : d->Wo;
@@ -665,18 +646,9 @@ size_t s2e_conv_patch_workspace_bytes(int dtype, const s2e_conv_desc* d) {
     return (size_t)plan.splits * d->N * d->Ho * d->Wo * d->Cout * sizeof(float);
 }
 
-static int cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 template <typename T, int BN>
 static int launch_patch(const PatchParams& p, int ks, hipStream_t st, int s2d = 0) {
-    const int grid = p.tiles < cu_count() ? p.tiles : cu_count();      // persistent: one 127-154 KB workgroup per CU
+    const int grid = p.tiles < s2e_cu_count() ? p.tiles : s2e_cu_count();      // persistent: one 127-154 KB workgroup per CU
     if constexpr (std::is_same<T, bf16_t>::value) {
         if (s2d == 1) conv_patch_kernel<T, BN, 2, false, 1><<<grid, 512, 0, st>>>(p);
         else if (s2d == 2) { if constexpr (BN == 128) conv_patch_kernel<T, 128, 2, false, 2><<<grid, 512, 0, st>>>(p); }
@@ -733,7 +705,7 @@ int s2e_conv_patch_launch(int dtype, const s2e_patch_plan* plan, const void* x, 
 // rows are idle (31 -> 22 us).  Below S2E_SPADE_FUSED_TILES (default 96) tiles the two-launch path runs; flags & 1 forces the
 // fused kernel at any tile count (tests).
 static int fused_plan(int dtype, int N, int H, int W, int C, int nh, int flags, s2e_conv_desc* d, s2e_patch_plan* plan) {
-    static const int min_tiles = [] { const char* e = getenv("S2E_SPADE_FUSED_TILES"); return e ? atoi(e) : 96; }();
+    static const int min_tiles = s2e_env_int("S2E_SPADE_FUSED_TILES", 96);
     if (min_tiles <= 0 && !(flags & 1)) return 0;
     if (C <= 0 || C % 64 != 0 || N <= 0 || H <= 0 || W <= 0) return 0;
     const int vec = dtype == S2E_BF16 ? 8 : 4;
@@ -802,7 +774,7 @@ static int spade_conv_modulate_impl(int dtype, const void* actv, const void* w_p
     if (p.mup && ((H | W) & 1)) S2E_FAIL(S2E_ERR_ARG, "s2e_spade_conv_modulate: flags 8 (x at half resolution) needs even H, W");
     p.mC = C; p.mlrelu = lrelu;
     p.rect_list = rect_list; p.rect_count = rect_count;
-    const int grid = p.tiles < cu_count() ? p.tiles : cu_count();
+    const int grid = p.tiles < s2e_cu_count() ? p.tiles : s2e_cu_count();
     hipStream_t st = (hipStream_t)stream;
     if (dtype == S2E_BF16) conv_patch_kernel<bf16_t, 128, 3, true><<<grid, 512, 0, st>>>(p);
     else conv_patch_kernel<float, 128, 3, true><<<grid, 512, 0, st>>>(p);

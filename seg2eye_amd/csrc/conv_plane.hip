@@ -67,7 +67,6 @@ constexpr int m_slot_base(int m, int TH, int p) {
     return b;
 }
 
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 template <int MODE, int BN, int TH, int S>
 __global__ __launch_bounds__(256, 2) void conv_plane_kernel(const PlaneParams p) {
@@ -237,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void conv_plane_kernel(const PlaneParams p)
     bool has_next = false;
     static_for<0, S * NR>([&](auto NN) { dma_piece(NN, 0, pb); });      // the first tile's stage 0 ...
     static_for<0, D>([&](auto JJ) { load_w_item(decltype(JJ)::value, cur, decltype(JJ)::value); });      // ... and first weights
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
 
     // One tile of class CLS.  The stream of (tile, stage) pairs never stops: during a tile's LAST stage the next tile's stage 0 lands in
@@ -332,8 +331,8 @@ __global__ __launch_bounds__(256, 2) void conv_plane_kernel(const PlaneParams p)
                         // back (above); then the waves meet
                         constexpr int after = 4 * (KSTEPS - JP + 1);
                         static_assert(after <= 63, "vmcnt range");
-                        if constexpr (KSTEPS == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(after) : "memory");
+                        if constexpr (KSTEPS == 1) wait_vmcnt<0>();
+                        else wait_vmcnt<after>();
                         __builtin_amdgcn_s_barrier();
                         if (!last_stage) read_x(ns, 0, 0, buf ^ 1, 0, NPF);       // (a following TILE reads its own first fragments: its class may differ)
                     }
@@ -367,19 +366,10 @@ __global__ __launch_bounds__(256, 2) void conv_plane_kernel(const PlaneParams p)
     }
 }
 
-int plane_cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 template <int MODE, int S>
 int plane_launch(const PlaneParams& p, hipStream_t st) {
     const long items = (long)p.rects * p.tiles_n * (m_so(MODE) == 2 ? 4 : 1);
-    const int cap = 2 * plane_cu_count();
+    const int cap = 2 * s2e_cu_count();
     const int grid = items < cap ? (int)items : cap;
     if (p.tiles_n * 128 == p.Cout) conv_plane_kernel<MODE, 128, 8, S><<<grid, 256, 0, st>>>(p);
     else conv_plane_kernel<MODE, 64, 8, S><<<grid, 256, 0, st>>>(p);
@@ -392,23 +382,14 @@ constexpr int plane_stage_chunks(int mode, int nch = 4) { return mode == PLANE_K
 
 }  // namespace
 
-// Channels per tile: 128, or 64 for a 64-channel layer.  S2E_PLANE_BN64=<k> (experiment; default 0 = off): 64-channel tiles also for
-// layers whose 128-channel tiles give the chip's workgroup slots fewer than k items each -- measured slower at k = 1, 2, 4 on every
-// shape of the step (twice the weight traffic per MFMA costs more than the fuller chip gains): kept for A/B runs only.
-static int plane_bn(const s2e_conv_desc* d, int mode, long rects) {
-    if (d->Cout % 128 != 0) return 64;
-    static const int per_slot = [] { const char* e = getenv("S2E_PLANE_BN64"); return e ? atoi(e) : 0; }();      // (measured: 64-channel tiles lose everywhere, 0 = never)
-    const long items128 = rects * (d->Cout / 128) * ((mode == PLANE_K3S2D || mode == PLANE_K4S2D) ? 4 : 1);
-    return items128 < (long)per_slot * 2 * plane_cu_count() ? 64 : 128;
-}
+// Channels per tile: 128, or 64 for a 64-channel layer.  (64-channel tiles for under-filled 128-channel launches measured slower on
+// every shape of the step: twice the weight traffic per MFMA costs more than the fuller chip gains.)
+static int plane_bn(const s2e_conv_desc* d) { return d->Cout % 128 != 0 ? 64 : 128; }
 
 // S2E_CONV_PLANE: bit mask of the modes this kernel may take (default: 1x1, the 3x3 and the 4x4 stride-2 pairs; the stride-1 modes
 // lose to conv_duo.hip on the large maps and stay off); 0 = never (A/B runs)
 static int plane_mask() {
-    static const int m = [] {
-        const char* e = getenv("S2E_CONV_PLANE");
-        return e ? atoi(e) : (1 << PLANE_K1) | (1 << PLANE_K3S2F) | (1 << PLANE_K3S2D) | (1 << PLANE_K4S2F) | (1 << PLANE_K4S2D);
-    }();
+    static const int m = s2e_env_int("S2E_CONV_PLANE", (1 << PLANE_K1) | (1 << PLANE_K3S2F) | (1 << PLANE_K3S2D) | (1 << PLANE_K4S2F) | (1 << PLANE_K4S2D));
     return m;
 }
 
@@ -437,8 +418,8 @@ int s2e_conv_plane_mode(int dtype, const s2e_conv_desc* d) {
     // rectangles of 8 x 16: the map must be at least one rectangle wide and tall, and the launch must give the chip something to do
     if (rw < 16 || rh < 8) return PLANE_NONE;
     const long rects = (long)d->N * ceil_div(rh, 8) * ceil_div(rw, 16);
-    const long items = rects * ceil_div(d->Cout, plane_bn(d, mode, rects)) * ((mode == PLANE_K3S2D || mode == PLANE_K4S2D) ? 4 : 1);
-    static const int min_items = [] { const char* e = getenv("S2E_CONV_PLANE_MIN"); return e ? atoi(e) : 128; }();
+    const long items = rects * ceil_div(d->Cout, plane_bn(d)) * ((mode == PLANE_K3S2D || mode == PLANE_K4S2D) ? 4 : 1);
+    static const int min_items = s2e_env_int("S2E_CONV_PLANE_MIN", 128);
     if (items < min_items) return PLANE_NONE;
     return mode;
 }
@@ -456,7 +437,7 @@ int s2e_conv_plane_launch(int mode, const void* x, const void* w, const float* b
     const int rh = mode == PLANE_K4S2D ? (d->Ho + 1) / 2 : dg ? d->Hi : d->Ho, rw = mode == PLANE_K4S2D ? (d->Wo + 1) / 2 : dg ? d->Wi : d->Wo;
     p.tiles_x = ceil_div(rw, 16); p.tiles_y = ceil_div(rh, 8);
     p.rects = d->N * p.tiles_y * p.tiles_x;
-    p.tiles_n = ceil_div(d->Cout, plane_bn(d, mode, p.rects));
+    p.tiles_n = ceil_div(d->Cout, plane_bn(d));
     p.nch = d->Cin / 32;
     p.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * d->Cin * 2);
     p.w_bytes = (unsigned)((long)ceil_div(d->Cout, 64) * 64 * d->KH * d->KW * d->Cin * 2);

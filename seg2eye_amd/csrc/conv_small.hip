@@ -90,14 +90,6 @@ __global__ __launch_bounds__(256) void fwd_cout1_kernel(SmallConvParams p) {
 // a handful of row blocks) with one LDS slab per quarter, summed in the stencil in a fixed order.
 // in_act: LeakyReLU is applied to the operand and the result rounded to bf16 (the MFMA's input type), where the vector kernel above
 // multiplied the fp32 value.
-__device__ __forceinline__ u32x4_t lrelu_bf16x8(u32x4_t r) {
-    float f[8];
-    unpack16<bf16_t>(r, f);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = lrelu02(f[j]);
-    return u32x4_t{pack2_bf16(f[0], f[1]), pack2_bf16(f[2], f[3]), pack2_bf16(f[4], f[5]), pack2_bf16(f[6], f[7])};
-}
-
 template <int KS, int NKW>       // NKW: K-steps (16 channels) a wave multiplies per row block = Cin / 16 / (channel quarters)
 __global__ __launch_bounds__(256) void fwd_cout1_mfma_kernel(SmallConvParams p, int tw, int th, int tiles_x, int tiles_y, int wk) {
     constexpr int NT = KS * KS, NTP = NT | 1;
@@ -134,7 +126,7 @@ __global__ __launch_bounds__(256) void fwd_cout1_mfma_kernel(SmallConvParams p, 
 #pragma unroll
         for (int j = 0; j < NKW; ++j) {
             u32x4_t v = a[j];
-            if (p.in_act == S2E_ACT_LRELU) v = lrelu_bf16x8(v);
+            if (p.in_act == S2E_ACT_LRELU) v = lrelu16<bf16_t, true>(v);
             if (!ok) v = u32x4_t{0u, 0u, 0u, 0u};
             acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, v), __builtin_bit_cast(bf16x8_t, bw[j]), acc, 0, 0, 0);
         }

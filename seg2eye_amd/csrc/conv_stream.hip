@@ -31,8 +31,6 @@
 
 namespace {
 
-__device__ __attribute__((aligned(16))) const uint32_t sk_zero16[4] = {0u, 0u, 0u, 0u};
-
 struct StreamParams {
     const void* x; const void* w; const float* bias; const void* res; const void* aux; void* y;
     int N, Hi, Wi, Cin, Ho, Wo, Cout;
@@ -111,7 +109,6 @@ template <int BN>
 __device__ __forceinline__ void sk_epilogue(const StreamParams& p, const SkTile& t, f32x16_t (&acc)[2][SkCfg<BN>::TN], char* Cs_c, int wave) {
     constexpr int TN = SkCfg<BN>::TN, WTN = BN / 2;
     constexpr int LPR = WTN / 8, RPS = 64 / LPR, SWEEPS = 32 / RPS;     // lanes per row, rows per sweep
-    typedef __attribute__((address_space(3))) void* lptr_t;
     typedef bf16_t T;
     const int lane = threadIdx.x & 63;
     const int wm = wave >> 1, wn = wave & 1, h = lane >> 5, l31 = lane & 31;
@@ -191,8 +188,6 @@ __global__ __launch_bounds__(256 + 64 * SK_LOADERS, 1) void conv_stream_kernel(c
     static_assert(16 % NLW == 0 && (NB * 4) % NLW == 0, "every loader wave issues the same number of pieces");
     constexpr int A_BYTES = Cfg::A_BYTES, STAGE = Cfg::STAGE, S = Cfg::S, PD = S - 1;
     __shared__ __attribute__((aligned(16))) char smem[Cfg::LDS_BYTES];
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wgi = xcd_remap(blockIdx.x, p.G);
@@ -203,7 +198,6 @@ __global__ __launch_bounds__(256 + 64 * SK_LOADERS, 1) void conv_stream_kernel(c
         // ------------------------------------------------------------ loader waves (run PD units ahead of the multiply)
         // loader wave w, piece i fills rows 8 (w + NLW i) .. + 7 of a stage; lane -> row offset lane >> 3, physical chunk
         // lane & 7 = logical chunk ^ ((row >> 1) & 7), the same for every i
-        typedef __attribute__((address_space(3))) void* lptr_t;
         const int lw = wave - 4;
         const int r0 = 8 * lw + (lane >> 3);
         const int c = (lane & 7) ^ ((r0 >> 1) & 7);
@@ -282,10 +276,10 @@ __global__ __launch_bounds__(256 + 64 * SK_LOADERS, 1) void conv_stream_kernel(c
         // all but the `keep` youngest K-steps' pieces of this wave have landed
         auto wait_units = [&](int keep) __attribute__((always_inline)) {
             static_assert(PD <= 4 && 3 * LPT <= 63, "wait table");
-            if (keep <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (keep == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(LPT) : "memory");
-            else if (keep == 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * LPT) : "memory");
-            else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(3 * LPT) : "memory");
+            if (keep <= 0) wait_vmcnt<0>();
+            else if (keep == 1) wait_vmcnt<LPT>();
+            else if (keep == 2) wait_vmcnt<2 * LPT>();
+            else wait_vmcnt<3 * LPT>();
         };
         // one loop for the fill (the first PD turns only load) and the steady state, so that the per-tile set-up (a few
         // hundred instructions of index arithmetic) exists once in the code
@@ -464,15 +458,6 @@ __global__ __launch_bounds__(256) void conv_stream_fixup_kernel(const StreamPara
     sk_epilogue<BN>(p, t, acc, smem, wave);
 }
 
-int sk_cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 bool sk_class_mode(const s2e_conv_desc* d) { return d->transposed && d->stride == 2; }
 int sk_bn(const s2e_conv_desc* d) { return d->Cout > 64 ? 128 : 64; }
 
@@ -506,7 +491,7 @@ bool sk_fill_units(const s2e_conv_desc* d, int kpad, StreamParams* p) {
     if (unit0[p->ncls] >= (1L << 31) - 4096) return false;
     for (int c = 0; c < 5; ++c) p->cls_unit0[c] = (int)unit0[c];
     p->units = (int)unit0[p->ncls];
-    const int cus = sk_cu_count();
+    const int cus = s2e_cu_count();
     p->G = p->units < cus ? p->units : cus;
     if (p->G < 1) p->G = 1;
     bool uniform = true;
@@ -533,7 +518,7 @@ bool sk_fill_units(const s2e_conv_desc* d, int kpad, StreamParams* p) {
 // S2E_CONV_STREAM: 0 = never; 1 (default) = the shapes it measured faster on (long-K tiles: >= 16 K-steps per tile and >= 64
 // tiles, no parity classes -- DESIGN 3.1e has the per-shape table); 2 = every shape the kernel can run (tests, A/B runs).
 int s2e_conv_stream_plan(int dtype, const s2e_conv_desc* d) {
-    static const int mode = [] { const char* e = getenv("S2E_CONV_STREAM"); return e ? atoi(e) : 1; }();
+    static const int mode = s2e_env_int("S2E_CONV_STREAM", 1);
     if (mode <= 0 || dtype != S2E_BF16) return 0;
     if (d->Cin % 8 != 0 || d->Cout % 8 != 0 || d->Cout <= 32 || d->in_act != S2E_ACT_NONE) return 0;
     if (d->KH * d->KW > 32 || d->out_act == S2E_ACT_TANH) return 0;

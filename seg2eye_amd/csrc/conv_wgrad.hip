@@ -31,11 +31,6 @@ template <typename T> struct WgLds;
 template <> struct WgLds<bf16_t> { static constexpr int ROW = 320; };   // 128 bf16 = 256 B + 64 B pad
 template <> struct WgLds<float>  { static constexpr int ROW = 512; };   // 128 f32
 
-__device__ __forceinline__ u32x2_t lds_tr16_b64(const char* p) {
-    s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)p);
-    return __builtin_bit_cast(u32x2_t, v);
-}
-
 // VECPATH: Cin and Cout are multiples of the 16-B vector width (every real layer except the 1- and
 // 5-channel heads); the element-wise gather lives in its own instantiation.
 // One workgroup's tile: block `blk` of `nblk` of the launch described by p (a launch of its own, or one job of a multi-job launch).
@@ -371,152 +366,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_multi_kernel(const WgMu
                       r.atomic[k] != 0);
 }
 
-// ------------------------------------------------------------------------------------ bf16 LDS-DMA variant
-// Same decomposition, operands staged with global_load_lds (no VGPR round trip, no ds_write_b128 -- the
-// register-staged kernel spends more LDS cycles on its stores than the MFMAs take).  Rows are 256 B,
-// unpadded; LDS-DMA writes lane-linear, so one instruction fills 4 rows and the XOR swizzle
-//   physical 16-B chunk = logical chunk ^ ((row & 3) << 2)
-// is applied to the SOURCE address.  With it the four rows a ds_read_b64_tr_b16 block touches fall in four
-// disjoint 64-B bank ranges (conflict-free).  Out-of-range rows / channels / padding taps read a zero page.
-__device__ __attribute__((aligned(16))) const uint32_t g_wg_zero16[4] = {0u, 0u, 0u, 0u};
-
-__global__ __launch_bounds__(256, 4) void conv_wgrad_glds_kernel(const WgradParams p) {
-    typedef bf16_t T;
-    constexpr int BR = 32, ROW = 256, OP_BYTES = BR * ROW, STAGE = 2 * OP_BYTES;
-    __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    // consecutive logical ids (= the (co,k) tiles of ONE pixel slice, which stream the same gy / x rows in
-    // lockstep) are placed on one XCD so they share that XCD's L2 instead of each L2 re-fetching the slice
-    int bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tk = bid % p.tiles_k; bid /= p.tiles_k;
-    const int tco = bid % p.tiles_co; const int split = bid / p.tiles_co;
-    const int m_begin = split * p.m_per_split;
-    const int m_end = min(p.M, m_begin + p.m_per_split);
-    if (m_begin >= m_end) return;
-
-    const T* __restrict__ xg = (const T*)p.x;
-    const T* __restrict__ gg = (const T*)p.gy;
-    // DMA mapping: wave w, instruction j fills rows 4*(w + 4*j) .. +3; lane -> row offset lane>>4, physical
-    // chunk lane&15 = logical chunk ^ ((row&3)<<2), row&3 == (lane>>4)&3 for both j
-    const int rsub = lane >> 4;
-    const int c = (lane & 15) ^ ((rsub & 3) << 2);           // logical chunk this lane fetches
-    const int co0 = tco * 128 + c * 8;
-    const int k0 = tk * 128 + c * 8;
-    const int HoWo = p.Ho * p.Wo;
-    int t_ci, t_ky, t_kx;
-    { const int tap = k0 / p.Cin; t_ci = k0 - tap * p.Cin; t_ky = tap / p.KW; t_kx = tap - t_ky * p.KW; }
-    const bool k_valid = k0 < p.Ktot, co_valid = co0 < p.Cout;
-    int rn[2], roy[2], rox[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int m = m_begin + 4 * wave + 16 * j + rsub;
-        rn[j] = m / HoWo; const int rem = m - rn[j] * HoWo;
-        roy[j] = rem / p.Wo; rox[j] = rem - roy[j] * p.Wo;
-    }
-    auto dma_chunk = [&](int ch, int buf) __attribute__((always_inline)) {
-        char* base = smem + buf * STAGE;
-        static_for<0, 2>([&](auto J) {
-            constexpr int j = decltype(J)::value;
-            const int m = m_begin + ch * BR + 4 * wave + 16 * j + rsub;
-            const bool mv = m < m_end;
-            const void* gsrc = (mv && co_valid) ? (const void*)(gg + (size_t)m * p.Cout + co0) : (const void*)g_wg_zero16;
-            __builtin_amdgcn_global_load_lds((gptr_t)gsrc, (lptr_t)(base + (4 * wave + 16 * j) * ROW), 16, 0, 0);
-            const int iy = roy[j] * p.stride - p.pad + t_ky, ix = rox[j] * p.stride - p.pad + t_kx;
-            const bool xv = mv && k_valid && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-            const void* xsrc = xv ? (const void*)(xg + ((size_t)(rn[j] * p.Hi + iy) * p.Wi + ix) * p.Cin + t_ci)
-                                  : (const void*)g_wg_zero16;
-            __builtin_amdgcn_global_load_lds((gptr_t)xsrc, (lptr_t)(base + OP_BYTES + (4 * wave + 16 * j) * ROW), 16, 0, 0);
-            rox[j] += BR;
-            while (rox[j] >= p.Wo) { rox[j] -= p.Wo; ++roy[j]; }
-            while (roy[j] >= p.Ho) { roy[j] -= p.Ho; ++rn[j]; }
-        });
-    };
-
-    f32x16_t acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    const int hh = lane >> 5, l31 = lane & 31;
-    const int i16 = lane & 15, q = i16 >> 2, pp = i16 & 3, g2 = (lane >> 4) & 1;
-    auto compute = [&](int buf) __attribute__((always_inline)) {
-        const char* Gs = smem + buf * STAGE;
-        const char* Xs = Gs + OP_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int r = 16 * ks + 8 * hh + q;                      // r & 3 == q; (r + 4) & 3 == q
-            u32x4_t a[2], b[2];
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) {
-                const int chunk = (wm * 64 + mi * 32) / 8 + 2 * g2 + (pp >> 1);
-                const char* ptr = Gs + r * ROW + ((chunk ^ (q << 2)) << 4) + (pp & 1) * 8;
-                const u32x2_t lo = lds_tr16_b64(ptr), hi = lds_tr16_b64(ptr + 4 * ROW);
-                a[mi] = u32x4_t{lo.x, lo.y, hi.x, hi.y};
-            }
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-                const int chunk = (wn * 64 + ni * 32) / 8 + 2 * g2 + (pp >> 1);
-                const char* ptr = Xs + r * ROW + ((chunk ^ (q << 2)) << 4) + (pp & 1) * 8;
-                const u32x2_t lo = lds_tr16_b64(ptr), hi = lds_tr16_b64(ptr + 4 * ROW);
-                b[ni] = u32x4_t{lo.x, lo.y, hi.x, hi.y};
-            }
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-                    acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                        __builtin_bit_cast(bf16x8_t, a[mi]), __builtin_bit_cast(bf16x8_t, b[ni]), acc[mi][ni], 0, 0, 0);
-        }
-    };
-    // bias gradient from the gy tile in LDS: thread t < 128 owns channel t of this tile
-    const bool do_bias = p.dbias != nullptr;
-    float bsum = 0.f;
-    auto bias_from_lds = [&](int buf, int ch) __attribute__((always_inline)) {
-        if (do_bias && (ch % p.tiles_k) == tk && tid < 128) {
-            const char* Gs = smem + buf * STAGE;
-            const int ch = tid >> 3, sub = (tid & 7) * 2;
-#pragma unroll 8
-            for (int r = 0; r < BR; ++r)
-                bsum += bf16_bits_to_f32(*(const unsigned short*)(Gs + r * ROW + ((ch ^ ((r & 3) << 2)) << 4) + sub));
-        }
-    };
-
-    const int nch = (m_end - m_begin + BR - 1) / BR;
-    dma_chunk(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int ch = 0; ch + 1 < nch; ++ch) {
-        const int cur = ch & 1;
-        dma_chunk(ch + 1, cur ^ 1);
-        compute(cur);
-        bias_from_lds(cur, ch);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    compute((nch - 1) & 1);
-    bias_from_lds((nch - 1) & 1, nch - 1);
-    if (do_bias && tid < 128) {
-        const int co = tco * 128 + tid;
-        if (co < p.Cout) atomicAdd(p.dbias + co, bsum);
-    }
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = tco * 128 + wm * 64 + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                const int k = tk * 128 + wn * 64 + ni * 32 + l31;
-                if (co < p.Cout && k < p.Ktot) atomicAdd(p.dw + (size_t)co * p.Ktot + k, acc[mi][ni][r]);
-            }
-}
-
 // Pixel splits of the generic kernel.  Two costs pull against each other (measured per shape, profiles/r01):
 //   * long pixel loops want MANY workgroups: c128->256 @256^2 runs 476 / 497 / 558 TFLOP/s at 512 / 1024 / 2048;
 //   * every split ends with a 64-KB partial tile (or, without a workspace, one fp32 atomic per dW element on addresses shared by
@@ -556,7 +405,7 @@ static void generic_wgrad_plan(const s2e_conv_desc* d, WgradParams* p, int* spli
 // S2E_WGRAD_PARTIAL=<n>: threshold (default 16); 2 = every split launch (bit-reproducible weight gradients of this kernel,
 // ~ +0.4 ms per step); 0 = never.
 static int wgrad_partial_min_splits() {
-    static const int n = [] { const char* e = getenv("S2E_WGRAD_PARTIAL"); return e ? atoi(e) : 16; }();
+    static const int n = s2e_env_int("S2E_WGRAD_PARTIAL", 16);
     return s2e_deterministic() ? 2 : n;
 }
 // Partial tiles + fixed-order reduce for this launch?  S2E_DETERMINISTIC: always -- even an unsplit launch adds its k-tile
@@ -632,24 +481,18 @@ extern "C" int s2e_conv2d_wgrad(int dtype, const void* x, const void* gy, float*
     generic_wgrad_plan(d, &p, &splits);
     const int tiles = p.tiles_k * p.tiles_co;
     hipStream_t st = (hipStream_t)stream;
-    const int br = 32;                               // pixels per chunk (64 measured no faster)
-    static const bool glds = [] { const char* e = getenv("S2E_WGRAD_GLDS"); return e ? atoi(e) != 0 : false; }();
-    const bool glds_path = dtype == S2E_BF16 && glds && d->in_act == S2E_ACT_NONE && d->Cin % 8 == 0 && d->Cout % 8 == 0;
     const int g = tiles * splits;
     // With a workspace the workgroups store their partial tiles and a second kernel adds them up in a fixed order:
     // deterministic, and cheaper than the atomics once a launch has more than a few splits (64 KB written + read per
     // workgroup at HBM rate against 64 KB of float atomics at ~1.3 TB/s chip-wide).
     const size_t need = (size_t)g * (128 * 128 + 128) * sizeof(float);
-    if (wgrad_use_partial(splits) && !glds_path && workspace && workspace_bytes >= need) {
+    if (wgrad_use_partial(splits) && workspace && workspace_bytes >= need) {
         p.partial = (float*)workspace;
         p.bpartial = p.partial + (size_t)g * (128 * 128);
     }
     if (dtype == S2E_BF16) {
-        if (d->Cin % 8 == 0 && d->Cout % 8 == 0) {
-            if (glds_path) conv_wgrad_glds_kernel<<<g, 256, 0, st>>>(p);
-            else if (br == 64) conv_wgrad_kernel<bf16_t, true, 64><<<g, 256, 0, st>>>(p);
-            else conv_wgrad_kernel<bf16_t, true, 32><<<g, 256, 0, st>>>(p);
-        } else conv_wgrad_kernel<bf16_t, false, 32><<<g, 256, 0, st>>>(p);
+        if (d->Cin % 8 == 0 && d->Cout % 8 == 0) conv_wgrad_kernel<bf16_t, true, 32><<<g, 256, 0, st>>>(p);    // (32 pixels per chunk: 64 measured no faster)
+        else conv_wgrad_kernel<bf16_t, false, 32><<<g, 256, 0, st>>>(p);
     } else if (dtype == S2E_F32) {
         if (d->Cin % 4 == 0 && d->Cout % 4 == 0) conv_wgrad_kernel<float, true, 32><<<g, 256, 0, st>>>(p);
         else conv_wgrad_kernel<float, false, 32><<<g, 256, 0, st>>>(p);
@@ -684,7 +527,7 @@ extern "C" int s2e_conv2d_wgrad_multi_supported(int dtype, const s2e_conv_desc* 
 // 6144: 12 per workgroup slot of the chip) goes by its MFMA work -- planned alone (2048 workgroups each) two dozen jobs made 30-40 k
 // workgroups and ~1 GB of partial tiles per step.  Fills ps[i] (shape, tiling, m_per_split) and splits[i].
 static void wgrad_multi_plan(const s2e_wgrad_multi_job* jobs, const int* idx, int n, WgradParams* ps, int* splits) {
-    static const int total_wg = [] { const char* e = getenv("S2E_WGRAD_MULTI_WGS"); return e ? atoi(e) : 6144; }();
+    static const int total_wg = s2e_env_int("S2E_WGRAD_MULTI_WGS", 6144);
     double work[WGM_MAX_JOBS], work_sum = 0.0;
     for (int i = 0; i < n; ++i) {
         const s2e_conv_desc* d = &jobs[idx[i]].d;

@@ -43,8 +43,6 @@
 
 namespace {
 
-__device__ __attribute__((aligned(16))) const uint32_t wb_zero16[4] = {0u, 0u, 0u, 0u};
-
 struct WbJob {
     const bf16_t* x; const bf16_t* gy; float* dw; float* dbias;
     const int* rect_list; const int* rect_count;      // label-sparse: the slabs are the halves of rect_list[0 .. *rect_count)
@@ -161,8 +159,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_batch_kernel(const WbBatch 
     constexpr int NPI = 7;                            // pieces per thread per slab: 4 gy, 3 x
     constexpr int RED_OFF = 2 * STAGE, PLAN_OFF = RED_OFF + 1024;
     __shared__ __attribute__((aligned(1024))) char smem[PLAN_OFF + ((sizeof(WbPlan) + 15) & ~15)];
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = rfl(tid >> 6);
     const int cb = wave >> 1, cib = wave & 1;
@@ -285,13 +281,13 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_batch_kernel(const WbBatch 
             char* dst;
             if constexpr (i < 4) {
                 ok = ok && g_ok;
-                src = ok ? (const void*)(gg + pix * Cout + g_col) : (const void*)wb_zero16;
+                src = ok ? (const void*)(gg + pix * Cout + g_col) : (const void*)s2e_zero16;
                 dst = smem + buf * STAGE + X_BYTES + (8 * i + wave) * 1024;
             } else {
-                src = ok ? (const void*)(xg + pix * Cin + x_col) : (const void*)wb_zero16;
+                src = ok ? (const void*)(xg + pix * Cin + x_col) : (const void*)s2e_zero16;
                 dst = smem + buf * STAGE + (8 * (i - 4) + wave) * 1024;
             }
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+            lds_dma16(src, dst);
         };
 
         f32x16_t acc[9];
@@ -308,7 +304,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_batch_kernel(const WbBatch 
         int r_ahead = 0;                              // list jobs: the rectangle of slab s + 2, requested a slab ahead of its use
         if (rl && s0 + 1 < s1) r_ahead = rl[(s0 + 1) >> 1];
         static_for<0, NPI>([&](auto I) { dma_piece(I, cur, 0); });
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         for (int s = s0; s < s1; ++s) {
             const int buf = (s - s0) & 1;
@@ -376,7 +372,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_batch_kernel(const WbBatch 
                     }
                 }
             });
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             __syncthreads();
             cur = nxt;
         }
@@ -531,26 +527,20 @@ __global__ __launch_bounds__(256) void wgrad_batch_fixup_kernel(const WbBatch b,
 // the dense 28-layer mix of tools/check_wgrad_batch.py --bench (spare, ov): (never, 0) 17.39 ms / 2.22 ms; (48, 0) -- equal unit
 // counts, no overhead term -- 17.44 / 2.78; (48, 4) 17.27 / 2.36; (24, 4) 17.26 / 2.19; (24, 6) 17.27.  Default 24 with ov = 4.
 int wb_spare_min() {
-    static const int v = [] { const char* e = getenv("S2E_WGRAD_BATCH_SPARE"); return e && atoi(e) > 0 ? atoi(e) : 24; }();
+    static const int v = s2e_env_int_ge("S2E_WGRAD_BATCH_SPARE", 1, 24);
     return v;
 }
 
 // experiment switch S2E_WGRAD_BATCH_OV: what a segment costs beside its slabs, in slabs (wb_make_plan's cost model)
 int wb_overhead() {
-    static const int v = [] { const char* e = getenv("S2E_WGRAD_BATCH_OV"); return e && atoi(e) >= 0 ? atoi(e) : 4; }();
+    static const int v = s2e_env_int_ge("S2E_WGRAD_BATCH_OV", 0, 4);
     return v;
 }
 
 int wb_workgroups() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        const char* e = getenv("S2E_WGRAD_BATCH_WGS");   // experiment switch: workgroups of the batched launch (default: one per CU)
-        if (e && atoi(e) > 0) v = atoi(e);
-        if (v > WB_FIX_LIST) v = WB_FIX_LIST;            // (the fix-up's owner list holds WB_FIX_LIST workgroups per tile: ADVICE r5)
-        return v;
-    }();
-    return n;
+    // experiment switch S2E_WGRAD_BATCH_WGS: workgroups of the batched launch (default: one per CU)
+    static const int v = s2e_env_int_ge("S2E_WGRAD_BATCH_WGS", 1, s2e_cu_count());
+    return v > WB_FIX_LIST ? WB_FIX_LIST : v;            // (the fix-up's owner list holds WB_FIX_LIST workgroups per tile: ADVICE r5)
 }
 
 }  // namespace

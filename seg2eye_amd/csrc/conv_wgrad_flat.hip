@@ -34,8 +34,6 @@
 
 namespace {
 
-__device__ __attribute__((aligned(16))) const uint32_t wf_zero16[4] = {0u, 0u, 0u, 0u};
-
 struct WfJob {
     const void* x; const void* gy; float* dw; float* dbias;
     int N, Hi, Wi, Cin, Ho, Wo, Cout, Ktot;
@@ -92,8 +90,6 @@ __device__ __forceinline__ void wf_body(const WfJob& p, const int blk, const int
     constexpr int X_BYTES = XPX * 128, STAGE = X_BYTES + WF_G_BYTES;
     static_assert(NS * STAGE <= WF_SMEM && XPX <= 56 * 8, "LDS budget; seven x pieces per wave");
     constexpr int NXP = 7, NPI = 2 + NXP;             // pieces per thread per slab: 2 gy, up to 7 x
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cb = wave >> 1, cib = wave & 1;
@@ -154,16 +150,16 @@ __device__ __forceinline__ void wf_body(const WfJob& p, const int blk, const int
         char* dst;
         if constexpr (i < 2) {
             const bool ok = v < NEVER && lx < p.Wo && ly < p.Ho;
-            src = ok ? (const void*)(gg + ((size_t)(q.n * p.Ho + ly) * p.Wo + lx) * p.Cout + g_col) : (const void*)wf_zero16;
+            src = ok ? (const void*)(gg + ((size_t)(q.n * p.Ho + ly) * p.Wo + lx) * p.Cout + g_col) : (const void*)s2e_zero16;
             dst = smem + buf * STAGE + X_BYTES + (8 * i + wave) * 1024;
         } else {
             const int P = (v >> 24) & 3;
             const int iy = (ly << SH) + (S == 2 ? (P >> 1) : 0) - p.pad, ix = (lx << SH) + (S == 2 ? (P & 1) : 0) - p.pad;
             const bool ok = v < NEVER && (unsigned)iy < (unsigned)p.Hi && (unsigned)ix < (unsigned)p.Wi;
-            src = ok ? (const void*)(xg + ((size_t)(q.n * p.Hi + iy) * p.Wi + ix) * p.Cin + x_col) : (const void*)wf_zero16;
+            src = ok ? (const void*)(xg + ((size_t)(q.n * p.Hi + iy) * p.Wi + ix) * p.Cin + x_col) : (const void*)s2e_zero16;
             dst = smem + buf * STAGE + (8 * (i - 2) + wave) * 1024;
         }
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        lds_dma16(src, dst);
     };
 
     // ---- fragment addressing (lane roles of the transpose read: conv_wgrad.hip)
@@ -200,15 +196,15 @@ __device__ __forceinline__ void wf_body(const WfJob& p, const int blk, const int
     for (int i = 0; i < NXP; ++i) npw += 8 * (8 * i + wave) < npx ? 1 : 0;
     auto wait_vm = [&](int n) __attribute__((always_inline)) {       // all but the n youngest loads of this wave are back
         switch (n) {
-            case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-            case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-            case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-            case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-            case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-            case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-            case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-            case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-            default: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
+            case 0: wait_vmcnt<0>(); break;
+            case 2: wait_vmcnt<2>(); break;
+            case 3: wait_vmcnt<3>(); break;
+            case 4: wait_vmcnt<4>(); break;
+            case 5: wait_vmcnt<5>(); break;
+            case 6: wait_vmcnt<6>(); break;
+            case 7: wait_vmcnt<7>(); break;
+            case 8: wait_vmcnt<8>(); break;
+            default: wait_vmcnt<9>(); break;
         }
     };
     // slabs s0 .. s0 + PF - 1 ahead of the loop; inside it slab s + PF is requested while slab s is multiplied (its buffer is the one slab
@@ -276,7 +272,7 @@ __device__ __forceinline__ void wf_body(const WfJob& p, const int blk, const int
         });
         buf = buf + 1 == NS ? 0 : buf + 1;
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();                                  // (the bias gather below reuses the first stage)
 
     // ---- combine: lanes 0..31 of a register hold 32 consecutive ci of one (co, tap) row
@@ -328,7 +324,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_flat_kernel(const WfMulti b
 }
 
 int wf_mask() {
-    static const int m = [] { const char* e = getenv("S2E_WGRAD_FLAT"); return e ? atoi(e) : (1 << WF_K4S1) | (1 << WF_K4S2); }();
+    static const int m = s2e_env_int("S2E_WGRAD_FLAT", (1 << WF_K4S1) | (1 << WF_K4S2));
     return m;
 }
 
@@ -374,8 +370,8 @@ int s2e_wgrad_flat_kind(int dtype, const s2e_conv_desc* d) {
 }
 
 int s2e_wgrad_flat_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n_all, hipStream_t st) {
-    static const int total_wg = [] { const char* e = getenv("S2E_WGRAD_FLAT_WGS"); const int v = e ? atoi(e) : 256; return v > 0 ? v : 256; }();
-    static const bool noepi = getenv("S2E_WF_NOEPI") != nullptr;
+    static const int total_wg = s2e_env_int_ge("S2E_WGRAD_FLAT_WGS", 1, 256);
+    static const int noepi = s2e_env_int("S2E_WF_NOEPI", 0) & 7;
     for (int base = 0; base < n_all; base += WF_MAX_JOBS) {
         const int n = n_all - base < WF_MAX_JOBS ? n_all - base : WF_MAX_JOBS;
         WfMulti b{};
@@ -410,7 +406,7 @@ int s2e_wgrad_flat_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n
             p.per_split = ceil_div(p.nslabs, splits);
             p.splits = ceil_div(p.nslabs, p.per_split);
             p.nblk = units[i] * p.splits;
-            p.flags = noepi ? atoi(getenv("S2E_WF_NOEPI")) & 7 : 0;
+            p.flags = noepi;
             // (another job whose dW range overlaps this one's: compared as address ranges, not only as pointers)
             bool shared = false;
             const char* lo = (const char*)p.dw;

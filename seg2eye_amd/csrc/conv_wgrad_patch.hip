@@ -28,8 +28,6 @@
 
 namespace {
 
-__device__ __attribute__((aligned(16))) const uint32_t wz_zero16[4] = {0u, 0u, 0u, 0u};
-
 struct WpParams {
     const void* x; const void* gy; float* dw; float* dbias;
     float* ws;                    // per-workgroup partial tiles [wg][9][128][64] (NULL: atomics straight into dw)
@@ -49,8 +47,6 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_patch_kernel(const WpParams
     constexpr int X_BYTES = XPX * 128, G_BYTES = 128 * 256, STAGE = X_BYTES + G_BYTES;
     constexpr int NPI = 9;                            // pieces per thread per slab: 4 gy, 4 x, +1 x (wave 0)
     __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cb = wave >> 1, cib = wave & 1;
@@ -118,13 +114,13 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_patch_kernel(const WpParams
         const void* src;
         char* dst;
         if constexpr (i < 4) {
-            src = ok ? (const void*)(gg + pix * p.Cout + g_col) : (const void*)wz_zero16;
+            src = ok ? (const void*)(gg + pix * p.Cout + g_col) : (const void*)s2e_zero16;
             dst = smem + buf * STAGE + X_BYTES + (8 * i + wave) * 1024;
         } else {
-            src = ok ? (const void*)(xg + pix * p.Cin + x_col) : (const void*)wz_zero16;
+            src = ok ? (const void*)(xg + pix * p.Cin + x_col) : (const void*)s2e_zero16;
             dst = smem + buf * STAGE + (8 * (i - 4) + wave) * 1024;
         }
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+        lds_dma16(src, dst);
     };
 
     // ---- fragment addressing (see conv_wgrad.hip for the transpose-read lane roles)
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_patch_kernel(const WpParams
         if (rl && s0 + 1 < s1) r_ahead = rl[(s0 + 1) >> 1];
         static_for<0, NPI>([&](auto I) { dma_piece(I, cur, 0); });
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     __syncthreads();
     for (int s = s0; s < s1; ++s) {
         const int buf = (s - s0) & 1;
@@ -224,7 +220,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad_patch_kernel(const WpParams
                     accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(A), __builtin_bit_cast(bf16x8_t, ones), accb, 0, 0, 0);
             }
         });
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         cur = nxt;
     }
@@ -300,13 +296,6 @@ struct WcParams {
     const int* rect_list; const int* rect_count; int tiles_x, tiles_y, splits;
 };
 
-// two bf16 from two LDS addresses into one register: the low half by ds_read_u16 (zero-extended), the high half by
-// ds_read_u16_d16_hi into a second register, OR-ed after the wait.  (A d16_hi read does NOT preserve the other half on
-// this target -- with SRAM ECC the destination's unused half is written as zero -- so the pair cannot share a register.)
-#define S2E_U16_PAIR(lo, hi, addr, off_lo, off_hi) \
-    asm volatile("ds_read_u16 %0, %1 offset:%2" : "=v"(lo) : "v"(addr), "n"(off_lo) : "memory"); \
-    asm volatile("ds_read_u16_d16_hi %0, %1 offset:%2" : "=v"(hi) : "v"(addr), "n"(off_hi) : "memory")
-
 template <int TWS>
 __device__ __forceinline__ void conv_wgrad_c8_body(const WcParams& p, int split, int tco, float* __restrict__ tile, char* smem) {
     typedef bf16_t T;
@@ -314,8 +303,6 @@ __device__ __forceinline__ void conv_wgrad_c8_body(const WcParams& p, int split,
     constexpr int XPIECES = 5;                        // 64 pixels x 16 B per piece; 320 >= 4 x 66
     constexpr int X_BYTES = XPIECES * 1024, G_BYTES = 128 * 256, STAGE = X_BYTES + G_BYTES;
     static_assert(PH * PW <= XPIECES * 64, "patch capacity");
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cb = wave;                              // 32-co block of this wave
@@ -375,13 +362,13 @@ __device__ __forceinline__ void conv_wgrad_c8_body(const WcParams& p, int split,
             const void* src;
             char* dst;
             if constexpr (i < 8) {
-                src = ok ? (const void*)(gg + pix * p.Cout + g_col) : (const void*)wz_zero16;
+                src = ok ? (const void*)(gg + pix * p.Cout + g_col) : (const void*)s2e_zero16;
                 dst = smem + buf * STAGE + X_BYTES + (4 * i + wave) * 1024;
             } else {
-                src = ok ? (const void*)(xg + pix * 8) : (const void*)wz_zero16;
+                src = ok ? (const void*)(xg + pix * 8) : (const void*)s2e_zero16;
                 dst = smem + buf * STAGE + (i == 8 ? wave : 4) * 1024;
             }
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
+            lds_dma16(src, dst);
         };
 
         const int i16 = lane & 15, q4 = i16 >> 2, pq = i16 & 3, g2 = (lane >> 4) & 1;
@@ -399,7 +386,7 @@ __device__ __forceinline__ void conv_wgrad_c8_body(const WcParams& p, int split,
 
         Slab cur = decode(s0);
         static_for<0, 10>([&](auto I) { dma_piece(I, cur, 0); });
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         __syncthreads();
         for (int s = s0; s < s1; ++s) {
             const int buf = (s - s0) & 1;
@@ -442,7 +429,7 @@ __device__ __forceinline__ void conv_wgrad_c8_body(const WcParams& p, int split,
                     acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_operand(A),
                              __builtin_bit_cast(bf16x8_t, u32x4_t{B[c][0], B[c][1], B[c][2], B[c][3]}), acc[c], 0, 0, 0);
             });
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             __syncthreads();
             cur = nxt;
         }
@@ -517,15 +504,6 @@ __global__ __launch_bounds__(256) void wgrad_c8_reduce_kernel(const float* __res
     else if (dbias) atomicAdd(dbias + co, a);
 }
 
-static int wp_cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 // dw[co][t * Cin + ci] += sum over the splits of the (co tile, ci tile) of  ws[wg][t][co % 128][ci % 64].  One thread
 // per 4 consecutive ci; blockIdx.y takes every gridDim.y-th split (small dW: keeps the chip busy; the few partial sums
 // per element that result are combined with atomics).
@@ -561,7 +539,7 @@ __global__ __launch_bounds__(256) void wgrad_patch_reduce_kernel(const float* __
 // slab x tile work items -- one per CU; swept in round 2: 1024 -> 256 moves the 16^2 [gamma | beta] and 8^2 layers here from the
 // generic kernel, generic weight gradient 1.46 -> 1.25 ms per step against +0.05 here; 128 and 64 measure the same.
 int s2e_wgrad_patch_plan(int dtype, const s2e_conv_desc* d) {
-    static const int min_items = [] { const char* e = getenv("S2E_WGRAD_PATCH"); return e ? atoi(e) : 256; }();
+    static const int min_items = s2e_env_int("S2E_WGRAD_PATCH", 256);
     if (min_items <= 0 || dtype != S2E_BF16) return 0;
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->in_act != S2E_ACT_NONE || d->transposed) return 0;
     if (d->Ho != d->Hi || d->Wo != d->Wi || d->Cin % 64 != 0 || d->Cout % 8 != 0 || d->Cout < 64) return 0;
@@ -582,7 +560,7 @@ static void wp_plan(int slab_w, const s2e_conv_desc* d, WpParams& p, int& splits
     p.sx = ceil_div(d->Wi, slab_w); p.sy = ceil_div(d->Hi, 128 / slab_w); p.nslabs = d->N * p.sy * p.sx;
     p.tiles_co = ceil_div(d->Cout, 128); p.tiles_ci = d->Cin / 64;
     const int tiles = p.tiles_co * p.tiles_ci;
-    splits = wp_cu_count() / tiles;                   // one workgroup per CU
+    splits = s2e_cu_count() / tiles;                   // one workgroup per CU
     if (splits < 1) splits = 1;
     if (splits > p.nslabs) splits = p.nslabs;
     p.per_split = ceil_div(p.nslabs, splits);
@@ -639,7 +617,7 @@ int s2e_wgrad_patch_launch(int slab_w, const void* x, const void* gy, float* dw,
 // ---- Cin = 8: bf16, 3x3, stride 1, pad 1, no fused input activation, Cout a multiple of 128, slabs >= 80 % inside the
 // image and at least 256 of them (64^2 and up at batch 8); needs the workspace.
 int s2e_wgrad_c8_plan(int dtype, const s2e_conv_desc* d) {
-    static const bool on = [] { const char* e = getenv("S2E_WGRAD_C8"); return e ? atoi(e) != 0 : true; }();
+    static const bool on = s2e_env_flag("S2E_WGRAD_C8", true);
     if (!on || dtype != S2E_BF16) return 0;
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->in_act != S2E_ACT_NONE || d->transposed) return 0;
     if (d->Ho != d->Hi || d->Wo != d->Wi || d->Cin != 8 || d->Cout % 128 != 0) return 0;
@@ -659,7 +637,7 @@ static void wc_plan(int slab_w, const s2e_conv_desc* d, WcParams& p, int& splits
     p.N = d->N; p.H = d->Hi; p.W = d->Wi; p.Cout = d->Cout;
     p.sx = ceil_div(d->Wi, slab_w); p.sy = ceil_div(d->Hi, 128 / slab_w); p.nslabs = d->N * p.sy * p.sx;
     tiles_co = d->Cout / 128;
-    splits = 2 * wp_cu_count() / tiles_co;            // two 74-KB workgroups per CU
+    splits = 2 * s2e_cu_count() / tiles_co;            // two 74-KB workgroups per CU
     if (splits < 1) splits = 1;
     if (splits > p.nslabs / 2) splits = p.nslabs / 2 > 0 ? p.nslabs / 2 : 1;
     p.per_split = ceil_div(p.nslabs, splits);

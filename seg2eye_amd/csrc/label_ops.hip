@@ -170,7 +170,7 @@ static long label_conv_blocks(int dtype, long npix, int Cout, int fast_min = 655
     const int cgb_h = (cw + vec - 1) / vec;
     const int ppb = ((64 % cgb_h) == 0 && npix >= fast_min) ? 256 : 256 / cgb_h;       // pixels per block per pass
     const long gx = (npix + ppb - 1) / ppb;
-    static const long cap = [] { const char* e = getenv("S2E_LABEL_CONV_CAP"); return e ? atol(e) : 1024L; }();   // (the optimum of 256 ... 2048, measured)
+    static const long cap = s2e_env_long("S2E_LABEL_CONV_CAP", 1024L);   // (the optimum of 256 ... 2048, measured)
     return gx > cap ? cap : gx;
 }
 

@@ -14,8 +14,16 @@ void s2e_set_error(const char* fmt, ...) {
 }
 extern "C" const char* s2e_last_error(void) { return g_err; }
 int s2e_deterministic(void) {
-    static const int v = [] { const char* e = getenv("S2E_DETERMINISTIC"); return e ? atoi(e) != 0 : 0; }();
+    static const int v = s2e_env_flag("S2E_DETERMINISTIC", false);
     return v;
+}
+int s2e_cu_count(void) {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        return v;
+    }();
+    return n;
 }
 extern "C" int s2e_version(void) { return 1; }
 

@@ -59,7 +59,7 @@ static RowGeom row_geom(int C, int vec) {
 // groups): thread = (channel group, one of 32 row lanes); fp32 sums per thread, the 32 lanes folded in fp64 in a fixed order
 // (bit-reproducible), and -- APPLY -- the same block normalises its slice in a second pass that re-reads x from L2.
 static int in_small_hw() {
-    static const int v = [] { const char* e = getenv("S2E_IN_SMALL_HW"); return e ? atoi(e) : 1280; }();
+    static const int v = s2e_env_int("S2E_IN_SMALL_HW", 1280);
     return v;
 }
 

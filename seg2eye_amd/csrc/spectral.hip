@@ -44,8 +44,6 @@ extern "C" int s2e_sn_block_shape(int which, int* rows, int* cols) {
 // conv (9 columns), which takes the scalar loops.  Rows past the matrix are CLAMPED to its last row and weighted with zero, so
 // that a batch's 16 loads are unconditional and all in flight together (a guarded load per row compiles to a branch and a
 // wait per row: 2.6 TB/s instead of 4.5).
-typedef const __attribute__((address_space(1))) float* sn_gptr;
-typedef const __attribute__((address_space(1))) f32x4_t* sn_gptr4;
 
 // ---- t += W^T u over a [BR x 256 V] block (V consecutive columns per thread); block_map = {layer, row0, col0}.
 // Measured on the generator's bank (267 MB; a call's duration, same box): 16x256 75 us, 32x256 74, 64x256 75, 128x256 74 --
@@ -62,16 +60,16 @@ __global__ __launch_bounds__(256) void sn_gemvT_kernel(const s2e_sn_layer* __res
 #pragma unroll
     for (int j = 0; j < V; ++j) acc[j] = 0.f;
     if (col < L.cols) {
-        sn_gptr wp = (sn_gptr)L.w + (size_t)row0 * L.cols + col;
-        sn_gptr up = (sn_gptr)L.u + row0;
+        gptr_f32_t wp = (gptr_f32_t)L.w + (size_t)row0 * L.cols + col;
+        gptr_f32_t up = (gptr_f32_t)L.u + row0;
         if (V == 1 || ((L.cols & 3) == 0 && ((uintptr_t)L.w & 15) == 0)) {
 #pragma unroll
             for (int b = 0; b < BR; b += 16) {
                 float w[16][V];
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
-                    sn_gptr src = wp + (size_t)min(b + k, nr - 1) * L.cols;
-                    if constexpr (V == 4) { const f32x4_t q = *(sn_gptr4)src; w[k][0] = q[0]; w[k][1] = q[1]; w[k][2] = q[2]; w[k][3] = q[3]; }
+                    gptr_f32_t src = wp + (size_t)min(b + k, nr - 1) * L.cols;
+                    if constexpr (V == 4) { const f32x4_t q = *(gptr_f32x4_t)src; w[k][0] = q[0]; w[k][1] = q[1]; w[k][2] = q[2]; w[k][3] = q[3]; }
                     else w[k][0] = *src;
                 }
 #pragma unroll
@@ -148,15 +146,15 @@ __global__ __launch_bounds__(256) void sn_gemv_kernel(const s2e_sn_layer* __rest
         const int cc = min(col, L.cols - 4);                   // a thread past the matrix re-reads its last columns, weighted with zero
         f32x4_t v4;
         if (L.taps > 1) { const int j0 = sn_vidx(L, cc); v4 = f32x4_t{L.v[j0], L.v[j0 + L.taps], L.v[j0 + 2 * L.taps], L.v[j0 + 3 * L.taps]}; }   // (cin % 4 == 0: one tap)
-        else v4 = *(sn_gptr4)((sn_gptr)L.v + cc);
+        else v4 = *(gptr_f32x4_t)((gptr_f32_t)L.v + cc);
         const float on = col < L.cols ? 1.f : 0.f;
         const f32x4_t vv = {v4[0] * on, v4[1] * on, v4[2] * on, v4[3] * on};
-        sn_gptr wp = (sn_gptr)L.w + (size_t)row0 * L.cols + cc;
+        gptr_f32_t wp = (gptr_f32_t)L.w + (size_t)row0 * L.cols + cc;
 #pragma unroll
         for (int b = 0; b < SN_BR; b += 16) {
             f32x4_t w[16];
 #pragma unroll
-            for (int k = 0; k < 16; ++k) w[k] = *(sn_gptr4)(wp + (size_t)min(b + k, nr - 1) * L.cols);
+            for (int k = 0; k < 16; ++k) w[k] = *(gptr_f32x4_t)(wp + (size_t)min(b + k, nr - 1) * L.cols);
 #pragma unroll
             for (int k = 0; k < 16; ++k) {
                 const float q = wave_sum_last((w[k][0] * vv[0] + w[k][1] * vv[1]) + (w[k][2] * vv[2] + w[k][3] * vv[3]));
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(256) void sn_gemv_kernel(const s2e_sn_layer* __rest
             }
         }
     } else {
-        sn_gptr wp = (sn_gptr)L.w + (size_t)row0 * L.cols + col;
+        gptr_f32_t wp = (gptr_f32_t)L.w + (size_t)row0 * L.cols + col;
         for (int r = 0; r < SN_BR; ++r) {
             float q = 0.f;
             if (r < nr)
@@ -230,7 +228,7 @@ __global__ __launch_bounds__(256) void sn_gemvT_chain_kernel(const s2e_sn_layer*
     const long long* sp = sn_sb(L, (k - 1) & 1);
     // the whole 32-row column strip is requested BEFORE |s| is summed: the chain is a string of dependent launches of ~10 us
     // each, and the norm (a pass over s plus a block reduction) otherwise sits in front of the weight loads' latency
-    sn_gptr wp = (sn_gptr)L.w + (size_t)row0 * L.cols + min(col, L.cols - 1);
+    gptr_f32_t wp = (gptr_f32_t)L.w + (size_t)row0 * L.cols + min(col, L.cols - 1);
     float w[SN_T_BR];
 #pragma unroll
     for (int r = 0; r < SN_T_BR; ++r) w[r] = wp[(size_t)min(r, nr - 1) * L.cols];
@@ -264,11 +262,11 @@ __global__ __launch_bounds__(256) void sn_gemv_chain_kernel(const s2e_sn_layer* 
     const long long* tp = sn_tb(L, k & 1);
     const bool vec = (L.cols & 3) == 0 && ((uintptr_t)L.w & 15) == 0;
     const int cc = vec ? min(col, L.cols - 4) : col;         // a thread past the matrix re-reads its last columns, weighted with zero (vv = 0)
-    sn_gptr wp = (sn_gptr)L.w + (size_t)row0 * L.cols + cc;
+    gptr_f32_t wp = (gptr_f32_t)L.w + (size_t)row0 * L.cols + cc;
     f32x4_t w[SN_BR];                                        // all 32 rows requested before |t| is summed (see the W^T u kernel)
     if (vec) {
 #pragma unroll
-        for (int r = 0; r < SN_BR; ++r) w[r] = *(sn_gptr4)(wp + (size_t)min(r, nr - 1) * L.cols);
+        for (int r = 0; r < SN_BR; ++r) w[r] = *(gptr_f32x4_t)(wp + (size_t)min(r, nr - 1) * L.cols);
     } else {                                                 // (the encoder's first layer: 9 columns; row by row this path was the chain's longest block)
 #pragma unroll
         for (int r = 0; r < SN_BR; ++r)

@@ -1,4 +1,5 @@
-// Transpose-read MFMA fragments of the patch-resident weight-gradient kernels (conv_wgrad_patch.hip, conv_wgrad_batch.hip).
+// Transpose-read MFMA fragments of the patch-resident weight-gradient kernels (conv_wgrad_patch.hip, conv_wgrad_batch.hip,
+// conv_wgrad_flat.hip).
 #pragma once
 #include "common.h"
 

@@ -34,6 +34,25 @@ def test_library_exports_every_declared_symbol():
     assert L.s2e_conv_k_pad(_lib.S2E_BF16, 9 * 128) == 1152 and L.s2e_conv_k_pad(_lib.S2E_F32, 80) == 96
 
 
+def test_every_library_switch_is_listed_in_design():
+    """Every S2E_* name the library reads goes through the s2e_env_* readers of csrc/common.h (no other getenv) and stands in
+    DESIGN.md's switch section, the one list of the library's switches."""
+    csrc = os.path.join(ROOT, 'seg2eye_amd', 'csrc')
+    design = open(os.path.join(ROOT, 'DESIGN.md')).read()
+    section = design[design.index('## 4. Experiment switches'):design.index('## 5. ')]
+    listed = set(re.findall(r'S2E_[A-Z0-9_]+', section))
+    read = set()
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name)).read()
+        stray = [ln for ln in text.splitlines() if 'getenv(' in ln and not (name == 'common.h' and 's2e_env_' in ln)]
+        assert not stray, (name, stray)
+        read |= set(re.findall(r's2e_env_[a-z_]+\(\s*"(S2E_[A-Z0-9_]+)"', text))
+        if name != 'common.h':                                  # outside the readers the name is always a literal
+            assert len(re.findall(r's2e_env_[a-z_]+\(', text)) == len(re.findall(r's2e_env_[a-z_]+\(\s*"S2E_', text)), name
+    assert len(read) >= 20, read                            # (a floor against a pattern that stopped matching)
+    assert read <= listed, sorted(read - listed)
+
+
 def test_argument_errors_are_reported_without_a_gpu():
     from seg2eye_amd import _lib
     L = _lib.lib()
