@@ -582,6 +582,27 @@ int s2e_openeds_error(int dtype, const void* fake, const void* target, int N, in
 int s2e_openeds_error_u8(const uint8_t* produced, const uint8_t* target, int N, int H, int W, float* err, void* stream);
 int s2e_resize_to255(int dtype, const void* x, int N, int H, int W, uint8_t* out, int Ho, int Wo, void* stream);
 
+/* ------------------------------------------------------------------ device-side preprocessing of OpenEDS frames
+ * What the dataset's transform does on the host (data/base_dataset.py:51-80, 'fixed' mode), bit for bit:
+ *   s2e_resize_bicubic_u8: Pillow's Image.resize(BICUBIC) of M single-channel uint8 frames (M,H,W) -> (M,Ho,Wo), then the
+ *       per-frame horizontal flip of the result (flip[m] != 0: out[y][x] = r[y][Wo-1-x]) and out = lut[r] (lut: 256 fp32 --
+ *       ToTensor + Normalize evaluated by the caller for every byte value).  out_u8 (NULL = skip): the flipped uint8 frames.
+ *       Pillow's rule is integer arithmetic: per axis, output index i sums `count` source pixels from `xmin` on,
+ *       bounds[i] = {xmin, count}, times the fixed-point taps k[i][0..count) (2^22 = 1.0), and a pass stores
+ *       clamp((2^21 + sum) >> 22, 0, 255); the horizontal pass runs first, the vertical pass on its uint8 result.  The caller
+ *       builds the tables (seg2eye_amd/ops/preprocess.py: bicubic_coeffs): kx int32 [Wo][ksize(W,Wo)], bx int32 [Wo][2], ky int32
+ *       [Ho][ksize(H,Ho)], by int32 [Ho][2], ksize(in,out) = 2*ceil(2*max(in/out,1)) + 1.  A pass whose size does not change is
+ *       skipped and its two tables may be NULL.  Indices read from the tables are clamped to the frame.
+ *       S2E_ERR_UNSUPPORTED when the source rows of ONE output row (ksize(H,Ho) rows of W + Wo bytes) exceed 64 KiB of LDS.
+ *   s2e_resize_nearest_u8: out[m][y][x] = src[m][ys[y]][xs[x']], x' = flip[m] ? Wo-1-x : x -- cv2.INTER_NEAREST with the index
+ *       tables ys int32 [Ho], xs int32 [Wo] built by the caller (src = min(int(dst * in / out), in - 1)).
+ * Both: S2E_ERR_ARG on a NULL pointer or a size <= 0, before any launch. */
+int s2e_resize_bicubic_u8(const uint8_t* src, const uint8_t* flip, int M, int H, int W, int Ho, int Wo,
+                          const int32_t* kx, const int32_t* bx, const int32_t* ky, const int32_t* by, const float* lut,
+                          float* out, uint8_t* out_u8, void* stream);
+int s2e_resize_nearest_u8(const uint8_t* src, const uint8_t* flip, int M, int H, int W, int Ho, int Wo,
+                          const int32_t* ys, const int32_t* xs, uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,8 @@ SIGNATURES = {
     's2e_adam_flat': [_vp, _vp, _vp, _vp, _l, _vp, _vp],
     's2e_adam_flat_ema': [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp],
     's2e_shard_sum': [_i, _vp, _vp, _i, _l, _vp],
+    's2e_resize_bicubic_u8': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    's2e_resize_nearest_u8': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
 }
 
 _lib = None

@@ -12,7 +12,11 @@ Built: the reference's training recipe -- `--preprocess_mode fixed` (resize to c
 cv2.INTER_NEAREST for masks, PIL bicubic for images), ToTensor + Normalize(0.5, 0.5) -> [-1, 1], horizontal flip
 augmentation, the train/validation vs test key sets, style sampling `random` / `first` / `ref` / `ref_random<N>`,
 `target_original`, `get_particular`, `get_validation_indices`, `get_random_indices`.  Other preprocess modes raise.
-cv2 is not in this image: its nearest-neighbour resize is restated by its rule (source index = floor(dst * src / dst))."""
+cv2 is not in this image: its nearest-neighbour resize is restated by its rule (source index = floor(dst * src / dst)).
+
+`--device_preprocess`: `__getitem__` makes the same random draws in the same order but returns the RAW 640 x 400
+uint8 frames (`label_raw`, `style_raw`, `target_raw`) and the flip decision (`flip`); `ops.preprocess.materialize` turns a batch
+of them into the contract above on the GPU, bit-identical to the host transform.  No PIL call is made on that path."""
 import re
 
 import numpy as np
@@ -118,6 +122,8 @@ class OpenEDSDataset(torch.utils.data.Dataset):
         user, idx = self._get_tuple_identifier_from_index(index)
         mask = np.asarray(h5[user][self.label_key][idx])
         params = get_params(self.opt, mask.shape, self.rng)
+        if getattr(self.opt, 'device_preprocess', False):
+            return self._raw_item(h5, user, idx, mask, params)
         mask_tensor = torch.from_numpy(np.ascontiguousarray(get_transform(self.opt, params, mask=True)(mask)))
         filename = h5[user][self.key_filenames][idx]
         filename = filename.decode('utf-8') if isinstance(filename, (bytes, np.bytes_)) else str(filename)
@@ -129,6 +135,23 @@ class OpenEDSDataset(torch.utils.data.Dataset):
             target = np.array(h5[user]['images_ss'][idx])
             out['target'] = transform_image(Image.fromarray(target, mode='L'))
             # only the ORIGINAL is flipped here; the transformed one was flipped by the transform (openeds_dataset.py:113)
+            out['target_original'] = torch.from_numpy(np.expand_dims(flip(target, params['flip']), axis=0).copy()).int()
+        return out
+
+    def _raw_item(self, h5, user, idx, mask, params):
+        """--device_preprocess: the sample as raw frames.  Same draws in the same order as the host path (the flip came first, the
+        style indices follow), so the same `rng` yields the same sample."""
+        if self.opt.preprocess_mode != 'fixed':
+            raise NotImplementedError("--device_preprocess restates preprocess_mode 'fixed' only (got '%s')" % self.opt.preprocess_mode)
+        filename = h5[user][self.key_filenames][idx]
+        filename = filename.decode('utf-8') if isinstance(filename, (bytes, np.bytes_)) else str(filename)
+        filename = re.sub(r'\.', '', filename)
+        style, _, _ = self.get_style_images(user, self.opt.input_ns, None, filename)
+        out = {'label_raw': torch.from_numpy(np.array(mask, dtype=np.uint8)), 'filename': filename, 'user': user, 'style_raw': style,
+               'flip': bool(self.opt.isTrain and not self.opt.no_flip and params['flip'])}      # (what get_transform applies)
+        if self.dataset_key != 'test':
+            target = np.array(h5[user]['images_ss'][idx], dtype=np.uint8)
+            out['target_raw'] = torch.from_numpy(target)
             out['target_original'] = torch.from_numpy(np.expand_dims(flip(target, params['flip']), axis=0).copy()).int()
         return out
 
@@ -172,14 +195,18 @@ class OpenEDSDataset(torch.utils.data.Dataset):
                 sel = sel - n_images
                 selected_idx[i] = sel
             imgs.append(np.asarray(h5[user_id][key][int(sel)]))
+        if transform_image is None:                             # --device_preprocess: the raw frames (ns, 640, 400) uint8
+            return torch.from_numpy(np.stack(imgs).astype(np.uint8, copy=False)), selected_idx, subsets
         tensors = [transform_image(Image.fromarray(im, mode='L')) for im in imgs]
         return torch.stack(tensors), selected_idx, subsets
 
     # ---------------------------------------------------------------- helpers the Tester uses
     def unsqueeze_batch(self, batch):
-        for key in ('style_image', 'target', 'target_original', 'label'):
+        for key in ('style_image', 'target', 'target_original', 'label', 'style_raw', 'target_raw', 'label_raw'):
             if key in batch:
                 batch[key] = batch[key].unsqueeze(0)
+        if 'flip' in batch:
+            batch['flip'] = torch.tensor([bool(batch['flip'])])
         return batch
 
     def get_particular(self, idx):
@@ -203,12 +230,14 @@ def create_dataloader(opt, store=None, style_refs=None, rank=0, world=1):
     ds = OpenEDSDataset(opt, store=store, style_refs=style_refs)
     print('dataset [%s] of size %d was created' % (type(ds).__name__, len(ds)))
     workers = int(opt.nThreads) if store is None else 0
+    # --device_preprocess: the raw frames leave from page-locked memory, so materialize's non_blocking copies are asynchronous
+    kw = {'pin_memory': True} if getattr(opt, 'device_preprocess', False) else {}
     if world > 1 and opt.isTrain:
         sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=not opt.serial_batches,
                                                                   drop_last=True)
-        dl = torch.utils.data.DataLoader(ds, batch_size=opt.batchSize, sampler=sampler, num_workers=workers, drop_last=True)
+        dl = torch.utils.data.DataLoader(ds, batch_size=opt.batchSize, sampler=sampler, num_workers=workers, drop_last=True, **kw)
     else:
         dl = torch.utils.data.DataLoader(ds, batch_size=opt.batchSize, shuffle=not opt.serial_batches, num_workers=workers,
-                                         drop_last=opt.isTrain)
+                                         drop_last=opt.isTrain, **kw)
     dl.N = ds.N
     return dl

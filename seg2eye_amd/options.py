@@ -35,6 +35,7 @@ _DEFAULTS = dict(
     ema_decay=0.0,             # > 0: exponential moving average of netG + netE's weights, kept by the Adam launch (optim.FlatAdam); 0 = off
     ema_start=0,               # optimizer steps during which the average just copies the weights (counted from a resume, like the moments)
     use_ema=False,             # test.py: load <epoch>_net_{G,E}_ema.pth instead of the live weights
+    device_preprocess=False,   # openeds: the dataset hands out raw frames; resize / flip / normalise run on the GPU (ops.preprocess)
 )
 
 
@@ -109,6 +110,8 @@ _CLI = [  # (name, type or 'flag', default, choices)
     ('no_overlap_allreduce', 'flag', False, None),
     ('grad_dtype', _S, 'fp32', ['fp32', 'bf16']), ('grad_exchange', _S, 'allreduce', ['allreduce', 'direct']),
     ('synthetic_size', _I, 64, None),        # samples per epoch of the synthetic dataset
+    # the dataset's resize / flip / normalise as HIP launches on raw frames, bit-identical to the host path; off = host
+    ('device_preprocess', 'flag', False, None),
 ]
 _CLI_TRAIN_BUILD = [
     ('ema_decay', _F, 0.0, None), ('ema_start', _I, 0, None),        # averaged generator weights; 0 = off
@@ -157,6 +160,9 @@ def parse(argv=None, is_train=True):
             setattr(opt, k, v)
     if not is_train:
         opt.continue_train = False
+    if opt.device_preprocess and (opt.dataset_mode != 'openeds' or opt.preprocess_mode != 'fixed'):
+        raise ValueError("--device_preprocess needs --dataset_mode openeds and --preprocess_mode fixed (got '%s', '%s'): it restates "
+                         "that dataset's host transform on the GPU" % (opt.dataset_mode, opt.preprocess_mode))
     if not 0.0 <= opt.ema_decay < 1.0 or opt.ema_start < 0:
         raise ValueError('--ema_decay must lie in [0, 1) (0 = off) and --ema_start must not be negative')
     # train.py replays each step as hipGraphs BY DEFAULT (round 4: the replayed step is 15 % faster than ~900 individual launches

@@ -159,6 +159,7 @@ class Pix2PixModel(nn.Module):
         """Move to the GPU; the label map becomes a uint8 SegMap instead of a one-hot float tensor
         (pix2pix_model.py:138-160)."""
         dev = self.device()
+        data = ops.materialize(data, self.opt, dev)            # (--device_preprocess: a raw batch; any other comes back as it is)
         label = data['label']
         if label.dim() == 4:
             label = label[:, 0]

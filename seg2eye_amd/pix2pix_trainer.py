@@ -161,6 +161,7 @@ class Pix2PixTrainer:
         if self.__dict__.get('_in_ema_scope'):
             raise RuntimeError('a generator step inside ema_scope() would train the averaged weights')
         self._train_mode()
+        data = self._materialized(data)
         if self.use_graphs and self._stage_inputs(data):     # (captures on first use; turns graphs off if that fails)
             self.graph_G.replay(self.sync_G.launch)          # (segment k, then group k's exchange beside segment k+1)
             for k, v in getattr(self, '_static_log', {}).items():   # the replay refreshed these in place: log this step's values
@@ -172,11 +173,18 @@ class Pix2PixTrainer:
     def run_discriminator_one_step(self, data):
         """trainers/pix2pix_trainer.py:37-45."""
         self._train_mode()
+        data = self._materialized(data)
         if self.use_graphs and self._stage_inputs(data):
             self.graph_D.replay()
         else:
             self._d_body(data)
         self.optimizer_D.step(grad_scale=self.sync_D.all_reduce())
+
+    def _materialized(self, data):
+        """--device_preprocess: a raw batch becomes the standard one on the GPU (ops.preprocess.materialize; train.py does this once
+        per batch, before both steps); every other batch comes back as it is."""
+        from .ops.preprocess import materialize
+        return materialize(data, self.opt, self.pix2pix_model.device())
 
     # ---- hipGraph capture ---------------------------------------------------------------------------
     @property

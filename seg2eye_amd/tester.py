@@ -18,6 +18,7 @@ import torch
 
 from . import data as data_mod
 from .networks.loss import MSECalculator
+from .ops.preprocess import materialize
 from .postprocessor import ImageProcessor
 
 
@@ -108,6 +109,7 @@ class Tester:
         error_log = self._prepare_error_log() if write_error_log else None
         all_errors, counter = [], 0
         for i, data_i in enumerate(generator):
+            data_i = materialize(data_i, self.opt, model.device())          # (--device_preprocess: raw frames -> the batch contract)
             counter += data_i['label'].shape[0]
             if counter > limit:
                 break
@@ -157,6 +159,7 @@ class Tester:
             if i % 10 == 0:
                 print('Processing batch %d (processed %d images)' % (i, self.opt.batchSize * i))
             names = [re.sub(r'\.', '', f) for f in data_i['filename']]        # test file names carry a dot to remove
+            data_i = materialize(data_i, self.opt, model.device())
             _, fake_resized = self.forward(model, data_i)
             imgs = fake_resized.cpu().numpy()
             for b, name in enumerate(names):

@@ -6,7 +6,8 @@ same checkpoint files (`<checkpoints_dir>/<name>/<epoch>_net_{G,D,E}.pth`, refer
 resume record, same validation passes -- every `--display_freq` samples a quick one (`--validation_limit` samples), every
 `--full_val_freq` samples a full one, on the train and validation splits, scored with the OpenEDS metric on the device
 (seg2eye_amd/tester.py).  Not carried over (out of scope): the visualizer / TF logging, source-tree copy.
-Data: `--dataset_mode synthetic` (default) or `openeds` (an H5 file at `--dataroot`; needs h5py).
+Data: `--dataset_mode synthetic` (default) or `openeds` (an H5 file at `--dataroot`; needs h5py); with `--device_preprocess` the
+OpenEDS frames are resized, flipped and normalised on the GPU, bit-identical to the host transform.
 
     python train.py --name run1 --batchSize 8 --aspect_ratio 1.0 --niter 1 --niter_decay 0
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 train.py ...
@@ -20,6 +21,7 @@ import torch
 from seg2eye_amd import distributed as dist
 from seg2eye_amd.data import create_dataloader
 from seg2eye_amd.iter_counter import IterationCounter
+from seg2eye_amd.ops.preprocess import materialize
 from seg2eye_amd.options import parse
 from seg2eye_amd.pix2pix_trainer import Pix2PixTrainer
 from seg2eye_amd.tester import Tester
@@ -97,6 +99,7 @@ class TrainingRun:
             sampler.set_epoch(epoch)                             # (DistributedSampler: a new permutation per epoch)
         for i, batch in enumerate(self.dataloader, start=c.epoch_iter):
             c.record_one_iteration()
+            batch = materialize(batch, self.opt, trainer.pix2pix_model.device())     # (--device_preprocess: once, before both steps)
             if i % self.opt.D_steps_per_G == 0:
                 trainer.run_generator_one_step(batch)
             trainer.run_discriminator_one_step(batch)
