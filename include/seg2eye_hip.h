@@ -582,6 +582,29 @@ int s2e_openeds_error(int dtype, const void* fake, const void* target, int N, in
 int s2e_openeds_error_u8(const uint8_t* produced, const uint8_t* target, int N, int H, int W, float* err, void* stream);
 int s2e_resize_to255(int dtype, const void* x, int N, int H, int W, uint8_t* out, int Ho, int Wo, void* stream);
 
+/* ------------------------------------------------------------------ side-by-side validation panels
+ * The reference's visualize_sidebyside (util/visualizer.py:131-166) for a batch of n samples, as three launches on the caller's
+ * stream with no host synchronisation between them: out[i] = [ style | label | target_original | fake | heat ], five h x w cells of
+ * uint8 side by side.  With R = the cv2.INTER_LINEAR resize of s2e_resize_to255 (float64 image, float weights) and norm =
+ * ImageProcessor.normalize over the WHOLE resized batch (min >= -1-1e-6 and max <= 1+1e-6: unchanged; else min >= 0: t / max * 2 - 1;
+ * else a range error), every cell is norm(R(.)):
+ *   style  (n, ns, H, W) fp32: the first min(ns, 4) images of a sample in make_grid(nrow=2, padding=0) order (1: the image, 2: one
+ *          row, 3 / 4: 2 x 2, a missing cell 0), then the fp32 mean of three replicated channels, ((a + a) + a) / 3
+ *   label  (n, H, W) uint8;  target_original (n, Ht, Wt) uint8;  fake (n, H, W) of fake_dtype (S2E_F32 or S2E_BF16)
+ *   heat = |fk - tg| / max_batch |fk - tg| * 2 - 1 from the normalised fake and target cells; all -1 where that maximum is 0
+ *   byte = clamp(trunc((v + 1) * 128), 0, 255).  All value arithmetic is float64, one rounding per operation, in the reference's order.
+ * out: row y of panel i starts at out + i * panel_stride + y * row_stride (bytes; row_stride >= 5 w, any alignment), so the panels
+ * may be the top rows of a larger buffer.  ws: s2e_sidebyside_ws_bytes(n, h, w) bytes, 8-byte aligned, holds the per-workgroup
+ * min / max partials (no atomics; bitwise reproducible).  status: one int the last launch ALWAYS writes -- 0, or bit 0 style, bit 1
+ * label, bit 2 target_original, bit 3 fake set where that tensor holds a NaN or fails normalize's range check (the panel bytes are
+ * then unspecified; nothing is read or written out of bounds).
+ * S2E_ERR_ARG (s2e_sidebyside_ws_bytes: -1) before any launch on a null pointer, a size <= 0, ns < 1, row_stride < 5 w, panels
+ * that overlap, a misaligned ws or status. */
+long s2e_sidebyside_ws_bytes(int n, int h, int w);
+int s2e_sidebyside_u8(int fake_dtype, const void* fake, const float* style, int ns, const uint8_t* label,
+                      const uint8_t* target_original, int n, int H, int W, int Ht, int Wt, int h, int w,
+                      int row_stride, long panel_stride, void* ws, int* status, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ device-side preprocessing of OpenEDS frames
  * What the dataset's transform does on the host (data/base_dataset.py:51-80, 'fixed' mode), bit for bit:
  *   s2e_resize_bicubic_u8: Pillow's Image.resize(BICUBIC) of M single-channel uint8 frames (M,H,W) -> (M,Ho,Wo), then the

@@ -189,6 +189,8 @@ SIGNATURES = {
     's2e_shard_sum': [_i, _vp, _vp, _i, _l, _vp],
     's2e_resize_bicubic_u8': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     's2e_resize_nearest_u8': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
+    's2e_sidebyside_ws_bytes': [_i, _i, _i],
+    's2e_sidebyside_u8': [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _l, _vp, _vp, _vp, _vp],
 }
 
 _lib = None
@@ -212,7 +214,7 @@ def lib():
             fn.argtypes = argtypes
             fn.restype = (C.c_char_p if name == 's2e_last_error' else
                           C.c_size_t if (name.endswith('_workspace_bytes') or name == 's2e_conv_plane_weight_elems') else
-                          C.c_long if name in ('s2e_pack_block_map', 's2e_grad_block_map', 's2e_sngrad_block_map', 's2e_sngrad_scratch_floats', 's2e_label_conv_block_map', 's2e_class_table_block_map') else C.c_int)
+                          C.c_long if name in ('s2e_pack_block_map', 's2e_grad_block_map', 's2e_sngrad_block_map', 's2e_sngrad_scratch_floats', 's2e_label_conv_block_map', 's2e_class_table_block_map', 's2e_sidebyside_ws_bytes') else C.c_int)
         _lib = L
     return _lib
 

@@ -36,6 +36,7 @@ _DEFAULTS = dict(
     ema_start=0,               # optimizer steps during which the average just copies the weights (counted from a resume, like the moments)
     use_ema=False,             # test.py: load <epoch>_net_{G,E}_ema.pth instead of the live weights
     device_preprocess=False,   # openeds: the dataset hands out raw frames; resize / flip / normalise run on the GPU (ops.preprocess)
+    visuals=False,             # train.py: loss_log.txt + side-by-side validation panels (seg2eye_amd/visualizer.py)
 )
 
 
@@ -115,6 +116,8 @@ _CLI = [  # (name, type or 'flag', default, choices)
 ]
 _CLI_TRAIN_BUILD = [
     ('ema_decay', _F, 0.0, None), ('ema_start', _I, 0, None),        # averaged generator weights; 0 = off
+    # the visualiser: loss_log.txt, PNG panels at every quick validation, `visualisation` in the error log; off = none of it
+    ('visuals', 'flag', False, None),
 ]
 _CLI_TEST_BUILD = [
     ('use_ema', 'flag', False, None),                                 # score / generate with the averaged weights' checkpoint files

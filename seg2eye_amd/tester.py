@@ -6,8 +6,10 @@
 
 What differs from the reference: the generated batch never leaves the GPU before it is scored (resize to 400 x 640,
 0..255 truncation and sqrt(sum d^2)/(H W) are `s2e_resize_to255` + `s2e_openeds_error_u8`); the error log carries error / user /
-filename (h5 with h5py, else npz) without the visualiser's side-by-side images; the visdom / TF visualisations are not built
-(out of scope); the dataset is whatever `data.create_dataloader`
+filename (h5 with h5py, else npz) and, with `--visuals`, the reference's fourth dataset `visualisation`: the side-by-side panels,
+built on the device too (seg2eye_amd/visualizer.py).  A `visualizer` handed to the constructor receives the
+statistics lines (`run(log=True)`) and the panels of `run_visual_validation`; without one neither happens (the reference builds
+its own Visualizer there; TensorBoard events are not built).  The dataset is whatever `data.create_dataloader`
 yields (synthetic, or the OpenEDS H5 dataset) -- batches must carry `target_original` (N, 1, 640, 400) for validation."""
 import os
 import re
@@ -20,6 +22,7 @@ from . import data as data_mod
 from .networks.loss import MSECalculator
 from .ops.preprocess import materialize
 from .postprocessor import ImageProcessor
+from .visualizer import CAPTION_ROWS, visualize_sidebyside
 
 
 class Tester:
@@ -32,6 +35,7 @@ class Tester:
         if not hasattr(self.opt, 'results_dir'):
             self.opt.results_dir = 'results/'
         self.dataloader = data_mod.create_dataloader(self.opt)
+        self.visualizer = visualizer
         self.is_validation = self.opt.dataset_key in ['validation', 'train']
         self.N = getattr(self.dataloader, 'N', len(self.dataloader) * self.opt.batchSize)
         self.results_dir = os.path.join(opt.checkpoints_dir, self.opt.name, self.opt.results_dir, self.opt.dataset_key)
@@ -76,18 +80,24 @@ class Tester:
     def _prepare_error_log(self):
         """tester.py:67-74: `error_log_<dataset_key>.h5` with one row per sample -- datasets `error` (float64), `user` (S4),
         `filename` (S13).  Written with h5py when it is installed; this image has none, so the same three arrays go to
-        `error_log_<dataset_key>.npz` instead (np.load gives the same names).  The reference's fourth dataset, `visualisation`
-        (side-by-side images rendered by util/visualizer.py with cv2), belongs to the visualiser: not built."""
-        return {'error': np.zeros((self.N,), dtype=np.float64), 'user': np.zeros((self.N,), dtype='S4'),
-                'filename': np.zeros((self.N,), dtype='S13')}
+        `error_log_<dataset_key>.npz` instead (np.load gives the same names).  With `--visuals` the reference's fourth dataset,
+        `visualisation` (N, 1, 380, 1000) uint8: one side-by-side panel per sample (380 KB each, held in memory until the close)."""
+        log = {'error': np.zeros((self.N,), dtype=np.float64), 'user': np.zeros((self.N,), dtype='S4'),
+               'filename': np.zeros((self.N,), dtype='S13')}
+        if getattr(self.opt, 'visuals', False):
+            log['visualisation'] = np.zeros((self.N, 1, 320 + CAPTION_ROWS, 5 * 200), dtype=np.uint8)
+        return log
 
-    def _write_error_log_batch(self, error_log, data_i, i, errors):
-        """tester.py:76-91 without the visualisation."""
+    def _write_error_log_batch(self, error_log, data_i, i, errors, fake=None):
+        """tester.py:76-91; the panels of a batch are normalised over that batch, as there."""
         a = i * self.opt.batchSize
         b = min(a + len(errors), self.N)
         error_log['user'][a:b] = np.array(list(data_i['user']), dtype='S4')[:b - a]
         error_log['filename'][a:b] = np.array(list(data_i['filename']), dtype='S13')[:b - a]
         error_log['error'][a:b] = np.asarray(errors, dtype=np.float64)[:b - a]
+        if 'visualisation' in error_log:
+            visuals = visualize_sidebyside({**data_i, 'fake': fake}, error_list=errors)
+            error_log['visualisation'][a:b] = np.stack(list(visuals.values()))[:b - a]
         return error_log
 
     def _close_error_log(self, error_log):
@@ -116,10 +126,10 @@ class Tester:
             if i % 10 == 9:
                 print('Processing batch %d' % i)
                 print('Error so far: %s' % (np.sum(all_errors) / len(all_errors) * 1471))
-            errors, _, _, _ = self.run_batch(data_i, model)
+            errors, fake, _, _ = self.run_batch(data_i, model)
             all_errors += list(errors)
             if error_log is not None:
-                self._write_error_log_batch(error_log, data_i, i, errors)
+                self._write_error_log_batch(error_log, data_i, i, errors, fake)
         if error_log is not None:
             print('error log: %s' % self._close_error_log(error_log))
         return all_errors
@@ -132,6 +142,38 @@ class Tester:
             print('  %s, %.2f' % (k, errors_dict[k]))
         print('  dataset_key: %s, model: %s, epoch: %s, n_steps: %s' % (self.opt.dataset_key, self.opt.name, epoch, n_steps))
 
+    def run_visual_validation(self, model, mode, epoch, n_steps, limit):
+        """tester.py:131-151: generate `limit` samples of the mode's index list, draw them side by side as ONE batch (its panels
+        share the batch-wide normalisation and heat scale) and hand the panels to the visualiser.  A dataset without index lists
+        is walked from the start, as in `run_partial_modes`.  -> the panels (OrderedDict)."""
+        print("Visualizing images for mode '%s'..." % mode)
+        try:
+            indices = self._get_validation_indices(mode, limit)
+        except NotImplementedError:
+            indices = None
+        batches, errors, count = [], [], 0
+        for data_i in self.get_iterator(self.dataloader, indices=indices):
+            if count >= limit:
+                break
+            data_i = materialize(data_i, self.opt, model.device())
+            e, fake, _, _ = self.run_batch(data_i, model)
+            batches.append({**data_i, 'fake': fake})
+            errors += list(e)
+            count += len(e)
+        result = {k: [x for b in batches for x in b[k]] for k in ('user', 'filename')}
+        for k in ('style_image', 'target_original', 'fake', 'label'):
+            result[k] = torch.cat([torch.as_tensor(b[k]).to(batches[0]['fake'].device) for b in batches], dim=0)
+        visuals = visualize_sidebyside(result, limit=limit, log_key='%s/%s' % (self.opt.dataset_key, mode), w=200, h=320,
+                                       error_list=np.asarray(errors).reshape(-1))
+        if self.visualizer is not None:
+            self.visualizer.display_current_results(visuals, epoch, n_steps)
+        return visuals
+
+    def log_visualizer(self, errors_dict, epoch=0, total_steps_so_far=0):
+        """tester.py:178-191."""
+        self.visualizer.print_current_errors(epoch or 0, total_steps_so_far or 0, errors_dict, t=0)
+        self.visualizer.plot_current_errors(errors_dict, total_steps_so_far)
+
     def run(self, model, mode, epoch=None, n_steps=None, limit=-1, write_error_log=False, log=False):
         """tester.py:165-176."""
         print("Running validation for mode '%s'..." % mode)
@@ -140,15 +182,21 @@ class Tester:
         all_errors = self.run_validation(model, generator, limit=limit, write_error_log=write_error_log)
         errors_dict = MSECalculator.calculate_error_statistics(all_errors, mode=mode, dataset_key=self.opt.dataset_key)
         self.print_results(all_errors, errors_dict, epoch, n_steps)
+        if log and self.visualizer is not None:
+            self.log_visualizer(errors_dict, epoch, n_steps)
         return all_errors, errors_dict
 
     def run_partial_modes(self, model, epoch, n_steps, log=False, visualize_images=False, limit=-1):
         """tester.py:221-233: a quick validation on `limit` random samples ('rand'); a dataset without index lists (the
-        synthetic one) is walked from the start for `limit` samples instead.  (No image visualisation: not built.)"""
+        synthetic one) is walked from the start for `limit` samples instead.  `visualize_images`: then 4 samples are drawn side
+        by side (`run_visual_validation`, which walks such a dataset from the start too)."""
         try:
-            return self.run(model=model, mode='rand', epoch=epoch, n_steps=n_steps, log=log, limit=limit)
+            out = self.run(model=model, mode='rand', epoch=epoch, n_steps=n_steps, log=log, limit=limit)
         except NotImplementedError:
-            return self.run(model=model, mode='full', epoch=epoch, n_steps=n_steps, log=log, limit=limit)
+            out = self.run(model=model, mode='full', epoch=epoch, n_steps=n_steps, log=log, limit=limit)
+        if visualize_images:
+            self.run_visual_validation(model, mode='rand', epoch=epoch, n_steps=n_steps, limit=4)
+        return out
 
     def run_test(self, model, limit=-1):
         """tester.py:193-219: one uint8 .npy of shape (1, 640, 400) per sample + the list of written paths."""

@@ -5,11 +5,15 @@ same checkpoint files (`<checkpoints_dir>/<name>/<epoch>_net_{G,D,E}.pth`, refer
 `<epoch>_net_{G,E}_ema.pth`, the averaged generator weights, which the validation passes then score) and `iter.txt`
 resume record, same validation passes -- every `--display_freq` samples a quick one (`--validation_limit` samples), every
 `--full_val_freq` samples a full one, on the train and validation splits, scored with the OpenEDS metric on the device
-(seg2eye_amd/tester.py).  Not carried over (out of scope): the visualizer / TF logging, source-tree copy.
+(seg2eye_amd/tester.py).  With `--visuals` the reference's Visualizer runs too (seg2eye_amd/visualizer.py): every loss and metric
+line also goes to `loss_log.txt`, every quick validation writes side-by-side panels (style images | label map | ground truth |
+generated image | error heat map, built on the GPU: DESIGN 3.12) as PNG files under `visuals/step<n>/`, and `--write_error_log`
+gains the `visualisation` dataset.  Not carried over (out of scope): TF logging / HTML pages, source-tree copy.
 Data: `--dataset_mode synthetic` (default) or `openeds` (an H5 file at `--dataroot`; needs h5py); with `--device_preprocess` the
 OpenEDS frames are resized, flipped and normalised on the GPU, bit-identical to the host transform.
 
     python train.py --name run1 --batchSize 8 --aspect_ratio 1.0 --niter 1 --niter_decay 0
+    python train.py --name run1 --batchSize 8 --aspect_ratio 1.0 --display_freq 1000 --visuals     # + loss_log.txt and PNG panels
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 train.py ...
 """
 import contextlib
@@ -25,6 +29,7 @@ from seg2eye_amd.ops.preprocess import materialize
 from seg2eye_amd.options import parse
 from seg2eye_amd.pix2pix_trainer import Pix2PixTrainer
 from seg2eye_amd.tester import Tester
+from seg2eye_amd.visualizer import Visualizer
 
 
 class TrainingRun:
@@ -43,7 +48,8 @@ class TrainingRun:
         self.counter = IterationCounter(opt, len(self.dataloader) * opt.batchSize)
         self.world = world
         # validation runs on rank 0 only (it has no collectives); the reference keeps one tester per split
-        self.testers = [Tester(opt, dataset_key=split) for split in ('train', 'validation')] if rank == 0 else []
+        self.visualizer = Visualizer(opt) if opt.visuals and rank == 0 else None      # (--visuals: one for the run, as in the reference)
+        self.testers = [Tester(opt, dataset_key=split, visualizer=self.visualizer) for split in ('train', 'validation')] if rank == 0 else []
         c = self.counter
         self.duties = ((c.needs_printing, self.report), (c.needs_displaying, self.quick_validation),
                        (c.needs_saving, self.save_latest), (c.needs_full_validation, self.full_validation))
@@ -55,6 +61,9 @@ class TrainingRun:
             return
         c = self.counter
         losses = self.trainer.get_latest_losses(include_log_losses=True)
+        if self.visualizer is not None:
+            self.visualizer.print_current_errors(self.epoch, c.total_steps_so_far, losses, c.time_per_iter)
+            return self.visualizer.plot_current_errors(losses, c.total_steps_so_far)
         head = '(epoch: %d, iters: %d, time: %.3f) ' % (self.epoch, c.total_steps_so_far, c.time_per_iter)
         print(head + ' '.join('%s: %.3f' % (name, float(v.float().mean())) for name, v in losses.items()), flush=True)
 
@@ -71,7 +80,7 @@ class TrainingRun:
         with torch.no_grad(), dist.solo(), self._weights():
             for t in self.testers:
                 t.run_partial_modes(model=self.trainer.pix2pix_model, epoch=self.epoch, n_steps=self.counter.total_steps_so_far,
-                                    log=True, visualize_images=False, limit=self.opt.validation_limit)
+                                    log=True, visualize_images=self.visualizer is not None, limit=self.opt.validation_limit)
         self.trainer.sync_replica_buffers()                      # rank 0's train-mode pass advanced its u, v / BN statistics
 
     def full_validation(self):
