@@ -166,8 +166,9 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 
 // compile-time loop: f(integral_constant<int, I>) for I in [0, N) -- indices stay constants, so small
 // per-thread arrays are always register-allocated (never scratch / LDS-promoted)
+template <int I> using int_c = std::integral_constant<int, I>;
 template <int I, int N, typename F> __device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) { f(std::integral_constant<int, I>{}); static_for<I + 1, N>(f); }
+    if constexpr (I < N) { f(int_c<I>{}); static_for<I + 1, N>(f); }
 }
 
 // Zero-fill as a KERNEL, never hipMemsetAsync: inside a captured hipGraph (ROCm 7.x) memset nodes were
@@ -177,6 +178,21 @@ __global__ void s2e_zero_kernel(uint32_t* __restrict__ p, size_t n_words);
 int s2e_zero_async(void* ptr, size_t bytes, hipStream_t st);
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+
+// ---------------------------------------------------------------- dtype dispatch and launch geometry (host)
+// f(T{}) with T the element type of dtype; any other dtype is S2E_ERR_ARG "<name>: bad dtype <dtype>".  A launcher whose dtype must be
+// refused ahead of its other checks says S2E_CHECK_DTYPE there: the dispatcher refuses only where it is called.
+template <typename F> static inline int s2e_with_dtype(int dtype, const char* name, F&& f) {
+    if (dtype == S2E_BF16) return f(bf16_t{});
+    if (dtype == S2E_F32) return f(float{});
+    S2E_FAIL(S2E_ERR_ARG, "%s: bad dtype %d", name, dtype);
+}
+#define S2E_CHECK_DTYPE(dtype, name) do { if ((dtype) != S2E_BF16 && (dtype) != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "%s: bad dtype %d", name, dtype); } while (0)
+static inline int s2e_vec_lanes(int dtype) { return dtype == S2E_BF16 ? 8 : 4; }      // elements of a 16-byte vector (Vec<T>::N)
+static inline int s2e_k_tile(int dtype) { return dtype == S2E_BF16 ? 64 : 32; }       // K elements of one MFMA tile step; s2e_conv_k_pad pads to it
+// 256-thread blocks for n items of a grid-stride kernel, at most cap
+static inline int s2e_grid1d(long n, int cap = 8192) { const long b = (n + 255) / 256; return (int)(b < cap ? b : cap); }
+static inline int s2e_pow2_shift(int v) { for (int b = 0; b < 31; ++b) if ((1 << b) == v) return b; return -1; }   // log2 of a power of two, else -1
 
 // S2E_DETERMINISTIC=1 (read once per process): every gradient of the train step is summed in a fixed order -- the generic weight
 // gradient's partial tiles for every split launch, one reduction pass instead of several combined with float atomics, the patch

@@ -510,18 +510,16 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(const ConvKParams p) {
 static int bn_for(int cout) { return cout > 64 ? 128 : (cout > 32 ? 64 : 32); }
 
 extern "C" int s2e_conv_cout_pad(int cout) { const int bn = bn_for(cout); return ceil_div(cout, bn) * bn; }
-extern "C" int s2e_conv_k_pad(int dtype, int k) { const int bk = dtype == S2E_BF16 ? 64 : 32; return ceil_div(k, bk) * bk; }
+extern "C" int s2e_conv_k_pad(int dtype, int k) { const int bk = s2e_k_tile(dtype); return ceil_div(k, bk) * bk; }
 
 template <typename T>
 static int launch_finish_t(const ConvKParams& p, hipStream_t st) {
-    const long nvec = (long)p.M * p.Cout / Vec<T>::N + 1;
-    const int fgrid = (int)((nvec + 255) / 256 < 4096 ? (nvec + 255) / 256 : 4096);
-    conv_finish_kernel<T><<<fgrid, 256, 0, st>>>(p);
+    conv_finish_kernel<T><<<s2e_grid1d((long)p.M * p.Cout / Vec<T>::N + 1, 4096), 256, 0, st>>>(p);
     S2E_CHECK_LAUNCH("conv_finish_kernel");
     return S2E_OK;
 }
 static int launch_finish(int dtype, const ConvKParams& p, hipStream_t st) {
-    return dtype == S2E_BF16 ? launch_finish_t<bf16_t>(p, st) : launch_finish_t<float>(p, st);
+    return s2e_with_dtype(dtype, "s2e_conv2d", [&](auto t) { return launch_finish_t<decltype(t)>(p, st); });
 }
 
 template <typename T, int BN>
@@ -547,7 +545,7 @@ static int launch_conv(const ConvKParams& p, hipStream_t st, bool s2 = false) {
 static bool s2_class_mode(int dtype, const s2e_conv_desc* d) {
     static const bool on = s2e_env_flag("S2E_IGEMM_S2CLASS", true);
     static const bool glds = s2e_env_flag("S2E_IGEMM_GLDS", true);
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     return on && glds && d->transposed && d->stride == 2 && d->in_act == S2E_ACT_NONE && d->Cin % vec == 0 && d->KH >= 2 && d->KW >= 2;
 }
 // pixel tiles of the four classes (oy & 1, ox & 1): prefix sums into t0[5]
@@ -567,7 +565,7 @@ static void plan_splits(int dtype, const s2e_conv_desc* d, int* tiles, int* tile
     const int M = d->N * d->Ho * d->Wo;
     *tiles_n = ceil_div(d->Cout, bn);
     *tiles = ceil_div(M, 128) * (*tiles_n);
-    const int nk = s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin) / (dtype == S2E_BF16 ? 64 : 32);
+    const int nk = s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin) / s2e_k_tile(dtype);
     if (s2_class_mode(dtype, d)) {                   // per-class tiles, never split (K shrinks to a quarter)
         int t0[5];
         s2_class_tiles(d, t0);

@@ -591,7 +591,7 @@ int s2e_conv_patch_plan(int dtype, const s2e_conv_desc* d, s2e_patch_plan* plan)
     if (!plan) plan = &local;
     plan->tw = plan->th = 0; plan->splits = 1; plan->bn = 0;
     if (min_tiles <= 0) return 0;
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     const int ks = d->KH;
     plan->s2d = 0;
     if (dtype == S2E_BF16 && ks == 4 && d->KW == 4 && d->stride == 2 && d->pad == 2 && d->in_act == S2E_ACT_NONE) {
@@ -673,7 +673,7 @@ int s2e_conv_patch_launch(int dtype, const s2e_patch_plan* plan, const void* x, 
     const int bn = plan->bn ? plan->bn : (d->Cout > 64 ? 128 : 64);
     p.tiles_x = ceil_div(d->Wo, p.tw); p.tiles_y = ceil_div(d->Ho, p.th); p.tiles_n = ceil_div(d->Cout, bn);
     p.tiles_out = p.N * p.tiles_y * p.tiles_x * p.tiles_n;
-    p.splits = plan->splits; p.cps = d->Cin / (dtype == S2E_BF16 ? 64 : 32) / plan->splits;
+    p.splits = plan->splits; p.cps = d->Cin / s2e_k_tile(dtype) / plan->splits;
     p.tiles = p.tiles_out * plan->splits;
     p.M = d->N * d->Ho * d->Wo; p.partial = partial;
     if (plan->s2d) {
@@ -692,9 +692,8 @@ int s2e_conv_patch_launch(int dtype, const s2e_patch_plan* plan, const void* x, 
         p.tiles_out = p.N * p.tiles_y * p.tiles_x * p.tiles_n; p.tiles = p.tiles_out;
         return launch_patch<bf16_t, 128>(p, 2, st, 2);
     }
-    if (dtype == S2E_BF16) return bn == 128 ? launch_patch<bf16_t, 128>(p, d->KH, st) : launch_patch<bf16_t, 64>(p, d->KH, st);
-    if (dtype == S2E_F32) return bn == 128 ? launch_patch<float, 128>(p, d->KH, st) : launch_patch<float, 64>(p, d->KH, st);
-    S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d: bad dtype %d", dtype);
+    return s2e_with_dtype(dtype, "s2e_conv2d", [&](auto t) { using T = decltype(t);
+        return bn == 128 ? launch_patch<T, 128>(p, d->KH, st) : launch_patch<T, 64>(p, d->KH, st); });
 }
 
 // ------------------------------------------------------------------------------------ fused [gamma | beta] conv + modulation
@@ -708,7 +707,7 @@ static int fused_plan(int dtype, int N, int H, int W, int C, int nh, int flags, 
     static const int min_tiles = s2e_env_int("S2E_SPADE_FUSED_TILES", 96);
     if (min_tiles <= 0 && !(flags & 1)) return 0;
     if (C <= 0 || C % 64 != 0 || N <= 0 || H <= 0 || W <= 0) return 0;
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     if (nh % (8 * vec) != 0) return 0;
     *d = s2e_conv_desc{N, H, W, nh, H, W, 2 * C, 3, 3, 1, 1, 0, S2E_ACT_NONE, S2E_ACT_NONE, S2E_AUX_NONE};
     plan->splits = 1; plan->tw = plan->th = 0;
@@ -750,7 +749,7 @@ static int spade_conv_modulate_impl(int dtype, const void* actv, const void* w_p
     if ((rect_list == nullptr) != (rect_count == nullptr)) S2E_FAIL(S2E_ERR_ARG, "s2e_spade_conv_modulate_sparse: rect_list and rect_count go together");
     if (((uintptr_t)stats | (uintptr_t)style | (uintptr_t)bias) & 15 || (style_ld & 3))
         S2E_FAIL(S2E_ERR_ARG, "s2e_spade_conv_modulate: stats, style and bias must be 16-byte aligned (style_ld a multiple of 4)");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_spade_conv_modulate: bad dtype %d", dtype);
+    S2E_CHECK_DTYPE(dtype, "s2e_spade_conv_modulate");
     s2e_conv_desc d; s2e_patch_plan plan;
     if (!fused_plan(dtype, N, H, W, C, nh, flags, &d, &plan))
         S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_spade_conv_modulate: shape N=%d %dx%d C=%d nh=%d is not taken by the fused kernel "
@@ -761,13 +760,13 @@ static int spade_conv_modulate_impl(int dtype, const void* actv, const void* w_p
     PatchParams p{};
     p.x = actv; p.w = w_packed; p.bias = bias; p.y = out;
     p.N = N; p.Hi = H; p.Wi = W; p.Cin = nh; p.Ho = H; p.Wo = W; p.Cout = 2 * C;
-    p.Kpad = ceil_div(9 * nh, dtype == S2E_BF16 ? 64 : 32) * (dtype == S2E_BF16 ? 64 : 32);
+    p.Kpad = s2e_conv_k_pad(dtype, 9 * nh);
     p.org = -1; p.flip = 0; p.out_act = S2E_ACT_NONE; p.aux_mode = S2E_AUX_NONE;
     p.tw = plan.tw; p.th = plan.th;
     p.tw_shift = (plan.tw & (plan.tw - 1)) == 0 ? __builtin_ctz(plan.tw) : -1;
     p.tiles_x = ceil_div(W, p.tw); p.tiles_y = ceil_div(H, p.th); p.tiles_n = C / 64;
     p.tiles_out = N * p.tiles_y * p.tiles_x * p.tiles_n;
-    p.splits = 1; p.cps = nh / (dtype == S2E_BF16 ? 64 : 32); p.tiles = p.tiles_out;
+    p.splits = 1; p.cps = nh / s2e_k_tile(dtype); p.tiles = p.tiles_out;
     p.M = N * H * W; p.partial = nullptr;
     p.mx = x; p.mstats = stats; p.mstyle = style; p.msld = style_ld > 0 ? style_ld : 2 * C; p.mgamma = gamma_out;
     p.mup = (flags & 8) != 0;
@@ -776,10 +775,9 @@ static int spade_conv_modulate_impl(int dtype, const void* actv, const void* w_p
     p.rect_list = rect_list; p.rect_count = rect_count;
     const int grid = p.tiles < s2e_cu_count() ? p.tiles : s2e_cu_count();
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) conv_patch_kernel<bf16_t, 128, 3, true><<<grid, 512, 0, st>>>(p);
-    else conv_patch_kernel<float, 128, 3, true><<<grid, 512, 0, st>>>(p);
-    S2E_CHECK_LAUNCH("conv_patch_kernel (fused modulation)");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_spade_conv_modulate", [&](auto t) {
+        conv_patch_kernel<decltype(t), 128, 3, true><<<grid, 512, 0, st>>>(p);
+        S2E_CHECK_LAUNCH("conv_patch_kernel (fused modulation)"); return S2E_OK; });
 }
 
 extern "C" int s2e_spade_conv_modulate(int dtype, const void* actv, const void* w_packed, const float* bias, const void* x,

@@ -672,7 +672,7 @@ static int small_fwd(const SmallConvParams& p, int kind, hipStream_t st) {
 }
 
 int s2e_small_conv_kind(int dtype, const s2e_conv_desc* d) {
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     if (!small_ks(d)) return SMALL_NONE;
     if (s2e_c8s2_fwd_ok(dtype, d)) return SMALL_FWD_C8S2;
     if (s2e_c8s2_dgrad_ok(dtype, d)) return SMALL_DGRAD_C8S2;
@@ -692,12 +692,12 @@ int s2e_small_conv_launch(int dtype, int kind, const SmallConvParams& p, hipStre
     if (kind == SMALL_DGRAD_C8S2) return s2e_c8s2_dgrad_launch(p, st);
     if (kind == SMALL_FWD_COUT1 && dtype == S2E_BF16 && cout1_mfma_plan(p, &t, &wk, &nkw))
         return p.KH == 3 ? cout1_mfma_go<3>(p, t, wk, nkw, st) : cout1_mfma_go<4>(p, t, wk, nkw, st);
-    if (p.KH == 3) return dtype == S2E_BF16 ? small_fwd<bf16_t, 3>(p, kind, st) : small_fwd<float, 3>(p, kind, st);
-    return dtype == S2E_BF16 ? small_fwd<bf16_t, 4>(p, kind, st) : small_fwd<float, 4>(p, kind, st);
+    return s2e_with_dtype(dtype, "s2e_conv2d", [&](auto t) { using T = decltype(t);
+        return p.KH == 3 ? small_fwd<T, 3>(p, kind, st) : small_fwd<T, 4>(p, kind, st); });
 }
 
 int s2e_small_wgrad_kind(int dtype, const s2e_conv_desc* d) {
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     if (!small_ks(d)) return SMALL_NONE;
     if (d->Cout == 1 && d->stride == 1 && d->Cin % vec == 0 && pow2_le64(d->Cin / vec)) return SMALL_WGRAD_COUT1;
     if (d->Cin == 1 && d->Cout % vec == 0 && pow2_le64(d->Cout / vec)) return SMALL_WGRAD_CIN1;
@@ -744,8 +744,9 @@ int s2e_small_wgrad_launch(int dtype, int kind, const s2e_conv_desc* d, const Sm
     const int nout = d->KH * d->KW * c;
     const size_t lds = (size_t)nout * sizeof(float) + band_patch_bytes(bd, d->KH);
     float* ws = (float*)workspace;
-    if (d->KH == 3) { if (dtype == S2E_BF16) small_wgrad_go<bf16_t, 3>(kind, p, bd, grid, lds, ws, st); else small_wgrad_go<float, 3>(kind, p, bd, grid, lds, ws, st); }
-    else            { if (dtype == S2E_BF16) small_wgrad_go<bf16_t, 4>(kind, p, bd, grid, lds, ws, st); else small_wgrad_go<float, 4>(kind, p, bd, grid, lds, ws, st); }
+    if (const int rc = s2e_with_dtype(dtype, "s2e_conv2d_wgrad", [&](auto t) { using T = decltype(t);
+            if (d->KH == 3) small_wgrad_go<T, 3>(kind, p, bd, grid, lds, ws, st); else small_wgrad_go<T, 4>(kind, p, bd, grid, lds, ws, st);
+            return S2E_OK; })) return rc;
     int slabs = grid / 32;
     slabs = slabs < 1 ? 1 : (slabs > 8 ? 8 : slabs);
     if (s2e_deterministic()) slabs = 1;              // (several row slabs are combined with float atomics)

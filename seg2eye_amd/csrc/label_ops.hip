@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void label_conv3x3_batch_kernel(const uint8_t*
 // fill the chip), 2048 inside the batched launch, where the other layers' blocks do: a 64^2 x 8 layer then has 128 blocks instead of 1024,
 // each of which builds the layer's 18-KB table first
 static long label_conv_blocks(int dtype, long npix, int Cout, int fast_min = 65536) {
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     const int cw = Cout < 128 ? Cout : 128;
     const int cgb_h = (cw + vec - 1) / vec;
     const int ppb = ((64 % cgb_h) == 0 && npix >= fast_min) ? 256 : 256 / cgb_h;       // pixels per block per pass
@@ -179,17 +179,16 @@ extern "C" int s2e_label_conv3x3(int dtype, const uint8_t* label, const float* w
     if (!label || !weight || !out || N <= 0 || h <= 0 || w <= 0 || Cout <= 0 || ncls <= 0 || ncls > 7)
         S2E_FAIL(S2E_ERR_ARG, "s2e_label_conv3x3: bad argument");
     if (H % h || W % w) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_label_conv3x3: %dx%d is not an integer multiple of %dx%d", H, W, h, w);
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_label_conv3x3: bad dtype %d", dtype);
+    S2E_CHECK_DTYPE(dtype, "s2e_label_conv3x3");
     const long npix = (long)N * h * w;
     if (npix >= (1L << 31)) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_label_conv3x3: too many pixels for 32-bit indices");
     const long gx = label_conv_blocks(dtype, npix, Cout);
     dim3 grid((unsigned)gx, ceil_div(Cout, 128));
     const size_t lds = ((size_t)(9 * ncls + 1) * 132 + (size_t)ncls * 128) * sizeof(float) + (size_t)ncls * 128 * 2;     // table rows at a pitch of 132 floats, uniform rows, the same as stored bf16
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) label_conv3x3_kernel<bf16_t><<<grid, 256, lds, st>>>(label, weight, bias, (bf16_t*)out, N, H, W, h, w, ncls, Cout, relu);
-    else label_conv3x3_kernel<float><<<grid, 256, lds, st>>>(label, weight, bias, (float*)out, N, H, W, h, w, ncls, Cout, relu);
-    S2E_CHECK_LAUNCH("label_conv3x3_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_label_conv3x3", [&](auto t) { using T = decltype(t);
+        label_conv3x3_kernel<T><<<grid, 256, lds, st>>>(label, weight, bias, (T*)out, N, H, W, h, w, ncls, Cout, relu);
+        S2E_CHECK_LAUNCH("label_conv3x3_kernel"); return S2E_OK; });
 }
 
 // Batched form: jobs (DEVICE array; every cout <= 128) share the label batch; block_map (DEVICE int32 triples) from
@@ -210,13 +209,11 @@ extern "C" int s2e_label_conv3x3_batch(int dtype, const uint8_t* label, const s2
                                        int n_blocks, void* out_base, int N, int H, int W, int ncls, void* stream) {
     if (!label || !jobs || !block_map || !out_base || n_blocks <= 0 || N <= 0 || ncls <= 0 || ncls > 7)
         S2E_FAIL(S2E_ERR_ARG, "s2e_label_conv3x3_batch: bad argument");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_label_conv3x3_batch: bad dtype %d", dtype);
     const size_t lds = ((size_t)(9 * ncls + 1) * 132 + (size_t)ncls * 128) * sizeof(float) + (size_t)ncls * 128 * 2;     // table rows at a pitch of 132 floats, uniform rows, the same as stored bf16
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) label_conv3x3_batch_kernel<bf16_t><<<n_blocks, 256, lds, st>>>(label, jobs, block_map, (char*)out_base, N, H, W, ncls);
-    else label_conv3x3_batch_kernel<float><<<n_blocks, 256, lds, st>>>(label, jobs, block_map, (char*)out_base, N, H, W, ncls);
-    S2E_CHECK_LAUNCH("label_conv3x3_batch_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_label_conv3x3_batch", [&](auto t) {
+        label_conv3x3_batch_kernel<decltype(t)><<<n_blocks, 256, lds, st>>>(label, jobs, block_map, (char*)out_base, N, H, W, ncls);
+        S2E_CHECK_LAUNCH("label_conv3x3_batch_kernel"); return S2E_OK; });
 }
 
 // ------------------------------------------------------------------------------------ one-hot (+ image) NHWC
@@ -269,22 +266,16 @@ extern "C" int s2e_onehot_nhwc(int dtype, const uint8_t* label, const void* img,
     if (!label || !out || N <= 0 || h <= 0 || w <= 0 || ncls <= 0 || cpad < ncls + (img ? 1 : 0))
         S2E_FAIL(S2E_ERR_ARG, "s2e_onehot_nhwc: bad argument");
     if (H % h || W % w) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_onehot_nhwc: non-integer downsampling ratio");
-    const long total = (long)N * h * w * cpad;
+    const long px = (long)N * h * w;
     hipStream_t st = (hipStream_t)stream;
-    if (cpad == 8 && ((uintptr_t)out & 15) == 0 && (long)N * h * w < (1L << 31) && (dtype == S2E_BF16 || dtype == S2E_F32)) {
-        const long px = (long)N * h * w;
-        const int gridp = (int)((px + 255) / 256 < 4096 ? (px + 255) / 256 : 4096);
-        if (dtype == S2E_BF16) onehot_nhwc8_kernel<bf16_t><<<gridp, 256, 0, st>>>(label, (const bf16_t*)img, (bf16_t*)out, N, H, W, h, w, ncls);
-        else onehot_nhwc8_kernel<float><<<gridp, 256, 0, st>>>(label, (const float*)img, (float*)out, N, H, W, h, w, ncls);
-        S2E_CHECK_LAUNCH("onehot_nhwc8_kernel");
-        return S2E_OK;
-    }
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (dtype == S2E_BF16) onehot_nhwc_kernel<bf16_t><<<grid, 256, 0, st>>>(label, (const bf16_t*)img, (bf16_t*)out, N, H, W, h, w, ncls, cpad);
-    else if (dtype == S2E_F32) onehot_nhwc_kernel<float><<<grid, 256, 0, st>>>(label, (const float*)img, (float*)out, N, H, W, h, w, ncls, cpad);
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_onehot_nhwc: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("onehot_nhwc_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_onehot_nhwc", [&](auto t) { using T = decltype(t);
+        if (cpad == 8 && ((uintptr_t)out & 15) == 0 && px < (1L << 31)) {
+            onehot_nhwc8_kernel<T><<<s2e_grid1d(px, 4096), 256, 0, st>>>(label, (const T*)img, (T*)out, N, H, W, h, w, ncls);
+            S2E_CHECK_LAUNCH("onehot_nhwc8_kernel");
+            return S2E_OK;
+        }
+        onehot_nhwc_kernel<T><<<s2e_grid1d(px * cpad), 256, 0, st>>>(label, (const T*)img, (T*)out, N, H, W, h, w, ncls, cpad);
+        S2E_CHECK_LAUNCH("onehot_nhwc_kernel"); return S2E_OK; });
 }
 
 // ------------------------------------------------------------------------------------ nearest x2 upsample
@@ -332,22 +323,16 @@ __global__ void upsample2x_bwd_kernel(const T* __restrict__ gy, T* __restrict__ 
 
 static int ups_launch(int dtype, const void* a, void* b, int N, int h, int w, int C, void* stream, bool fwd, const char* name) {
     if (!a || !b || N <= 0 || h <= 0 || w <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "%s: bad argument", name);
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "%s: bad dtype %d", name, dtype);
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    S2E_CHECK_DTYPE(dtype, name);
+    const int vec = s2e_vec_lanes(dtype);
     if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: C=%d not a multiple of %d", name, C, vec);
     const int cg = C / vec;
-    const long nvec = (long)N * h * w * cg * (fwd ? 4 : 1);
-    const int grid = (int)((nvec + 255) / 256 < 8192 ? (nvec + 255) / 256 : 8192);
+    const int grid = s2e_grid1d((long)N * h * w * cg * (fwd ? 4 : 1));
     hipStream_t st = (hipStream_t)stream;
-    if (fwd) {
-        if (dtype == S2E_BF16) upsample2x_fwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)a, (bf16_t*)b, N, h, w, cg);
-        else upsample2x_fwd_kernel<float><<<grid, 256, 0, st>>>((const float*)a, (float*)b, N, h, w, cg);
-    } else {
-        if (dtype == S2E_BF16) upsample2x_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)a, (bf16_t*)b, N, h, w, cg);
-        else upsample2x_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)a, (float*)b, N, h, w, cg);
-    }
-    S2E_CHECK_LAUNCH(name);
-    return S2E_OK;
+    return s2e_with_dtype(dtype, name, [&](auto t) { using T = decltype(t);
+        if (fwd) upsample2x_fwd_kernel<T><<<grid, 256, 0, st>>>((const T*)a, (T*)b, N, h, w, cg);
+        else upsample2x_bwd_kernel<T><<<grid, 256, 0, st>>>((const T*)a, (T*)b, N, h, w, cg);
+        S2E_CHECK_LAUNCH(name); return S2E_OK; });
 }
 extern "C" int s2e_upsample2x_fwd(int dtype, const void* x, void* y, int N, int h, int w, int C, void* stream) {
     return ups_launch(dtype, x, y, N, h, w, C, stream, true, "s2e_upsample2x_fwd");
@@ -478,33 +463,19 @@ __global__ __launch_bounds__(256) void avgpool_bwd_vec_kernel(const T* __restric
 }
 static int pool_launch(int dtype, const void* a, void* b, int N, int H, int W, int C, void* stream, bool fwd, const char* name) {
     if (!a || !b || N <= 0 || H <= 0 || W <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "%s: bad argument", name);
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "%s: bad dtype %d", name, dtype);
     const long total = fwd ? (long)N * ((H + 1) / 2) * ((W + 1) / 2) * C : (long)N * H * W * C;
     hipStream_t st = (hipStream_t)stream;
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
-    if (C % vec == 0 && total / vec < (1L << 31) && (long)N * H * W * C < (1L << 31)) {      // one 16-byte vector per thread
-        const long tv = total / vec;
-        const int gridv = (int)((tv + 255) / 256 < 8192 ? (tv + 255) / 256 : 8192);
-        if (fwd) {
-            if (dtype == S2E_BF16) avgpool_fwd_vec_kernel<bf16_t><<<gridv, 256, 0, st>>>((const bf16_t*)a, (bf16_t*)b, N, H, W, C);
-            else avgpool_fwd_vec_kernel<float><<<gridv, 256, 0, st>>>((const float*)a, (float*)b, N, H, W, C);
+    return s2e_with_dtype(dtype, name, [&](auto t) { using T = decltype(t);
+        constexpr int vec = Vec<T>::N;
+        if (C % vec == 0 && total / vec < (1L << 31) && (long)N * H * W * C < (1L << 31)) {      // one 16-byte vector per thread
+            const int gridv = s2e_grid1d(total / vec);
+            if (fwd) avgpool_fwd_vec_kernel<T><<<gridv, 256, 0, st>>>((const T*)a, (T*)b, N, H, W, C);
+            else avgpool_bwd_vec_kernel<T><<<gridv, 256, 0, st>>>((const T*)a, (T*)b, N, H, W, C);
         } else {
-            if (dtype == S2E_BF16) avgpool_bwd_vec_kernel<bf16_t><<<gridv, 256, 0, st>>>((const bf16_t*)a, (bf16_t*)b, N, H, W, C);
-            else avgpool_bwd_vec_kernel<float><<<gridv, 256, 0, st>>>((const float*)a, (float*)b, N, H, W, C);
+            if (fwd) avgpool_fwd_kernel<T><<<s2e_grid1d(total), 256, 0, st>>>((const T*)a, (T*)b, N, H, W, C);
+            else avgpool_bwd_kernel<T><<<s2e_grid1d(total), 256, 0, st>>>((const T*)a, (T*)b, N, H, W, C);
         }
-        S2E_CHECK_LAUNCH(name);
-        return S2E_OK;
-    }
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    if (fwd) {
-        if (dtype == S2E_BF16) avgpool_fwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)a, (bf16_t*)b, N, H, W, C);
-        else avgpool_fwd_kernel<float><<<grid, 256, 0, st>>>((const float*)a, (float*)b, N, H, W, C);
-    } else {
-        if (dtype == S2E_BF16) avgpool_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)a, (bf16_t*)b, N, H, W, C);
-        else avgpool_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)a, (float*)b, N, H, W, C);
-    }
-    S2E_CHECK_LAUNCH(name);
-    return S2E_OK;
+        S2E_CHECK_LAUNCH(name); return S2E_OK; });
 }
 extern "C" int s2e_avgpool3x3s2_fwd(int dtype, const void* x, void* y, int N, int H, int W, int C, void* stream) {
     return pool_launch(dtype, x, y, N, H, W, C, stream, true, "s2e_avgpool3x3s2_fwd");
@@ -523,13 +494,9 @@ __global__ void tanh_bwd_kernel(const T* __restrict__ gy, const T* __restrict__ 
 }
 extern "C" int s2e_tanh_bwd(int dtype, const void* gy, const void* y, void* gx, long n, void* stream) {
     if (!gy || !y || !gx || n <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_tanh_bwd: bad argument");
-    const int grid = (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) tanh_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)gy, (const bf16_t*)y, (bf16_t*)gx, n);
-    else if (dtype == S2E_F32) tanh_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)gy, (const float*)y, (float*)gx, n);
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_tanh_bwd: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("tanh_bwd_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_tanh_bwd", [&](auto t) { using T = decltype(t);
+        tanh_bwd_kernel<T><<<s2e_grid1d(n), 256, 0, (hipStream_t)stream>>>((const T*)gy, (const T*)y, (T*)gx, n);
+        S2E_CHECK_LAUNCH("tanh_bwd_kernel"); return S2E_OK; });
 }
 
 // ------------------------------------------------------------------------------------ LeakyReLU backward
@@ -551,14 +518,9 @@ __global__ void lrelu_bwd_kernel(const T* __restrict__ gy, const T* __restrict__
 extern "C" int s2e_lrelu_bwd(int dtype, const void* gy, const void* y, void* gx, long n, void* stream) {
     if (!gy || !y || !gx || n <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_lrelu_bwd: bad argument");
     if (((uintptr_t)gy | (uintptr_t)y | (uintptr_t)gx) & 15) S2E_FAIL(S2E_ERR_ARG, "s2e_lrelu_bwd: pointers must be 16-byte aligned");
-    const long nv = n / 4 + 1;
-    const int grid = (int)((nv + 255) / 256 < 8192 ? (nv + 255) / 256 : 8192);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) lrelu_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)gy, (const bf16_t*)y, (bf16_t*)gx, n);
-    else if (dtype == S2E_F32) lrelu_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)gy, (const float*)y, (float*)gx, n);
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_lrelu_bwd: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("lrelu_bwd_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_lrelu_bwd", [&](auto t) { using T = decltype(t);
+        lrelu_bwd_kernel<T><<<s2e_grid1d(n / 4 + 1), 256, 0, (hipStream_t)stream>>>((const T*)gy, (const T*)y, (T*)gx, n);
+        S2E_CHECK_LAUNCH("lrelu_bwd_kernel"); return S2E_OK; });
 }
 
 // ------------------------------------------------------------------------------------ bilinear resize (encoder front end)
@@ -605,20 +567,15 @@ __global__ __launch_bounds__(256) void bilinear_bwd_kernel(const T* __restrict__
 
 static int bilinear_launch(int dtype, const void* a, void* b, int N, int H, int W, int Ho, int Wo, void* stream, bool fwd, const char* name) {
     if (!a || !b || N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0) S2E_FAIL(S2E_ERR_ARG, "%s: bad argument", name);
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "%s: bad dtype %d", name, dtype);
+    S2E_CHECK_DTYPE(dtype, name);
     if (Ho > 65535 || N > 65535) S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: grid too large", name);
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(ceil_div(Wo, 256), Ho, N);
     const float sy = (float)H / (float)Ho, sx = (float)W / (float)Wo;
-    if (fwd) {
-        if (dtype == S2E_BF16) bilinear_fwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const float*)a, (bf16_t*)b, H, W, Ho, Wo, sy, sx);
-        else bilinear_fwd_kernel<float><<<grid, 256, 0, st>>>((const float*)a, (float*)b, H, W, Ho, Wo, sy, sx);
-    } else {
-        if (dtype == S2E_BF16) bilinear_bwd_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)a, (float*)b, H, W, Ho, Wo, sy, sx);
-        else bilinear_bwd_kernel<float><<<grid, 256, 0, st>>>((const float*)a, (float*)b, H, W, Ho, Wo, sy, sx);
-    }
-    S2E_CHECK_LAUNCH(name);
-    return S2E_OK;
+    return s2e_with_dtype(dtype, name, [&](auto t) { using T = decltype(t);
+        if (fwd) bilinear_fwd_kernel<T><<<grid, 256, 0, st>>>((const float*)a, (T*)b, H, W, Ho, Wo, sy, sx);
+        else bilinear_bwd_kernel<T><<<grid, 256, 0, st>>>((const T*)a, (float*)b, H, W, Ho, Wo, sy, sx);
+        S2E_CHECK_LAUNCH(name); return S2E_OK; });
 }
 extern "C" int s2e_bilinear_resize_fwd(int dtype, const float* x, void* y, int N, int H, int W, int Ho, int Wo, void* stream) {
     return bilinear_launch(dtype, x, y, N, H, W, Ho, Wo, stream, true, "s2e_bilinear_resize_fwd");
@@ -798,15 +755,12 @@ extern "C" int s2e_spade_class_table(int dtype, const float* w_sh, const float* 
                                      float* table, int ncls, int nh, int C, void* stream) {
     if (!w_sh || !b_sh || !w_packed || !table || ncls <= 0 || ncls > 8 || nh <= 0 || nh > 128 || C <= 0)
         S2E_FAIL(S2E_ERR_ARG, "s2e_spade_class_table: bad argument (nh <= 128)");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_spade_class_table: bad dtype %d", dtype);
-    const int bk = dtype == S2E_BF16 ? 64 : 32;
-    const int kpad = ceil_div(9 * nh, bk) * bk;
+    const int kpad = s2e_conv_k_pad(dtype, 9 * nh);
     const dim3 grid(ceil_div(2 * C, 4), ncls);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) spade_class_table_kernel<bf16_t><<<grid, 256, 0, st>>>(w_sh, b_sh, (const bf16_t*)w_packed, bias, table, ncls, nh, 2 * C, kpad);
-    else spade_class_table_kernel<float><<<grid, 256, 0, st>>>(w_sh, b_sh, (const float*)w_packed, bias, table, ncls, nh, 2 * C, kpad);
-    S2E_CHECK_LAUNCH("spade_class_table_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_spade_class_table", [&](auto t) { using T = decltype(t);
+        spade_class_table_kernel<T><<<grid, 256, 0, st>>>(w_sh, b_sh, (const T*)w_packed, bias, table, ncls, nh, 2 * C, kpad);
+        S2E_CHECK_LAUNCH("spade_class_table_kernel"); return S2E_OK; });
 }
 
 extern "C" long s2e_class_table_block_map(const s2e_class_table_job* jobs_host, int n_jobs, int* block_map_host) {
@@ -824,14 +778,11 @@ extern "C" int s2e_spade_class_table_batch(int dtype, const s2e_class_table_job*
                                            void* table_base, int ncls, void* stream) {
     if (!jobs || !block_map || !table_base || n_blocks <= 0 || ncls <= 0 || ncls > 8)
         S2E_FAIL(S2E_ERR_ARG, "s2e_spade_class_table_batch: bad argument");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_spade_class_table_batch: bad dtype %d", dtype);
-    const int bk = dtype == S2E_BF16 ? 64 : 32;
     const dim3 grid(n_blocks, ncls);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) spade_class_table_batch_kernel<bf16_t><<<grid, 256, 0, st>>>(jobs, block_map, (char*)table_base, ncls, bk);
-    else spade_class_table_batch_kernel<float><<<grid, 256, 0, st>>>(jobs, block_map, (char*)table_base, ncls, bk);
-    S2E_CHECK_LAUNCH("spade_class_table_batch_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_spade_class_table_batch", [&](auto t) {
+        spade_class_table_batch_kernel<decltype(t)><<<grid, 256, 0, st>>>(jobs, block_map, (char*)table_base, ncls, s2e_k_tile(dtype));
+        S2E_CHECK_LAUNCH("spade_class_table_batch_kernel"); return S2E_OK; });
 }
 
 // SPADE+Style modulation of the label-uniform rectangles: out = [lrelu] 0.5*((x-mean)*rstd*(1+gamma)+beta + x*(1+s0)+s1) with
@@ -936,8 +887,8 @@ extern "C" int s2e_spade_modulate_uniform(int dtype, const void* x, const float*
     if (!x || !stats || !style || !table || !cls || !uni_list || !counts || !out || N <= 0 || H < 5 || W < 5 || C <= 0 || tw <= 0 || th <= 0)
         S2E_FAIL(S2E_ERR_ARG, "s2e_spade_modulate_uniform: bad argument");
     if (x_up && ((H | W) & 1)) S2E_FAIL(S2E_ERR_ARG, "s2e_spade_modulate_uniform: x_up needs even H, W");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_spade_modulate_uniform: bad dtype %d", dtype);
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    S2E_CHECK_DTYPE(dtype, "s2e_spade_modulate_uniform");
+    const int vec = s2e_vec_lanes(dtype);
     if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_spade_modulate_uniform: C=%d not a multiple of %d", C, vec);
     if ((((uintptr_t)stats | (uintptr_t)style | (uintptr_t)table) & 15) || (style_ld & 3) || (C & 3))
         S2E_FAIL(S2E_ERR_ARG, "s2e_spade_modulate_uniform: stats, style and table must be 16-byte aligned (style_ld, C multiples of 4)");
@@ -946,12 +897,8 @@ extern "C" int s2e_spade_modulate_uniform(int dtype, const void* x, const float*
     const int grid = (int)(rects < 2048 ? rects : 2048);
     const int sld = style_ld > 0 ? style_ld : 2 * C;
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16)
-        spade_modulate_uniform_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)x, stats, style, sld, table, cls, uni_list, counts,
-                                                                  (bf16_t*)out, (bf16_t*)gamma_out, H, W, C, tw, th, tiles_x, tiles_y, lrelu, x_up);
-    else
-        spade_modulate_uniform_kernel<float><<<grid, 256, 0, st>>>((const float*)x, stats, style, sld, table, cls, uni_list, counts,
-                                                                 (float*)out, (float*)gamma_out, H, W, C, tw, th, tiles_x, tiles_y, lrelu, x_up);
-    S2E_CHECK_LAUNCH("spade_modulate_uniform_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_spade_modulate_uniform", [&](auto t) { using T = decltype(t);
+        spade_modulate_uniform_kernel<T><<<grid, 256, 0, st>>>((const T*)x, stats, style, sld, table, cls, uni_list, counts,
+                                                             (T*)out, (T*)gamma_out, H, W, C, tw, th, tiles_x, tiles_y, lrelu, x_up);
+        S2E_CHECK_LAUNCH("spade_modulate_uniform_kernel"); return S2E_OK; });
 }

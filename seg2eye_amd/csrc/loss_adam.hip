@@ -120,35 +120,30 @@ static int loss_dispatch(bool grad, int mode, const T* a, const T* b, long n, fl
     // one 16-byte vector per thread and trip.  The reduction ends with ONE float atomic per block on a single address, and
     // same-address atomics serialise at ~12 ns each: 1024 blocks cost the feature-matching sums more (13 us) than their 2 ... 17 MB
     // of reads -- at most 256 blocks
-    const long work = n / Vec<T>::N + 1;
-    const int cap = grad ? 2048 : 256;
-    const int grid = (int)((work + 255) / 256 < cap ? (work + 255) / 256 : cap);
-#define S2E_L(MM) do { if (grad) loss_grad_kernel<T, MM><<<grid, 256, 0, st>>>(a, b, n, scale, gscale, (T*)out, accumulate); \
-                       else loss_reduce_kernel<T, MM><<<grid, 256, 0, st>>>(a, b, n, scale, (float*)out); } while (0)
+    const int grid = s2e_grid1d(n / Vec<T>::N + 1, grad ? 2048 : 256);
+    auto go = [&](auto MM) { if (grad) loss_grad_kernel<T, MM><<<grid, 256, 0, st>>>(a, b, n, scale, gscale, (T*)out, accumulate);
+                             else loss_reduce_kernel<T, MM><<<grid, 256, 0, st>>>(a, b, n, scale, (float*)out); };
     switch (mode) {
-        case S2E_LOSS_NEG_MEAN: S2E_L(S2E_LOSS_NEG_MEAN); break;
-        case S2E_LOSS_HINGE_REAL: S2E_L(S2E_LOSS_HINGE_REAL); break;
-        case S2E_LOSS_HINGE_FAKE: S2E_L(S2E_LOSS_HINGE_FAKE); break;
-        case S2E_LOSS_L1: S2E_L(S2E_LOSS_L1); break;
+        case S2E_LOSS_NEG_MEAN: go(int_c<S2E_LOSS_NEG_MEAN>{}); break;
+        case S2E_LOSS_HINGE_REAL: go(int_c<S2E_LOSS_HINGE_REAL>{}); break;
+        case S2E_LOSS_HINGE_FAKE: go(int_c<S2E_LOSS_HINGE_FAKE>{}); break;
+        case S2E_LOSS_L1: go(int_c<S2E_LOSS_L1>{}); break;
         default: S2E_FAIL(S2E_ERR_ARG, "loss: bad mode %d", mode);
     }
-#undef S2E_L
     S2E_CHECK_LAUNCH("loss kernel");
     return S2E_OK;
 }
 
 extern "C" int s2e_loss_reduce(int dtype, int mode, const void* a, const void* b, long n, float scale, float* out, void* stream) {
     if (!a || !out || n <= 0 || (mode == S2E_LOSS_L1 && !b)) S2E_FAIL(S2E_ERR_ARG, "s2e_loss_reduce: bad argument");
-    if (dtype == S2E_BF16) return loss_dispatch<bf16_t>(false, mode, (const bf16_t*)a, (const bf16_t*)b, n, scale, nullptr, out, 0, (hipStream_t)stream);
-    if (dtype == S2E_F32) return loss_dispatch<float>(false, mode, (const float*)a, (const float*)b, n, scale, nullptr, out, 0, (hipStream_t)stream);
-    S2E_FAIL(S2E_ERR_ARG, "s2e_loss_reduce: bad dtype %d", dtype);
+    return s2e_with_dtype(dtype, "s2e_loss_reduce", [&](auto t) { using T = decltype(t);
+        return loss_dispatch<T>(false, mode, (const T*)a, (const T*)b, n, scale, nullptr, out, 0, (hipStream_t)stream); });
 }
 extern "C" int s2e_loss_grad(int dtype, int mode, const void* a, const void* b, long n, float scale, const float* gscale,
                              void* da, int accumulate, void* stream) {
     if (!a || !da || n <= 0 || (mode == S2E_LOSS_L1 && !b)) S2E_FAIL(S2E_ERR_ARG, "s2e_loss_grad: bad argument");
-    if (dtype == S2E_BF16) return loss_dispatch<bf16_t>(true, mode, (const bf16_t*)a, (const bf16_t*)b, n, scale, gscale, da, accumulate, (hipStream_t)stream);
-    if (dtype == S2E_F32) return loss_dispatch<float>(true, mode, (const float*)a, (const float*)b, n, scale, gscale, da, accumulate, (hipStream_t)stream);
-    S2E_FAIL(S2E_ERR_ARG, "s2e_loss_grad: bad dtype %d", dtype);
+    return s2e_with_dtype(dtype, "s2e_loss_grad", [&](auto t) { using T = decltype(t);
+        return loss_dispatch<T>(true, mode, (const T*)a, (const T*)b, n, scale, gscale, da, accumulate, (hipStream_t)stream); });
 }
 
 // ------------------------------------------------------------------------------------ Adam over a flat arena
@@ -210,8 +205,7 @@ __global__ void adam_tick_kernel(float* hyper) { hyper[4] += 1.f; }
 extern "C" int s2e_adam_flat(float* p, const float* g, float* m, float* v, long n, float* hyper, void* stream) {
     if (!p || !g || !m || !v || !hyper || n <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_adam_flat: bad argument");
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) S2E_FAIL(S2E_ERR_ARG, "s2e_adam_flat: arenas must be 16-byte aligned");
-    const long nv = n / 4 + 1;
-    const int grid = (int)((nv + 255) / 256 < 4096 ? (nv + 255) / 256 : 4096);
+    const int grid = s2e_grid1d(n / 4 + 1, 4096);
     adam_flat_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p, g, m, v, n, hyper);
     S2E_CHECK_LAUNCH("adam_flat_kernel");
     adam_tick_kernel<<<1, 1, 0, (hipStream_t)stream>>>(hyper);      // after every block has read hyper[4]
@@ -293,8 +287,7 @@ extern "C" int s2e_adam_flat_ema(float* p, const float* g, float* m, float* v, f
     if (!p || !g || !m || !v || !ema || !hyper || !ema_hyper || n <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_adam_flat_ema: bad argument");
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15)
         S2E_FAIL(S2E_ERR_ARG, "s2e_adam_flat_ema: arenas must be 16-byte aligned");
-    const long nv = n / 4 + 1;
-    const int grid = (int)((nv + 255) / 256 < 4096 ? (nv + 255) / 256 : 4096);      // (s2e_adam_flat's grid)
+    const int grid = s2e_grid1d(n / 4 + 1, 4096);      // (s2e_adam_flat's grid)
     adam_flat_ema_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(p, g, m, v, ema, n, hyper, ema_hyper);
     S2E_CHECK_LAUNCH("adam_flat_ema_kernel");
     adam_tick_kernel<<<1, 1, 0, (hipStream_t)stream>>>(hyper);      // after every block has read hyper[4]
@@ -331,13 +324,9 @@ __global__ __launch_bounds__(256) void shard_sum_kernel(const T* __restrict__ re
 
 extern "C" int s2e_shard_sum(int dtype, const void* recv, void* out, int world, long shard, void* stream) {
     if (!recv || !out || world <= 0 || shard <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_shard_sum: bad argument");
-    if ((((uintptr_t)recv | (uintptr_t)out) & 15) || (shard * (dtype == S2E_BF16 ? 2 : 4)) % 16 != 0)
+    if ((((uintptr_t)recv | (uintptr_t)out) & 15) || shard % s2e_vec_lanes(dtype) != 0)
         S2E_FAIL(S2E_ERR_ARG, "s2e_shard_sum: buffers and the shard size must be 16-byte multiples");
-    const long nv = shard / (dtype == S2E_BF16 ? 8 : 4) + 1;
-    const int grid = (int)((nv + 255) / 256 < 2048 ? (nv + 255) / 256 : 2048);
-    if (dtype == S2E_BF16) shard_sum_kernel<bf16_t><<<grid, 256, 0, (hipStream_t)stream>>>((const bf16_t*)recv, (bf16_t*)out, world, shard);
-    else if (dtype == S2E_F32) shard_sum_kernel<float><<<grid, 256, 0, (hipStream_t)stream>>>((const float*)recv, (float*)out, world, shard);
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_shard_sum: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("shard_sum_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_shard_sum", [&](auto t) { using T = decltype(t);
+        shard_sum_kernel<T><<<s2e_grid1d(shard / Vec<T>::N + 1, 2048), 256, 0, (hipStream_t)stream>>>((const T*)recv, (T*)out, world, shard);
+        S2E_CHECK_LAUNCH("shard_sum_kernel"); return S2E_OK; });
 }

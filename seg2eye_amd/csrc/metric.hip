@@ -95,11 +95,9 @@ extern "C" int s2e_openeds_error(int dtype, const void* fake, const void* target
     if (!fake || !target || !err || N <= 0 || H <= 0 || W <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_openeds_error: bad argument");
     hipStream_t st = (hipStream_t)stream;
     const long HW = (long)H * W;
-    if (dtype == S2E_BF16) openeds_error_kernel<bf16_t><<<N, 1024, 0, st>>>((const bf16_t*)fake, (const bf16_t*)target, HW, err);
-    else if (dtype == S2E_F32) openeds_error_kernel<float><<<N, 1024, 0, st>>>((const float*)fake, (const float*)target, HW, err);
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_openeds_error: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("openeds_error_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_openeds_error", [&](auto t) { using T = decltype(t);
+        openeds_error_kernel<T><<<N, 1024, 0, st>>>((const T*)fake, (const T*)target, HW, err);
+        S2E_CHECK_LAUNCH("openeds_error_kernel"); return S2E_OK; });
 }
 
 extern "C" int s2e_openeds_error_u8(const uint8_t* produced, const uint8_t* target, int N, int H, int W, float* err, void* stream) {
@@ -116,9 +114,7 @@ extern "C" int s2e_resize_to255(int dtype, const void* x, int N, int H, int W, u
     const dim3 grid(ceil_div(Wo, 256), Ho, N);
     // cv2: inv_scale = dst / (double)src; scale = 1. / inv_scale
     const double sy = 1.0 / ((double)Ho / (double)H), sx = 1.0 / ((double)Wo / (double)W);
-    if (dtype == S2E_BF16) resize_to255_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)x, out, H, W, Ho, Wo, sy, sx);
-    else if (dtype == S2E_F32) resize_to255_kernel<float><<<grid, 256, 0, st>>>((const float*)x, out, H, W, Ho, Wo, sy, sx);
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_resize_to255: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("resize_to255_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_resize_to255", [&](auto t) { using T = decltype(t);
+        resize_to255_kernel<T><<<grid, 256, 0, st>>>((const T*)x, out, H, W, Ho, Wo, sy, sx);
+        S2E_CHECK_LAUNCH("resize_to255_kernel"); return S2E_OK; });
 }

@@ -219,12 +219,17 @@ __global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__
 
 // channel groups per block of the small-map kernels: 8, or 4 when 8 would leave most of the CUs without a block
 static int small_groups(int N, int C, int vec) { return (long)N * ceil_div(C, 8 * vec) < 192 ? 4 : 8; }
-#define S2E_SMALL_LAUNCH(KERNEL, TT, ...) do { \
-    if (small_groups(N, C, vec) == 4) { const dim3 sg(ceil_div(C, 4 * vec), N); KERNEL<TT, 4><<<sg, 256, 0, st>>>(__VA_ARGS__); } \
-    else { const dim3 sg(ceil_div(C, 8 * vec), N); KERNEL<TT, 8><<<sg, 256, 0, st>>>(__VA_ARGS__); } } while (0)
-#define S2E_SMALL_LAUNCH2(KERNEL, TT, AP, ...) do { \
-    if (small_groups(N, C, vec) == 4) { const dim3 sg(ceil_div(C, 4 * vec), N); KERNEL<TT, AP, 4><<<sg, 256, 0, st>>>(__VA_ARGS__); } \
-    else { const dim3 sg(ceil_div(C, 8 * vec), N); KERNEL<TT, AP, 8><<<sg, 256, 0, st>>>(__VA_ARGS__); } } while (0)
+// f(G as an integral_constant, the grid) for a small-map kernel of element type T
+template <typename T, typename F> static void small_launch(int N, int C, F&& f) {
+    constexpr int vec = Vec<T>::N;
+    if (small_groups(N, C, vec) == 4) f(int_c<4>{}, dim3(ceil_div(C, 4 * vec), N));
+    else f(int_c<8>{}, dim3(ceil_div(C, 8 * vec), N));
+}
+// f(mode as an integral_constant): the element-wise kernels are stamped for SPADE_STYLE and PLAIN_IN
+template <typename F> static void with_norm_mode(int mode, F&& f) {
+    if (mode == S2E_NORM_SPADE_STYLE) f(int_c<S2E_NORM_SPADE_STYLE>{});
+    else f(int_c<S2E_NORM_PLAIN_IN>{});
+}
 
 template <typename T>
 __global__ __launch_bounds__(256) void in_stats_partial_kernel(const T* __restrict__ x, float* __restrict__ part,
@@ -377,7 +382,7 @@ extern "C" int s2e_in_stats_from_partials(const float* part, int N, int P, int C
 }
 
 extern "C" size_t s2e_in_stats_workspace_bytes(int dtype, int N, int HW, int C) {
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     if (N <= 0 || HW <= 0 || C <= 0 || C % vec) return 0;
     const RowGeom g = row_geom(C, vec);
     const int P = ceil_div(HW, g.rpp * slab_iters_for(HW, g.rpp, N, g.zblocks));
@@ -385,7 +390,7 @@ extern "C" size_t s2e_in_stats_workspace_bytes(int dtype, int N, int HW, int C) 
 }
 
 extern "C" int s2e_in_stats_counters(int dtype, int N, int HW, int C) {
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     if (N <= 0 || HW <= 0 || C <= 0 || C % vec || HW <= in_small_hw()) return 0;
     return N * row_geom(C, vec).zblocks;
 }
@@ -393,24 +398,22 @@ extern "C" int s2e_in_stats_counters(int dtype, int N, int HW, int C) {
 extern "C" int s2e_in_stats(int dtype, const void* x, int N, int HW, int C, float eps, double* ws, float* stats, unsigned* counters,
                             void* stream) {
     if (!x || !ws || !stats || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_in_stats: bad argument");
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_in_stats: bad dtype %d", dtype);
+    S2E_CHECK_DTYPE(dtype, "s2e_in_stats");
+    const int vec = s2e_vec_lanes(dtype);
     if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_in_stats: C=%d not a multiple of %d", C, vec);
     hipStream_t st = (hipStream_t)stream;
-    if (HW <= in_small_hw()) {                               // small map: statistics in one launch
-        if (dtype == S2E_BF16) S2E_SMALL_LAUNCH2(in_small_kernel, bf16_t, 0, (const bf16_t*)x, nullptr, ws, stats, HW, C, eps, 0);
-        else S2E_SMALL_LAUNCH2(in_small_kernel, float, 0, (const float*)x, nullptr, ws, stats, HW, C, eps, 0);
-        S2E_CHECK_LAUNCH("in_small_kernel");
-        return S2E_OK;
-    }
+    if (HW <= in_small_hw())                                 // small map: statistics in one launch
+        return s2e_with_dtype(dtype, "s2e_in_stats", [&](auto t) { using T = decltype(t);
+            small_launch<T>(N, C, [&](auto G, dim3 sg) { in_small_kernel<T, 0, G><<<sg, 256, 0, st>>>((const T*)x, nullptr, ws, stats, HW, C, eps, 0); });
+            S2E_CHECK_LAUNCH("in_small_kernel"); return S2E_OK; });
     const RowGeom g = row_geom(C, vec);
     const int iters = slab_iters_for(HW, g.rpp, N, g.zblocks);
     const int P = ceil_div(HW, g.rpp * iters);
     dim3 grid(P, N, g.zblocks);
     float* part = (float*)(ws + (size_t)N * C * 2);          // [N][P][C][2] floats behind the N*C*2 doubles
-    if (dtype == S2E_BF16) in_stats_partial_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)x, part, HW, C, g.cg, g.cgb, g.rpp, iters, counters, ws, stats, eps);
-    else in_stats_partial_kernel<float><<<grid, 256, 0, st>>>((const float*)x, part, HW, C, g.cg, g.cgb, g.rpp, iters, counters, ws, stats, eps);
-    S2E_CHECK_LAUNCH("in_stats_partial_kernel");
+    if (const int rc = s2e_with_dtype(dtype, "s2e_in_stats", [&](auto t) { using T = decltype(t);
+            in_stats_partial_kernel<T><<<grid, 256, 0, st>>>((const T*)x, part, HW, C, g.cg, g.cgb, g.rpp, iters, counters, ws, stats, eps);
+            S2E_CHECK_LAUNCH("in_stats_partial_kernel"); return S2E_OK; })) return rc;
     if (counters) return S2E_OK;
     in_stats_finalize_kernel<<<ceil_div((long)N * C, 256), 256, 0, st>>>(part, ws, stats, N * C, C, P, HW, eps);
     S2E_CHECK_LAUNCH("in_stats_finalize_kernel");
@@ -480,23 +483,19 @@ __global__ void colsum_scalar_kernel(const T* __restrict__ gsrc, float* __restri
 
 extern "C" int s2e_colsum(int dtype, const void* g, long M, int C, float* out, void* stream) {
     if (!g || !out || M <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_colsum: bad argument");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_colsum: bad dtype %d", dtype);
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
     hipStream_t st = (hipStream_t)stream;
-    if (C % vec) {
-        dim3 grid((unsigned)(M / 1024 + 1 < 256 ? M / 1024 + 1 : 256), C);
-        if (dtype == S2E_BF16) colsum_scalar_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)g, out, M, C);
-        else colsum_scalar_kernel<float><<<grid, 256, 0, st>>>((const float*)g, out, M, C);
-        S2E_CHECK_LAUNCH("colsum_scalar_kernel");
-        return S2E_OK;
-    }
-    const RowGeom rg = row_geom(C, vec);
-    const int rows_per_block = rg.rpp * 64;      // long slabs: same-address atomics serialise, keep them few
-    dim3 grid(ceil_div(M, rows_per_block), 1, rg.zblocks);
-    if (dtype == S2E_BF16) colsum_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)g, out, M, C, rg.cg, rg.cgb, rg.rpp, rows_per_block);
-    else colsum_kernel<float><<<grid, 256, 0, st>>>((const float*)g, out, M, C, rg.cg, rg.cgb, rg.rpp, rows_per_block);
-    S2E_CHECK_LAUNCH("colsum_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_colsum", [&](auto t) { using T = decltype(t);
+        if (C % Vec<T>::N) {
+            dim3 grid((unsigned)(M / 1024 + 1 < 256 ? M / 1024 + 1 : 256), C);
+            colsum_scalar_kernel<T><<<grid, 256, 0, st>>>((const T*)g, out, M, C);
+            S2E_CHECK_LAUNCH("colsum_scalar_kernel");
+            return S2E_OK;
+        }
+        const RowGeom rg = row_geom(C, Vec<T>::N);
+        const int rows_per_block = rg.rpp * 64;      // long slabs: same-address atomics serialise, keep them few
+        dim3 grid(ceil_div(M, rows_per_block), 1, rg.zblocks);
+        colsum_kernel<T><<<grid, 256, 0, st>>>((const T*)g, out, M, C, rg.cg, rg.cgb, rg.rpp, rows_per_block);
+        S2E_CHECK_LAUNCH("colsum_kernel"); return S2E_OK; });
 }
 
 // ------------------------------------------------------------------------------------ modulation forward
@@ -558,8 +557,8 @@ extern "C" int s2e_modulate_fwd(int dtype, int mode, const void* x, const void* 
                                 void* out, int N, int HW, int C, int lrelu, int style_ld, void* stream) {
     if (!x || !stats || !out || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_fwd: bad argument");
     if (mode == S2E_NORM_SPADE_STYLE && (!gb || !style)) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_fwd: SPADE_STYLE needs gb and style");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_fwd: bad dtype %d", dtype);
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    S2E_CHECK_DTYPE(dtype, "s2e_modulate_fwd");
+    const int vec = s2e_vec_lanes(dtype);
     if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_modulate_fwd: C=%d not a multiple of %d", C, vec);
     const int cg = C / vec;
     const int sld = style_ld > 0 ? style_ld : 2 * C;
@@ -569,15 +568,12 @@ extern "C" int s2e_modulate_fwd(int dtype, int mode, const void* x, const void* 
     const int gx_cap = 8192 / N > 1 ? 8192 / N : 1;
     if (gx > gx_cap) gx = gx_cap;
     const dim3 grid(gx, N);
-    int cg_shift = -1;
-    for (int b = 0; b < 31; ++b) if ((1 << b) == cg) cg_shift = b;
+    const int cg_shift = s2e_pow2_shift(cg);
     hipStream_t st = (hipStream_t)stream;
-#define S2E_LAUNCH_MOD(TT, MM) modulate_fwd_kernel<TT, MM><<<grid, 256, 0, st>>>((const TT*)x, (const TT*)gb, stats, style, (TT*)out, HW, C, cg, cg_shift, lrelu, sld)
-    if (dtype == S2E_BF16) { if (mode == S2E_NORM_SPADE_STYLE) S2E_LAUNCH_MOD(bf16_t, S2E_NORM_SPADE_STYLE); else S2E_LAUNCH_MOD(bf16_t, S2E_NORM_PLAIN_IN); }
-    else { if (mode == S2E_NORM_SPADE_STYLE) S2E_LAUNCH_MOD(float, S2E_NORM_SPADE_STYLE); else S2E_LAUNCH_MOD(float, S2E_NORM_PLAIN_IN); }
-#undef S2E_LAUNCH_MOD
-    S2E_CHECK_LAUNCH("modulate_fwd_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_modulate_fwd", [&](auto t) { using T = decltype(t);
+        with_norm_mode(mode, [&](auto MM) {
+            modulate_fwd_kernel<T, MM><<<grid, 256, 0, st>>>((const T*)x, (const T*)gb, stats, style, (T*)out, HW, C, cg, cg_shift, lrelu, sld); });
+        S2E_CHECK_LAUNCH("modulate_fwd_kernel"); return S2E_OK; });
 }
 
 // ------------------------------------------------------------------------------------ modulation backward
@@ -1054,22 +1050,20 @@ static int modulate_bwd_impl(int dtype, int mode, const void* g, const void* x, 
     if (!g || !x || !stats || !dx || !ws || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: bad argument");
     if (mode == S2E_NORM_SPADE_STYLE && (!gb || !style || !dgb || !dstyle))
         S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: SPADE_STYLE needs gb, style, dgb, dstyle");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: bad dtype %d", dtype);
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    S2E_CHECK_DTYPE(dtype, "s2e_modulate_bwd");
+    const int vec = s2e_vec_lanes(dtype);
     if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_modulate_bwd: C=%d not a multiple of %d", C, vec);
     hipStream_t st = (hipStream_t)stream;
     const float inv_xw = xw ? 1.f / (float)xw : 0.f;
     if (xw && (!fout || batch || stage != 0 || HW % xw || ((HW / xw) | xw) & 1))
         S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: x at half resolution needs the gamma-only form, per-sample statistics and an even H x W map");
     if (quad && (!xw || mode != S2E_NORM_SPADE_STYLE)) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: dx_quad goes with x_up_w (SPADE_STYLE mode)");
-    if (fout && mode == S2E_NORM_SPADE_STYLE && !batch && stage == 0 && HW <= in_small_hw()) {     // small map: one launch
-        if (dtype == S2E_BF16) S2E_SMALL_LAUNCH(spade_small_bwd_kernel, bf16_t, (const bf16_t*)g, (const bf16_t*)x, (const bf16_t*)gb, (const bf16_t*)fout,
-                                                 stats, style, (bf16_t*)dx, (const bf16_t*)dx_add, (bf16_t*)dgb, dstyle, HW, C, lrelu, sld, acc, xw, inv_xw, quad);
-        else S2E_SMALL_LAUNCH(spade_small_bwd_kernel, float, (const float*)g, (const float*)x, (const float*)gb, (const float*)fout,
-                              stats, style, (float*)dx, (const float*)dx_add, (float*)dgb, dstyle, HW, C, lrelu, sld, acc, xw, inv_xw, quad);
-        S2E_CHECK_LAUNCH("spade_small_bwd_kernel");
-        return S2E_OK;
-    }
+    if (fout && mode == S2E_NORM_SPADE_STYLE && !batch && stage == 0 && HW <= in_small_hw())       // small map: one launch
+        return s2e_with_dtype(dtype, "s2e_modulate_bwd", [&](auto t) { using T = decltype(t);
+            small_launch<T>(N, C, [&](auto G, dim3 sg) {
+                spade_small_bwd_kernel<T, G><<<sg, 256, 0, st>>>((const T*)g, (const T*)x, (const T*)gb, (const T*)fout, stats, style, (T*)dx, (const T*)dx_add,
+                                                                  (T*)dgb, dstyle, HW, C, lrelu, sld, acc, xw, inv_xw, quad); });
+            S2E_CHECK_LAUNCH("spade_small_bwd_kernel"); return S2E_OK; });
     const RowGeom rg = row_geom(C, vec);
     const int iters = slab_iters_for(HW, rg.rpp, N, rg.zblocks);
     dim3 grid1(ceil_div(HW, rg.rpp * iters), N, rg.zblocks);
@@ -1079,8 +1073,7 @@ static int modulate_bwd_impl(int dtype, int mode, const void* g, const void* x, 
     const int gx_cap = 8192 / N > 1 ? 8192 / N : 1;
     if (gx > gx_cap) gx = gx_cap;
     dim3 grid2(gx, N);
-    int cg_shift = -1;
-    for (int b = 0; b < 31; ++b) if ((1 << b) == rg.cg) cg_shift = b;
+    const int cg_shift = s2e_pow2_shift(rg.cg);
     const int gridc = ceil_div((long)N * C, 256);
     f32x4_t* coef = (f32x4_t*)(ws + (size_t)N * C * 4);
     const int P = (int)grid1.x;                            // partial-sum slots per sample
@@ -1088,18 +1081,20 @@ static int modulate_bwd_impl(int dtype, int mode, const void* g, const void* x, 
     // the sums of ALL samples must be complete before the batch-statistics coefficients read them, and a staged call hands
     // them to the caller between the stages: a separate (tiny) launch then; otherwise the coefficient kernel adds up its own
     const bool sums_first = batch || stage == 1;
-#define S2E_LAUNCH_BWD(TT, MM) do { \
-    if (stage != 2) { modulate_bwd_reduce_kernel<TT, MM><<<grid1, 256, 0, st>>>((const TT*)g, (const TT*)x, (const TT*)gb, stats, style, (TT*)dgb, part, HW, C, rg.cg, rg.cgb, rg.rpp, lrelu, sld, iters, (const TT*)fout, xw, inv_xw); \
-        if (sums_first) modulate_bwd_sums_kernel<MM><<<gridc, 256, 0, st>>>(part, ws, N, C, P); } \
-    if (stage != 1) { modulate_bwd_coef_kernel<MM><<<gridc, 256, 0, st>>>(ws, (stage == 2 || sums_first) ? nullptr : part, P, coef, stats, style, dstyle, N, C, HW, sld, batch, batch_count); \
-    if (quad) { const int gq = ((HW >> 2) * rg.cg + 255) / 256; \
-        modulate_bwd_apply_quad_kernel<TT><<<dim3(gq < gx_cap ? gq : gx_cap, N), 256, 0, st>>>((const TT*)x, (const TT*)gb, (const TT*)dgb, coef, (TT*)dx, (const TT*)dx_add, HW, C, rg.cg, acc, gst, xw, 2.f * inv_xw); } \
-    else modulate_bwd_apply_kernel<TT, MM><<<grid2, 256, 0, st>>>((const TT*)g, (const TT*)x, (const TT*)gb, (const TT*)dgb, coef, (TT*)dx, (const TT*)dx_add, vps, HW, C, rg.cg, cg_shift, lrelu, acc, gst, xw, inv_xw); } } while (0)
-    if (dtype == S2E_BF16) { if (mode == S2E_NORM_SPADE_STYLE) S2E_LAUNCH_BWD(bf16_t, S2E_NORM_SPADE_STYLE); else S2E_LAUNCH_BWD(bf16_t, S2E_NORM_PLAIN_IN); }
-    else { if (mode == S2E_NORM_SPADE_STYLE) S2E_LAUNCH_BWD(float, S2E_NORM_SPADE_STYLE); else S2E_LAUNCH_BWD(float, S2E_NORM_PLAIN_IN); }
-#undef S2E_LAUNCH_BWD
-    S2E_CHECK_LAUNCH("modulate_bwd kernels");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_modulate_bwd", [&](auto t) { using T = decltype(t);
+        with_norm_mode(mode, [&](auto MM) {
+            if (stage != 2) {
+                modulate_bwd_reduce_kernel<T, MM><<<grid1, 256, 0, st>>>((const T*)g, (const T*)x, (const T*)gb, stats, style, (T*)dgb, part, HW, C, rg.cg, rg.cgb, rg.rpp, lrelu, sld, iters, (const T*)fout, xw, inv_xw);
+                if (sums_first) modulate_bwd_sums_kernel<MM><<<gridc, 256, 0, st>>>(part, ws, N, C, P);
+            }
+            if (stage == 1) return;
+            modulate_bwd_coef_kernel<MM><<<gridc, 256, 0, st>>>(ws, (stage == 2 || sums_first) ? nullptr : part, P, coef, stats, style, dstyle, N, C, HW, sld, batch, batch_count);
+            if (quad) {
+                const int gq = ((HW >> 2) * rg.cg + 255) / 256;
+                modulate_bwd_apply_quad_kernel<T><<<dim3(gq < gx_cap ? gq : gx_cap, N), 256, 0, st>>>((const T*)x, (const T*)gb, (const T*)dgb, coef, (T*)dx, (const T*)dx_add, HW, C, rg.cg, acc, gst, xw, 2.f * inv_xw);
+            } else modulate_bwd_apply_kernel<T, MM><<<grid2, 256, 0, st>>>((const T*)g, (const T*)x, (const T*)gb, (const T*)dgb, coef, (T*)dx, (const T*)dx_add, vps, HW, C, rg.cg, cg_shift, lrelu, acc, gst, xw, inv_xw);
+        });
+        S2E_CHECK_LAUNCH("modulate_bwd kernels"); return S2E_OK; });
 }
 
 extern "C" int s2e_modulate_bwd(int dtype, int mode, const void* g, const void* x, const void* gb, const float* stats,
@@ -1139,7 +1134,7 @@ extern "C" int s2e_modulate_bwd_relay(int dtype, int mode, const void* g, const 
 }
 
 extern "C" size_t s2e_modulate_bwd_workspace_bytes(int dtype, int N, int HW, int C) {
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    const int vec = s2e_vec_lanes(dtype);
     if (N <= 0 || HW <= 0 || C <= 0 || C % vec) return 0;
     const RowGeom rg = row_geom(C, vec);
     const int P = ceil_div(HW, rg.rpp * slab_iters_for(HW, rg.rpp, N, rg.zblocks));
@@ -1153,16 +1148,14 @@ extern "C" size_t s2e_modulate_bwd_workspace_bytes(int dtype, int N, int HW, int
 extern "C" int s2e_instance_norm_fwd(int dtype, const void* x, void* out, float* stats, double* ws, int N, int HW, int C,
                                      float eps, int lrelu, void* stream) {
     if (!x || !out || !stats || !ws || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_instance_norm_fwd: bad argument");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_instance_norm_fwd: bad dtype %d", dtype);
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    S2E_CHECK_DTYPE(dtype, "s2e_instance_norm_fwd");
+    const int vec = s2e_vec_lanes(dtype);
     if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_instance_norm_fwd: C=%d not a multiple of %d", C, vec);
-    if (HW <= in_small_hw()) {
-        hipStream_t st = (hipStream_t)stream;
-        if (dtype == S2E_BF16) S2E_SMALL_LAUNCH2(in_small_kernel, bf16_t, 1, (const bf16_t*)x, (bf16_t*)out, ws, stats, HW, C, eps, lrelu);
-        else S2E_SMALL_LAUNCH2(in_small_kernel, float, 1, (const float*)x, (float*)out, ws, stats, HW, C, eps, lrelu);
-        S2E_CHECK_LAUNCH("in_small_kernel");
-        return S2E_OK;
-    }
+    if (HW <= in_small_hw())
+        return s2e_with_dtype(dtype, "s2e_instance_norm_fwd", [&](auto t) { using T = decltype(t);
+            small_launch<T>(N, C, [&](auto G, dim3 sg) {
+                in_small_kernel<T, 1, G><<<sg, 256, 0, (hipStream_t)stream>>>((const T*)x, (T*)out, ws, stats, HW, C, eps, lrelu); });
+            S2E_CHECK_LAUNCH("in_small_kernel"); return S2E_OK; });
     if (const int rc = s2e_in_stats(dtype, x, N, HW, C, eps, ws, stats, nullptr, stream)) return rc;
     return s2e_modulate_fwd(dtype, S2E_NORM_PLAIN_IN, x, nullptr, stats, nullptr, out, N, HW, C, lrelu, 0, stream);
 }
@@ -1171,15 +1164,13 @@ extern "C" int s2e_instance_norm_fwd(int dtype, const void* x, void* out, float*
 extern "C" int s2e_instance_norm_bwd(int dtype, const void* g, const void* x, const float* stats, void* dx, double* ws,
                                      int N, int HW, int C, int lrelu, void* stream) {
     if (!g || !x || !stats || !dx || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_instance_norm_bwd: bad argument");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_instance_norm_bwd: bad dtype %d", dtype);
-    const int vec = dtype == S2E_BF16 ? 8 : 4;
+    S2E_CHECK_DTYPE(dtype, "s2e_instance_norm_bwd");
+    const int vec = s2e_vec_lanes(dtype);
     if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_instance_norm_bwd: C=%d not a multiple of %d", C, vec);
-    if (HW <= in_small_hw()) {
-        hipStream_t st = (hipStream_t)stream;
-        if (dtype == S2E_BF16) S2E_SMALL_LAUNCH(in_small_bwd_kernel, bf16_t, (const bf16_t*)g, (const bf16_t*)x, stats, (bf16_t*)dx, HW, C, lrelu);
-        else S2E_SMALL_LAUNCH(in_small_bwd_kernel, float, (const float*)g, (const float*)x, stats, (float*)dx, HW, C, lrelu);
-        S2E_CHECK_LAUNCH("in_small_bwd_kernel");
-        return S2E_OK;
-    }
+    if (HW <= in_small_hw())
+        return s2e_with_dtype(dtype, "s2e_instance_norm_bwd", [&](auto t) { using T = decltype(t);
+            small_launch<T>(N, C, [&](auto G, dim3 sg) {
+                in_small_bwd_kernel<T, G><<<sg, 256, 0, (hipStream_t)stream>>>((const T*)g, (const T*)x, stats, (T*)dx, HW, C, lrelu); });
+            S2E_CHECK_LAUNCH("in_small_bwd_kernel"); return S2E_OK; });
     return s2e_modulate_bwd(dtype, S2E_NORM_PLAIN_IN, g, x, nullptr, stats, nullptr, dx, nullptr, nullptr, ws, N, HW, C, lrelu, 0, stream);
 }

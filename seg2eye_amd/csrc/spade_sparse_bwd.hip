@@ -217,11 +217,9 @@ extern "C" int s2e_spade_uniform_sums(int dtype, const void* dgb, int N, int H, 
     const int tiles_y = H / 16, tiles_x = W / 16;
     const int grid = N * (tiles_y - 2) * (tiles_x - 2);      // as many blocks as there can be uniform-interior rectangles
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) spade_uniform_sums_kernel<bf16_t><<<grid, 256, 0, st>>>((const bf16_t*)dgb, H, W, C2, tiles_y, tiles_x, cls, ui_list, counts, R, ncls);
-    else if (dtype == S2E_F32) spade_uniform_sums_kernel<float><<<grid, 256, 0, st>>>((const float*)dgb, H, W, C2, tiles_y, tiles_x, cls, ui_list, counts, R, ncls);
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_spade_uniform_sums: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("spade_uniform_sums_kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_spade_uniform_sums", [&](auto t) { using T = decltype(t);
+        spade_uniform_sums_kernel<T><<<grid, 256, 0, st>>>((const T*)dgb, H, W, C2, tiles_y, tiles_x, cls, ui_list, counts, R, ncls);
+        S2E_CHECK_LAUNCH("spade_uniform_sums_kernel"); return S2E_OK; });
 }
 
 extern "C" int s2e_spade_uniform_grads(const s2e_spade_uni_job* jobs_host, int n_jobs, void* stream) {

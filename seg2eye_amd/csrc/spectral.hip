@@ -536,7 +536,7 @@ extern "C" int s2e_pack_conv_weight(int dtype, const float* w, void* packed, con
                                     int cin_pad, int transposed, void* stream) {
     if (!w || !packed || cout <= 0 || cin <= 0 || kh <= 0 || kw <= 0 || cin_pad < cin)
         S2E_FAIL(S2E_ERR_ARG, "s2e_pack_conv_weight: bad argument");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_pack_conv_weight: bad dtype %d", dtype);
+    S2E_CHECK_DTYPE(dtype, "s2e_pack_conv_weight");
     const int taps = kh * kw;
     if (taps > 64) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_pack_conv_weight: kernel %dx%d too large", kh, kw);
     const bool tr = (transposed & 1) != 0;
@@ -554,32 +554,25 @@ extern "C" int s2e_pack_conv_weight(int dtype, const float* w, void* packed, con
     if (transposed & 2) {                                    // source in channels-last order w[co][tap][ci]
         if (cin_pad != cin) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_pack_conv_weight: a channels-last source needs cin_pad == cin");
         if (cin % 8) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_pack_conv_weight: a channels-last source needs cin %% 8 == 0");
-        if (!tr) {                                           // forward: the source row IS the packed row: a streaming convert
+    }
+    return s2e_with_dtype(dtype, "s2e_pack_conv_weight", [&](auto t) { using T = decltype(t);
+        if ((transposed & 2) && !tr) {                       // channels-last, forward: the source row IS the packed row: a streaming convert
             const int grid = ceil_div((long)rows * kpad, PACK_CL_ELEMS);
-            if (dtype == S2E_BF16) pack_fwd_cl_kernel<bf16_t><<<grid, 256, 0, st>>>(w, (bf16_t*)packed, sigma, cout, taps * cin, rows, kpad);
-            else pack_fwd_cl_kernel<float><<<grid, 256, 0, st>>>(w, (float*)packed, sigma, cout, taps * cin, rows, kpad);
-        } else {
+            pack_fwd_cl_kernel<T><<<grid, 256, 0, st>>>(w, (T*)packed, sigma, cout, taps * cin, rows, kpad);
+        } else if (transposed & 2) {
             dim3 grid(ceil_div(cout, 64), taps * ceil_div(rows, 64));
             const size_t lds = (size_t)64 * 65 * sizeof(float);
-            if (dtype == S2E_BF16) pack_tr_cl_kernel<bf16_t><<<grid, 256, lds, st>>>(w, (bf16_t*)packed, sigma, cout, cin, taps, rows, kpad);
-            else pack_tr_cl_kernel<float><<<grid, 256, lds, st>>>(w, (float*)packed, sigma, cout, cin, taps, rows, kpad);
+            pack_tr_cl_kernel<T><<<grid, 256, lds, st>>>(w, (T*)packed, sigma, cout, cin, taps, rows, kpad);
+        } else if (!transposed) {
+            dim3 grid(rows / 4, ceil_div(cin_pad, 64));
+            const size_t lds = (size_t)4 * 64 * taps * sizeof(float);
+            pack_fwd_kernel<T><<<grid, 256, lds, st>>>(w, (T*)packed, sigma, cout, cin, taps, cin_pad, kpad);
+        } else {
+            dim3 grid(ceil_div(cout, 64), ceil_div(rows, 8));
+            const size_t lds = (size_t)64 * (8 * taps + 1) * sizeof(float);
+            pack_tr_kernel<T><<<grid, 256, lds, st>>>(w, (T*)packed, sigma, cout, cin, taps, rows, kpad);
         }
-        S2E_CHECK_LAUNCH("pack kernels (channels-last source)");
-        return S2E_OK;
-    }
-    if (!transposed) {
-        dim3 grid(rows / 4, ceil_div(cin_pad, 64));
-        const size_t lds = (size_t)4 * 64 * taps * sizeof(float);
-        if (dtype == S2E_BF16) pack_fwd_kernel<bf16_t><<<grid, 256, lds, st>>>(w, (bf16_t*)packed, sigma, cout, cin, taps, cin_pad, kpad);
-        else pack_fwd_kernel<float><<<grid, 256, lds, st>>>(w, (float*)packed, sigma, cout, cin, taps, cin_pad, kpad);
-    } else {
-        dim3 grid(ceil_div(cout, 64), ceil_div(rows, 8));
-        const size_t lds = (size_t)64 * (8 * taps + 1) * sizeof(float);
-        if (dtype == S2E_BF16) pack_tr_kernel<bf16_t><<<grid, 256, lds, st>>>(w, (bf16_t*)packed, sigma, cout, cin, taps, rows, kpad);
-        else pack_tr_kernel<float><<<grid, 256, lds, st>>>(w, (float*)packed, sigma, cout, cin, taps, rows, kpad);
-    }
-    S2E_CHECK_LAUNCH("pack kernels");
-    return S2E_OK;
+        S2E_CHECK_LAUNCH((transposed & 2) ? "pack kernels (channels-last source)" : "pack kernels"); return S2E_OK; });
 }
 
 extern "C" long s2e_pack_block_map(int dtype, const s2e_pack_job* jobs_host, int n_jobs, int* block_map_host) {
@@ -607,15 +600,14 @@ extern "C" long s2e_pack_block_map(int dtype, const s2e_pack_job* jobs_host, int
 extern "C" int s2e_pack_conv_weights(int dtype, const s2e_pack_job* jobs, const int* block_map, int n_blocks, int max_taps,
                                      const float* sigma_base, void* stream) {
     if (!jobs || !block_map || n_blocks <= 0 || max_taps <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_pack_conv_weights: bad argument");
-    if (dtype != S2E_BF16 && dtype != S2E_F32) S2E_FAIL(S2E_ERR_ARG, "s2e_pack_conv_weights: bad dtype %d", dtype);
+    S2E_CHECK_DTYPE(dtype, "s2e_pack_conv_weights");
     if (max_taps > 16) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_pack_conv_weights: more than 16 taps");
     size_t lds = (size_t)64 * (8 * max_taps + 1) * sizeof(float);
     if (lds < (size_t)64 * 65 * sizeof(float)) lds = (size_t)64 * 65 * sizeof(float);      // (the channels-last tile transpose)
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) pack_batch_kernel<bf16_t><<<n_blocks, 256, lds, st>>>(jobs, block_map, sigma_base, dtype);
-    else pack_batch_kernel<float><<<n_blocks, 256, lds, st>>>(jobs, block_map, sigma_base, dtype);
-    S2E_CHECK_LAUNCH("batched pack kernel");
-    return S2E_OK;
+    return s2e_with_dtype(dtype, "s2e_pack_conv_weights", [&](auto t) {
+        pack_batch_kernel<decltype(t)><<<n_blocks, 256, lds, st>>>(jobs, block_map, sigma_base, dtype);
+        S2E_CHECK_LAUNCH("batched pack kernel"); return S2E_OK; });
 }
 
 // ------------------------------------------------------------------------------------ gradient through W = W_orig / sigma
@@ -822,7 +814,7 @@ extern "C" int s2e_unpack_weight_grad(const float* gw_packed, float* gw_oihw, in
                                       int accumulate, void* stream) {
     if (!gw_packed || !gw_oihw || cout <= 0 || cin <= 0 || cin_pad < cin) S2E_FAIL(S2E_ERR_ARG, "s2e_unpack_weight_grad: bad argument");
     const long total = (long)cout * cin * kh * kw;
-    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    const int grid = s2e_grid1d(total, 2048);
     const int taps = kh * kw;
     if (taps > 1 && taps <= 64) {
         const int tiles = ceil_div(cout, SNG_ROWS) * ceil_div(cin, 64);
@@ -841,7 +833,7 @@ extern "C" int s2e_sn_weight_grad(const float* gw_packed, const float* w_orig, c
         S2E_FAIL(S2E_ERR_ARG, "s2e_sn_weight_grad: bad argument");
     hipStream_t st = (hipStream_t)stream;
     const long total = (long)cout * cin * kh * kw;
-    const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    const int grid = s2e_grid1d(total, 2048);
     const int taps = kh * kw;
     if (taps > 1 && taps <= 64) {
         const int tiles = ceil_div(cout, SNG_ROWS) * ceil_div(cin, 64);

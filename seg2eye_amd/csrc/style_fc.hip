@@ -139,17 +139,16 @@ extern "C" int s2e_style_fc_bwd(const float* dbig, const float* gbig, const floa
     }
     hipStream_t st = (hipStream_t)stream;
     const size_t sm = bwd_smem(K);
-#define S2E_SF(KK) do { \
-        static bool attr_done = false; \
-        if (!attr_done) { (void)hipFuncSetAttribute((const void*)style_fc_bwd_kernel<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); attr_done = true; } \
-        style_fc_bwd_kernel<KK><<<grid, SF_THREADS, sm, st>>>(dbig, gbig, big, w, W, gW, gb, partial, N, S, slope); } while (0)
+    auto go = [&](auto KK) {
+        static bool attr_done = false;                       // one per instantiation, as the kernel
+        if (!attr_done) { (void)hipFuncSetAttribute((const void*)style_fc_bwd_kernel<KK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm); attr_done = true; }
+        style_fc_bwd_kernel<KK><<<grid, SF_THREADS, sm, st>>>(dbig, gbig, big, w, W, gW, gb, partial, N, S, slope); };
     switch (K) {
-        case 8: S2E_SF(8); break;
-        case 16: S2E_SF(16); break;
-        case 32: S2E_SF(32); break;
-        default: S2E_SF(64); break;
+        case 8: go(int_c<8>{}); break;
+        case 16: go(int_c<16>{}); break;
+        case 32: go(int_c<32>{}); break;
+        default: go(int_c<64>{}); break;
     }
-#undef S2E_SF
     S2E_CHECK_LAUNCH("style_fc_bwd_kernel");
     if (dw) {
         style_fc_dw_fold_kernel<<<ceil_div(N * K, SF_THREADS), SF_THREADS, 0, st>>>(partial, dw, N * K, grid);
@@ -310,6 +309,13 @@ __global__ __launch_bounds__(256) void fc_head_bwd_kernel(const T* __restrict__ 
 }
 }  // namespace
 
+// launch(T{}, NMAX as an integral_constant): the head kernels are stamped for the element type and for up to 16 or 32 outputs
+template <typename F> static int with_head_kernel(int dtype, int N, const char* name, const char* kernel, F&& launch) {
+    return s2e_with_dtype(dtype, name, [&](auto t) {
+        if (N <= 16) launch(t, int_c<16>{}); else launch(t, int_c<32>{});
+        S2E_CHECK_LAUNCH(kernel); return S2E_OK; });
+}
+
 extern "C" int s2e_fc_head_supported(int M, int N) { return M >= 1 && M <= FH_MAXM && N >= 1 && N <= FH_MAXN; }
 
 extern "C" size_t s2e_fc_head_fwd_workspace_bytes(int M, int P, int C, int N) {
@@ -324,12 +330,8 @@ extern "C" int s2e_fc_head_fwd(int dtype, const void* x, const float* W, const f
         hipStream_t st2 = (hipStream_t)stream;
         const int chunks = ceil_div((long)P * C, 256);
         const dim3 grid(chunks, ceil_div(M, 8));
-#define S2E_FHP(TT, NM) fc_head_part_kernel<TT, NM><<<grid, 256, 0, st2>>>((const TT*)x, W, (float*)workspace, M, P, C, N, slope)
-        if (dtype == S2E_BF16) { if (N <= 16) S2E_FHP(bf16_t, 16); else S2E_FHP(bf16_t, 32); }
-        else if (dtype == S2E_F32) { if (N <= 16) S2E_FHP(float, 16); else S2E_FHP(float, 32); }
-#undef S2E_FHP
-        else S2E_FAIL(S2E_ERR_ARG, "s2e_fc_head_fwd: bad dtype %d", dtype);
-        S2E_CHECK_LAUNCH("fc_head_part_kernel");
+        if (const int rc = with_head_kernel(dtype, N, "s2e_fc_head_fwd", "fc_head_part_kernel", [&](auto t, auto NM) { using T = decltype(t);
+                fc_head_part_kernel<T, NM><<<grid, 256, 0, st2>>>((const T*)x, W, (float*)workspace, M, P, C, N, slope); })) return rc;
         fc_head_fin_kernel<<<ceil_div(M * N, 256), 256, 0, st2>>>((const float*)workspace, b, y, M, N, chunks);
         S2E_CHECK_LAUNCH("fc_head_fin_kernel");
         return S2E_OK;
@@ -338,13 +340,8 @@ extern "C" int s2e_fc_head_fwd(int dtype, const void* x, const float* W, const f
     if ((size_t)P * C * sizeof(float) > 48 * 1024) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_fc_head_fwd: a sample row of %d x %d features does not fit the LDS stage", P, C);
     hipStream_t st = (hipStream_t)stream;
     const size_t lds = (size_t)P * (C + 1) * sizeof(float);
-#define S2E_FH(TT, NM) fc_head_fwd_kernel<TT, NM><<<M, FH_FWD_THREADS, lds, st>>>((const TT*)x, W, b, y, P, C, N, slope)
-    if (dtype == S2E_BF16) { if (N <= 16) S2E_FH(bf16_t, 16); else S2E_FH(bf16_t, 32); }
-    else if (dtype == S2E_F32) { if (N <= 16) S2E_FH(float, 16); else S2E_FH(float, 32); }
-#undef S2E_FH
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_fc_head_fwd: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("fc_head_fwd_kernel");
-    return S2E_OK;
+    return with_head_kernel(dtype, N, "s2e_fc_head_fwd", "fc_head_fwd_kernel", [&](auto t, auto NM) { using T = decltype(t);
+        fc_head_fwd_kernel<T, NM><<<M, FH_FWD_THREADS, lds, st>>>((const T*)x, W, b, y, P, C, N, slope); });
 }
 
 extern "C" int s2e_fc_head_bwd(int dtype, const void* x, const float* W, const float* dy, void* dx, float* dW, float* db, int M, int P, int C,
@@ -352,11 +349,6 @@ extern "C" int s2e_fc_head_bwd(int dtype, const void* x, const float* W, const f
     if (!x || !W || !dy || P <= 0 || C <= 0 || !s2e_fc_head_supported(M, N)) S2E_FAIL(S2E_ERR_ARG, "s2e_fc_head_bwd: bad argument (M=%d N=%d)", M, N);
     hipStream_t st = (hipStream_t)stream;
     const int grid = ceil_div((long)P * C, 256);
-#define S2E_FH(TT, NM) fc_head_bwd_kernel<TT, NM><<<grid, 256, 0, st>>>((const TT*)x, W, dy, (TT*)dx, dW, db, M, P, C, N, slope)
-    if (dtype == S2E_BF16) { if (N <= 16) S2E_FH(bf16_t, 16); else S2E_FH(bf16_t, 32); }
-    else if (dtype == S2E_F32) { if (N <= 16) S2E_FH(float, 16); else S2E_FH(float, 32); }
-#undef S2E_FH
-    else S2E_FAIL(S2E_ERR_ARG, "s2e_fc_head_bwd: bad dtype %d", dtype);
-    S2E_CHECK_LAUNCH("fc_head_bwd_kernel");
-    return S2E_OK;
+    return with_head_kernel(dtype, N, "s2e_fc_head_bwd", "fc_head_bwd_kernel", [&](auto t, auto NM) { using T = decltype(t);
+        fc_head_bwd_kernel<T, NM><<<grid, 256, 0, st>>>((const T*)x, W, dy, (T*)dx, dW, db, M, P, C, N, slope); });
 }

@@ -330,6 +330,6 @@ extern "C" int s2e_sidebyside_u8(int fake_dtype, const void* fake, const float* 
     g.syt = 1.0 / ((double)h / (double)Ht); g.sxt = 1.0 / ((double)w / (double)Wt);
     g.syg = 1.0 / ((double)h / (double)g.GH); g.sxg = 1.0 / ((double)w / (double)g.GW);
     hipStream_t st = (hipStream_t)stream;
-    if (fake_dtype == S2E_BF16) return sbs_launch<bf16_t>(g, row_stride, panel_stride, (double*)ws, status, out, st);
-    return sbs_launch<float>(g, row_stride, panel_stride, (double*)ws, status, out, st);
+    return s2e_with_dtype(fake_dtype, "s2e_sidebyside_u8", [&](auto t) {
+        return sbs_launch<decltype(t)>(g, row_stride, panel_stride, (double*)ws, status, out, st); });
 }

@@ -408,3 +408,178 @@ def test_checkpoint_roundtrip_and_module_prefix(tmp_path):
     checkpoint.load_network(D2, 'D', 'latest', opt)
     for (k, a), (_, b) in zip(D.state_dict().items(), D2.state_dict().items()):
         assert torch.equal(a, b), k
+
+
+# A dummy (never dereferenced) non-null pointer, 16-byte aligned; the dtype codes; the S2E_NORM_* modes used below; one conv shape
+# (an s2e_conv_desc, passed by reference): the patch-resident forward, the generic weight gradient.
+P, BF16, F32, BAD = 0x7000, 1, 0, 7
+SP, ACC = 0, 0x100
+BIG = ('s2e_conv_desc', 8, 256, 256, 128, 256, 256, 256, 3, 3, 1, 1, 0, 0, 0, 0)
+# (entry point, arguments, return code, s2e_last_error()) of calls that fail BEFORE any launch: per entry point a missing required
+# pointer, dtype 7 with otherwise plausible arguments (and with a second fault, to pin which check wins), and where the op has a
+# vector-width rule a C that breaks it for that dtype.  -1 is S2E_ERR_ARG, -3 S2E_ERR_UNSUPPORTED.
+HOST_ERROR_TABLE = [
+    ('s2e_label_conv3x3', (BF16, None, P, P, P, 1, 8, 8, 8, 8, 4, 16, 0, None), -1, 's2e_label_conv3x3: bad argument'),
+    ('s2e_label_conv3x3', (BAD, P, P, P, P, 1, 8, 8, 8, 8, 4, 16, 0, None), -1, 's2e_label_conv3x3: bad dtype 7'),
+    ('s2e_label_conv3x3', (BAD, P, P, P, P, 1, 9, 8, 8, 8, 4, 16, 0, None), -3, 's2e_label_conv3x3: 9x8 is not an integer multiple of 8x8'),
+    ('s2e_label_conv3x3_batch', (BF16, P, None, P, 4, P, 1, 8, 8, 4, None), -1, 's2e_label_conv3x3_batch: bad argument'),
+    ('s2e_label_conv3x3_batch', (BAD, P, P, P, 4, P, 1, 8, 8, 4, None), -1, 's2e_label_conv3x3_batch: bad dtype 7'),
+    ('s2e_onehot_nhwc', (BF16, P, None, None, 1, 8, 8, 8, 8, 4, 8, None), -1, 's2e_onehot_nhwc: bad argument'),
+    ('s2e_onehot_nhwc', (BAD, P, None, P, 1, 8, 8, 8, 8, 4, 8, None), -1, 's2e_onehot_nhwc: bad dtype 7'),
+    ('s2e_onehot_nhwc', (BAD, P, None, P, 1, 8, 8, 8, 8, 4, 5, None), -1, 's2e_onehot_nhwc: bad dtype 7'),
+    ('s2e_upsample2x_fwd', (BF16, None, P, 1, 4, 4, 8, None), -1, 's2e_upsample2x_fwd: bad argument'),
+    ('s2e_upsample2x_fwd', (BAD, P, P, 1, 4, 4, 8, None), -1, 's2e_upsample2x_fwd: bad dtype 7'),
+    ('s2e_upsample2x_fwd', (BF16, P, P, 1, 4, 4, 12, None), -3, 's2e_upsample2x_fwd: C=12 not a multiple of 8'),
+    ('s2e_upsample2x_fwd', (F32, P, P, 1, 4, 4, 6, None), -3, 's2e_upsample2x_fwd: C=6 not a multiple of 4'),
+    ('s2e_upsample2x_bwd', (F32, P, None, 1, 4, 4, 8, None), -1, 's2e_upsample2x_bwd: bad argument'),
+    ('s2e_upsample2x_bwd', (BAD, P, P, 1, 4, 4, 8, None), -1, 's2e_upsample2x_bwd: bad dtype 7'),
+    ('s2e_upsample2x_bwd', (BF16, P, P, 1, 4, 4, 12, None), -3, 's2e_upsample2x_bwd: C=12 not a multiple of 8'),
+    ('s2e_upsample2x_bwd', (F32, P, P, 1, 4, 4, 6, None), -3, 's2e_upsample2x_bwd: C=6 not a multiple of 4'),
+    ('s2e_avgpool3x3s2_fwd', (BF16, None, P, 1, 8, 8, 8, None), -1, 's2e_avgpool3x3s2_fwd: bad argument'),
+    ('s2e_avgpool3x3s2_fwd', (BAD, P, P, 1, 8, 8, 8, None), -1, 's2e_avgpool3x3s2_fwd: bad dtype 7'),
+    ('s2e_avgpool3x3s2_bwd', (F32, P, None, 1, 8, 8, 8, None), -1, 's2e_avgpool3x3s2_bwd: bad argument'),
+    ('s2e_avgpool3x3s2_bwd', (BAD, P, P, 1, 8, 8, 3, None), -1, 's2e_avgpool3x3s2_bwd: bad dtype 7'),
+    ('s2e_tanh_bwd', (BF16, P, None, P, 64, None), -1, 's2e_tanh_bwd: bad argument'),
+    ('s2e_tanh_bwd', (BAD, P, P, P, 64, None), -1, 's2e_tanh_bwd: bad dtype 7'),
+    ('s2e_lrelu_bwd', (BF16, P, P, None, 64, None), -1, 's2e_lrelu_bwd: bad argument'),
+    ('s2e_lrelu_bwd', (BAD, P, P, P, 64, None), -1, 's2e_lrelu_bwd: bad dtype 7'),
+    ('s2e_lrelu_bwd', (BAD, P, P + 4, P, 64, None), -1, 's2e_lrelu_bwd: pointers must be 16-byte aligned'),
+    ('s2e_bilinear_resize_fwd', (BF16, None, P, 1, 8, 8, 4, 4, None), -1, 's2e_bilinear_resize_fwd: bad argument'),
+    ('s2e_bilinear_resize_fwd', (BAD, P, P, 1, 8, 8, 4, 4, None), -1, 's2e_bilinear_resize_fwd: bad dtype 7'),
+    ('s2e_bilinear_resize_fwd', (BAD, P, P, 1, 8, 8, 70000, 4, None), -1, 's2e_bilinear_resize_fwd: bad dtype 7'),
+    ('s2e_bilinear_resize_bwd', (F32, P, None, 1, 8, 8, 4, 4, None), -1, 's2e_bilinear_resize_bwd: bad argument'),
+    ('s2e_bilinear_resize_bwd', (BAD, P, P, 1, 8, 8, 4, 4, None), -1, 's2e_bilinear_resize_bwd: bad dtype 7'),
+    ('s2e_spade_class_table', (BF16, P, P, None, P, P, 4, 64, 64, None), -1, 's2e_spade_class_table: bad argument (nh <= 128)'),
+    ('s2e_spade_class_table', (BAD, P, P, P, P, P, 4, 64, 64, None), -1, 's2e_spade_class_table: bad dtype 7'),
+    ('s2e_spade_class_table_batch', (F32, P, None, 4, P, 4, None), -1, 's2e_spade_class_table_batch: bad argument'),
+    ('s2e_spade_class_table_batch', (BAD, P, P, 4, P, 4, None), -1, 's2e_spade_class_table_batch: bad dtype 7'),
+    ('s2e_spade_modulate_uniform', (BF16, P, P, P, 0, P, P, P, None, P, None, 1, 16, 16, 64, 8, 8, 1, 0, None), -1, 's2e_spade_modulate_uniform: bad argument'),
+    ('s2e_spade_modulate_uniform', (BAD, P, P, P, 0, P, P, P, P, P, None, 1, 16, 16, 64, 8, 8, 1, 0, None), -1, 's2e_spade_modulate_uniform: bad dtype 7'),
+    ('s2e_spade_modulate_uniform', (BAD, P, P, P, 0, P, P, P, P, P, None, 1, 15, 16, 64, 8, 8, 1, 1, None), -1, 's2e_spade_modulate_uniform: x_up needs even H, W'),
+    ('s2e_spade_modulate_uniform', (BF16, P, P, P, 0, P, P, P, P, P, None, 1, 16, 16, 12, 8, 8, 1, 0, None), -3, 's2e_spade_modulate_uniform: C=12 not a multiple of 8'),
+    ('s2e_spade_modulate_uniform', (F32, P, P, P, 0, P, P, P, P, P, None, 1, 16, 16, 6, 8, 8, 1, 0, None), -3, 's2e_spade_modulate_uniform: C=6 not a multiple of 4'),
+    ('s2e_spade_uniform_sums', (BF16, None, 1, 64, 64, 128, 4, P, P, P, P, None), -1, 's2e_spade_uniform_sums: null pointer'),
+    ('s2e_spade_uniform_sums', (BAD, P, 1, 64, 64, 128, 4, P, P, P, P, None), -1, 's2e_spade_uniform_sums: bad dtype 7'),
+    ('s2e_in_stats', (BF16, None, 1, 64, 8, 1e-05, P, P, None, None), -1, 's2e_in_stats: bad argument'),
+    ('s2e_in_stats', (BAD, P, 1, 64, 8, 1e-05, P, P, None, None), -1, 's2e_in_stats: bad dtype 7'),
+    ('s2e_in_stats', (BF16, P, 1, 64, 12, 1e-05, P, P, None, None), -3, 's2e_in_stats: C=12 not a multiple of 8'),
+    ('s2e_in_stats', (F32, P, 1, 64, 6, 1e-05, P, P, None, None), -3, 's2e_in_stats: C=6 not a multiple of 4'),
+    ('s2e_colsum', (BF16, None, 10, 8, P, None), -1, 's2e_colsum: bad argument'),
+    ('s2e_colsum', (BAD, P, 10, 8, P, None), -1, 's2e_colsum: bad dtype 7'),
+    ('s2e_colsum', (BAD, P, 10, 3, P, None), -1, 's2e_colsum: bad dtype 7'),
+    ('s2e_modulate_fwd', (BF16, 1, P, None, None, None, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_fwd: bad argument'),
+    ('s2e_modulate_fwd', (BF16, 0, P, None, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_fwd: SPADE_STYLE needs gb and style'),
+    ('s2e_modulate_fwd', (BAD, 1, P, None, P, None, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_fwd: bad dtype 7'),
+    ('s2e_modulate_fwd', (BAD, 0, P, None, P, None, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_fwd: SPADE_STYLE needs gb and style'),
+    ('s2e_modulate_fwd', (BF16, 1, P, None, P, None, P, 1, 64, 12, 0, 0, None), -3, 's2e_modulate_fwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_fwd', (F32, 1, P, None, P, None, P, 1, 64, 6, 0, 0, None), -3, 's2e_modulate_fwd: C=6 not a multiple of 4'),
+    ('s2e_modulate_bwd', (BF16, 1, P, P, None, P, None, P, None, None, None, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, P, P, None, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: SPADE_STYLE needs gb, style, dgb, dstyle'),
+    ('s2e_modulate_bwd', (BAD, 1, P, P, None, P, None, P, None, None, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd', (BF16, 1, P, P, None, P, None, P, None, None, P, 1, 64, 12, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_bwd', (F32, 1, P, P, None, P, None, P, None, None, P, 1, 64, 6, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
+    ('s2e_modulate_bwd_gamma', (BF16, 1, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd_gamma: SPADE_STYLE modes only'),
+    ('s2e_modulate_bwd_gamma', (BF16, 0, P, P, None, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd_gamma: gamma and out are required'),
+    ('s2e_modulate_bwd_gamma', (BF16, 0, P, P, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
+    ('s2e_modulate_bwd_gamma', (BAD, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd_gamma', (BF16, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 12, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_bwd_gamma', (F32, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 6, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
+    ('s2e_modulate_bwd_staged', (BF16, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 3, 0.0, 0, 0, None), -1, 's2e_modulate_bwd_staged: stage 3'),
+    ('s2e_modulate_bwd_staged', (BF16, 0, P, P, P, P, None, P, P, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
+    ('s2e_modulate_bwd_staged', (BAD, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd_staged', (BAD, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 8, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd_staged', (BF16, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 12, 0, 0, 1, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_bwd_staged', (F32, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 6, 0, 0, 1, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
+    ('s2e_modulate_bwd_staged', (BF16, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 8, 0, None), -1, 's2e_modulate_bwd: x at half resolution needs the gamma-only form, per-sample statistics and an even H x W map'),
+    ('s2e_modulate_bwd_relay', (BF16, SP | ACC, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 3, 0.0, 0, 0, None), -1, 's2e_modulate_bwd_relay: stage 3'),
+    ('s2e_modulate_bwd_relay', (BF16, 0, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd_relay: mode without S2E_NORM_ACCUMULATE_DX'),
+    ('s2e_modulate_bwd_relay', (BF16, SP | ACC, P, P, P, P, P, P, None, P, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
+    ('s2e_modulate_bwd_relay', (BAD, SP | ACC, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd_relay', (BF16, SP | ACC, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 12, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_bwd_relay', (F32, SP | ACC, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 6, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
+    ('s2e_instance_norm_fwd', (BF16, P, P, P, None, 1, 64, 8, 1e-05, 1, None), -1, 's2e_instance_norm_fwd: bad argument'),
+    ('s2e_instance_norm_fwd', (BAD, P, P, P, P, 1, 64, 8, 1e-05, 1, None), -1, 's2e_instance_norm_fwd: bad dtype 7'),
+    ('s2e_instance_norm_fwd', (BF16, P, P, P, P, 1, 64, 12, 1e-05, 1, None), -3, 's2e_instance_norm_fwd: C=12 not a multiple of 8'),
+    ('s2e_instance_norm_fwd', (F32, P, P, P, P, 1, 64, 6, 1e-05, 1, None), -3, 's2e_instance_norm_fwd: C=6 not a multiple of 4'),
+    ('s2e_instance_norm_bwd', (BF16, P, P, None, P, P, 1, 64, 8, 1, None), -1, 's2e_instance_norm_bwd: bad argument'),
+    ('s2e_instance_norm_bwd', (BAD, P, P, P, P, P, 1, 64, 8, 1, None), -1, 's2e_instance_norm_bwd: bad dtype 7'),
+    ('s2e_instance_norm_bwd', (BF16, P, P, P, P, P, 1, 64, 12, 1, None), -3, 's2e_instance_norm_bwd: C=12 not a multiple of 8'),
+    ('s2e_instance_norm_bwd', (F32, P, P, P, P, P, 1, 64, 6, 1, None), -3, 's2e_instance_norm_bwd: C=6 not a multiple of 4'),
+    ('s2e_loss_reduce', (BF16, 0, None, None, 64, 1.0, P, None), -1, 's2e_loss_reduce: bad argument'),
+    ('s2e_loss_reduce', (BF16, 3, P, None, 64, 1.0, P, None), -1, 's2e_loss_reduce: bad argument'),
+    ('s2e_loss_reduce', (BAD, 0, P, None, 64, 1.0, P, None), -1, 's2e_loss_reduce: bad dtype 7'),
+    ('s2e_loss_reduce', (BAD, 9, P, None, 64, 1.0, P, None), -1, 's2e_loss_reduce: bad dtype 7'),
+    ('s2e_loss_reduce', (BF16, 9, P, None, 64, 1.0, P, None), -1, 'loss: bad mode 9'),
+    ('s2e_loss_grad', (F32, 0, P, None, 64, 1.0, None, None, 0, None), -1, 's2e_loss_grad: bad argument'),
+    ('s2e_loss_grad', (BAD, 0, P, None, 64, 1.0, None, P, 0, None), -1, 's2e_loss_grad: bad dtype 7'),
+    ('s2e_loss_grad', (F32, 9, P, None, 64, 1.0, None, P, 0, None), -1, 'loss: bad mode 9'),
+    ('s2e_shard_sum', (BF16, P, None, 2, 64, None), -1, 's2e_shard_sum: bad argument'),
+    ('s2e_shard_sum', (BAD, P, P, 2, 64, None), -1, 's2e_shard_sum: bad dtype 7'),
+    ('s2e_shard_sum', (BF16, P, P, 2, 4, None), -1, 's2e_shard_sum: buffers and the shard size must be 16-byte multiples'),
+    ('s2e_shard_sum', (F32, P, P, 2, 6, None), -1, 's2e_shard_sum: buffers and the shard size must be 16-byte multiples'),
+    ('s2e_shard_sum', (BAD, P, P, 2, 6, None), -1, 's2e_shard_sum: buffers and the shard size must be 16-byte multiples'),
+    ('s2e_fc_head_fwd', (BF16, P, P, None, P, 2, 4, 8, 16, 0.2, None, 0, None), -1, 's2e_fc_head_fwd: bad argument (M=2 N=16)'),
+    ('s2e_fc_head_fwd', (BAD, P, P, P, P, 2, 4, 8, 16, 0.2, None, 0, None), -1, 's2e_fc_head_fwd: bad dtype 7'),
+    ('s2e_fc_head_fwd', (BAD, P, P, P, P, 2, 4, 8, 32, 0.2, P, 1 << 20, None), -1, 's2e_fc_head_fwd: bad dtype 7'),
+    ('s2e_fc_head_fwd', (BF16, P, P, P, P, 2, 4, 8, 64, 0.2, P, 1 << 20, None), -1, 's2e_fc_head_fwd: bad argument (M=2 N=64)'),
+    ('s2e_fc_head_fwd', (BF16, P, P, P, P, 2, 256, 64, 16, 0.2, None, 0, None), -3, 's2e_fc_head_fwd: a sample row of 256 x 64 features does not fit the LDS stage'),
+    ('s2e_fc_head_bwd', (BF16, P, None, P, P, P, P, 2, 4, 8, 16, 0.2, None), -1, 's2e_fc_head_bwd: bad argument (M=2 N=16)'),
+    ('s2e_fc_head_bwd', (BAD, P, P, P, P, P, P, 2, 4, 8, 16, 0.2, None), -1, 's2e_fc_head_bwd: bad dtype 7'),
+    ('s2e_pack_conv_weight', (BF16, P, None, None, 64, 64, 3, 3, 64, 0, None), -1, 's2e_pack_conv_weight: bad argument'),
+    ('s2e_pack_conv_weight', (BAD, P, P, None, 64, 64, 3, 3, 64, 0, None), -1, 's2e_pack_conv_weight: bad dtype 7'),
+    ('s2e_pack_conv_weight', (BAD, P, P, None, 64, 64, 9, 9, 64, 0, None), -1, 's2e_pack_conv_weight: bad dtype 7'),
+    ('s2e_pack_conv_weight', (F32, P, P, None, 64, 64, 3, 3, 64, 4, None), -3, 's2e_pack_conv_weight: the plane layout needs bf16, cin_pad == cin and a K dimension that is a multiple of 32'),
+    ('s2e_pack_conv_weight', (F32, P, P, None, 64, 60, 3, 3, 60, 2, None), -3, 's2e_pack_conv_weight: a channels-last source needs cin % 8 == 0'),
+    ('s2e_pack_conv_weights', (BF16, None, P, 4, 9, None, None), -1, 's2e_pack_conv_weights: bad argument'),
+    ('s2e_pack_conv_weights', (BAD, P, P, 4, 9, None, None), -1, 's2e_pack_conv_weights: bad dtype 7'),
+    ('s2e_pack_conv_weights', (BAD, P, P, 4, 25, None, None), -1, 's2e_pack_conv_weights: bad dtype 7'),
+    ('s2e_conv2d', (BF16, None, P, None, None, None, P, BIG, None, 0, None), -1, 's2e_conv2d: null pointer'),
+    ('s2e_conv2d', (BAD, P, P, None, None, None, P, BIG, None, 0, None), -1, 's2e_conv2d: bad dtype 7'),
+    ('s2e_conv2d_wgrad', (BF16, P, None, P, None, BIG, None, 0, None), -1, 's2e_conv2d_wgrad: null pointer'),
+    ('s2e_conv2d_wgrad', (BAD, P, P, P, None, BIG, None, 0, None), -1, 's2e_conv2d_wgrad: bad dtype 7'),
+    ('s2e_spade_conv_modulate', (BF16, P, P, P, P, None, P, 0, P, None, 8, 64, 64, 64, 128, 1, 0, None), -1, 's2e_spade_conv_modulate: null pointer'),
+    ('s2e_spade_conv_modulate', (BAD, P, P, P, P, P, P, 0, P, None, 8, 64, 64, 64, 128, 1, 0, None), -1, 's2e_spade_conv_modulate: bad dtype 7'),
+    ('s2e_spade_conv_modulate', (BAD, P, P, P, P, P, P, 2, P, None, 8, 64, 64, 64, 128, 1, 0, None), -1, 's2e_spade_conv_modulate: stats, style and bias must be 16-byte aligned (style_ld a multiple of 4)'),
+    ('s2e_spade_conv_modulate', (F32, P, P, P, P, P, P, 0, P, None, 8, 64, 64, 64, 24, 1, 0, None), -3, 's2e_spade_conv_modulate: shape N=8 64x64 C=64 nh=24 is not taken by the fused kernel (s2e_spade_conv_modulate_supported); run s2e_conv2d + s2e_modulate_fwd'),
+    ('s2e_spade_conv_modulate_sparse', (BF16, P, P, P, P, P, P, 0, P, None, 8, 64, 64, 64, 128, 1, 0, P, None, None), -1, 's2e_spade_conv_modulate_sparse: rect_list / rect_count missing'),
+    ('s2e_spade_conv_modulate_sparse', (BAD, P, P, P, P, P, P, 0, P, None, 8, 64, 64, 64, 128, 1, 0, P, P, None), -1, 's2e_spade_conv_modulate: bad dtype 7'),
+    ('s2e_openeds_error', (BF16, P, None, 1, 8, 8, P, None), -1, 's2e_openeds_error: bad argument'),
+    ('s2e_openeds_error', (BAD, P, P, 1, 8, 8, P, None), -1, 's2e_openeds_error: bad dtype 7'),
+    ('s2e_resize_to255', (BF16, None, 1, 8, 8, P, 4, 4, None), -1, 's2e_resize_to255: bad argument'),
+    ('s2e_resize_to255', (BAD, P, 1, 8, 8, P, 4, 4, None), -1, 's2e_resize_to255: bad dtype 7'),
+    ('s2e_resize_to255', (BAD, P, 1, 8, 8, P, 70000, 4, None), -3, 's2e_resize_to255: grid too large'),
+    ('s2e_sidebyside_u8', (BF16, None, P, 1, P, P, 1, 8, 8, 8, 8, 4, 4, 20, 80, P, P, P, None), -1, 's2e_sidebyside_u8: bad argument fake (null)'),
+    ('s2e_sidebyside_u8', (BAD, P, P, 1, P, P, 1, 8, 8, 8, 8, 4, 4, 20, 80, P, P, P, None), -1, 's2e_sidebyside_u8: bad argument fake_dtype'),
+    ('s2e_sidebyside_u8', (BAD, None, P, 1, P, P, 1, 8, 8, 8, 8, 4, 4, 20, 80, P, P, P, None), -1, 's2e_sidebyside_u8: bad argument fake_dtype'),
+]
+# the host-only size queries, one bf16 and one fp32 shape each (and a C that breaks the vector-width rule: 0)
+HOST_QUERY_TABLE = [
+    ('s2e_in_stats_workspace_bytes', (BF16, 2, 4096, 64), 10240),
+    ('s2e_in_stats_workspace_bytes', (F32, 2, 4096, 64), 18432),
+    ('s2e_in_stats_workspace_bytes', (BF16, 2, 4096, 12), 0),
+    ('s2e_in_stats_counters', (BF16, 2, 4096, 64), 2),
+    ('s2e_in_stats_counters', (F32, 2, 4096, 64), 2),
+    ('s2e_in_stats_counters', (F32, 2, 4096, 6), 0),
+    ('s2e_modulate_bwd_workspace_bytes', (BF16, 2, 4096, 64), 22528),
+    ('s2e_modulate_bwd_workspace_bytes', (F32, 2, 4096, 64), 38912),
+    ('s2e_modulate_bwd_workspace_bytes', (BF16, 2, 4096, 12), 0),
+]
+
+
+def test_dtype_entry_points_reject_bad_calls_before_any_launch():
+    """The return code and the message of an invalid call are the library's behaviour, including which check wins when several
+    fail.  Host-only: with a GPU visible the test skips itself, so that a dummy pointer can never reach a kernel."""
+    if torch.cuda.is_available():
+        pytest.skip('dummy pointers: host-only by construction')
+    from seg2eye_amd import _lib
+    L = _lib.lib()
+    assert (_lib.S2E_BF16, _lib.S2E_F32, _lib.NORM_SPADE_STYLE, _lib.NORM_ACCUMULATE_DX) == (BF16, F32, SP, ACC)
+    assert len({name for name, _, _, _ in HOST_ERROR_TABLE}) == 38
+    got = []
+    for name, args, _, _ in HOST_ERROR_TABLE:
+        rc = getattr(L, name)(*[ctypes.byref(_lib.ConvDesc(*a[1:])) if a is BIG else a for a in args])
+        got.append((name, args, rc, L.s2e_last_error().decode() if rc else ''))
+    wrong = [(g, w) for g, w in zip(got, HOST_ERROR_TABLE) if g != w]
+    assert not wrong, wrong
+    for name, args, want in HOST_QUERY_TABLE:
+        assert getattr(L, name)(*args) == want, (name, args)
