@@ -41,7 +41,8 @@ enum { S2E_NORM_SPADE_STYLE = 0, S2E_NORM_PLAIN_IN = 1,
        S2E_NORM_SPADE_STYLE_BATCH = 2,     /* s2e_modulate_bwd only: stats are BATCH statistics (BatchNorm SPADE) */
        S2E_NORM_ACCUMULATE_DX = 0x100 };   /* s2e_modulate_bwd only, OR-ed into mode: dx += instead of dx = (dx holds the
                                               gradient another consumer of the same x has already written) */
-enum { S2E_LOSS_NEG_MEAN = 0, S2E_LOSS_HINGE_REAL = 1, S2E_LOSS_HINGE_FAKE = 2, S2E_LOSS_L1 = 3 };
+enum { S2E_LOSS_NEG_MEAN = 0, S2E_LOSS_HINGE_REAL = 1, S2E_LOSS_HINGE_FAKE = 2, S2E_LOSS_L1 = 3,
+       S2E_LOSS_L1_NANGRAD = 4 };          /* L1 whose GRADIENT is NaN for a NaN difference (torch's, and S2E_LOSS_L1's, is 0) */
 
 int s2e_version(void);
 const char* s2e_last_error(void);
@@ -506,7 +507,10 @@ int s2e_lrelu_bwd(int dtype, const void* gy, const void* y, void* gx, long n, vo
  * Scalar reductions of GANLoss hinge (loss.py:66-77) and the GAN feature-matching L1
  * (pix2pix_model.py:231-241).  out[0] += scale * sum_i f(a_i, b_i):
  *   NEG_MEAN: -a      HINGE_REAL: -min(a-1,0)      HINGE_FAKE: -min(-a-1,0)      L1: |a-b|
- * (pass scale = coefficient / n for a mean).  b is only read for L1. */
+ * (pass scale = coefficient / n for a mean).  b is only read for L1 and L1_NANGRAD.
+ * L1_NANGRAD is L1 in everything but one case of s2e_loss_grad: where a_i - b_i is NaN the derivative is NaN, not the 0 that
+ * torch's sign() and L1 give -- a deliberate departure, used under the gradient guard so that a non-finite feature reaches the
+ * gradient arena (and s2e_grad_guard) instead of vanishing.  Every other input gives L1's bits. */
 int s2e_loss_reduce(int dtype, int mode, const void* a, const void* b, long n, float scale, float* out, void* stream);
 /* da_i (=|+=) scale * upstream * d f(a_i,b_i)/d a_i ; upstream = *gscale (a DEVICE fp32 scalar, the
  * gradient of the total loss w.r.t. this term; NULL means 1) so no host sync is needed;
@@ -559,6 +563,37 @@ int s2e_adam_flat(float* p, const float* g, float* m, float* v, long n, float* h
  * misaligned arena or n <= 0, before any launch. */
 int s2e_adam_flat_ema(float* p, const float* g, float* m, float* v, float* ema, long n, float* hyper, const float* ema_hyper,
                       void* stream);
+/* The gradient guard (an extension: the reference has none): skip a step whose gradient holds a non-finite element, clip by the
+ * global norm, report both -- without a host round trip.  s2e_grad_guard examines the gradient arena g[0..n) and writes the guard
+ * record; the guarded steps below read one word of it.
+ *   guard: 8 fp32 in DEVICE memory, first_bad: one int32 in DEVICE memory.
+ *     guard[0] in   max_norm; <= 0: no clipping
+ *     guard[1] in   skip_nonfinite, 0 or 1
+ *     guard[2] out  norm = |hyper[5]| * sqrt(sum g_i^2) over the FINITE elements: the norm of the gradient Adam would consume (hyper[5]
+ *                   = grad_scale); squares and sum in fp64, rounded to fp32 once
+ *     guard[3] out  the coefficient c this step applies:
+ *                     0    a skipped step: skip_nonfinite != 0 and a non-finite element exists;
+ *                     NaN  a non-finite element exists and skip_nonfinite == 0 (the step poisons the parameters, as an unguarded one);
+ *                     min(1, max_norm / (norm + 1e-6))  otherwise when max_norm > 0, in fp64 from the fp64 norm, rounded once
+ *                          (torch.nn.utils.clip_grad_norm_ with norm_type = 2);
+ *                     1    otherwise
+ *     guard[4] out  steps skipped so far             guard[5] out  steps clipped (c < 1) so far
+ *     guard[6] out  consecutive skipped steps; 0 after a step that ran         guard[7] reserved, written as 0
+ *     first_bad out the smallest i with !(|g[i]| <= FLT_MAX) -- an element test, never inferred from the sum --, or -1
+ *   The counters accumulate in the record: the caller zeroes it once.  Two launches, no atomics: per-block {fp64 sum, first index}
+ *   records in `workspace` (s2e_grad_guard_workspace_bytes(n) bytes, 8-byte aligned, owned by the caller), combined in a fixed order by
+ *   a one-block launch -- the same arena gives the same bits.  Reads g once (4 bytes per element).
+ * s2e_adam_flat_guarded / s2e_adam_flat_ema_guarded: s2e_adam_flat / s2e_adam_flat_ema with grad_scale = hyper[5] * guard[3] (one fp32
+ * multiply; c == 1 gives the unguarded bits).  With guard[3] == 0 the launch returns before it touches p, m, v or ema and hyper[4] is
+ * NOT incremented: a skipped step is not a step.
+ * All four: S2E_ERR_ARG (s2e_grad_guard_workspace_bytes: 0) on a null pointer, a misaligned arena, n <= 0 (s2e_grad_guard: also
+ * n >= 2^31 - 1) or a workspace that is too small, before any launch. */
+size_t s2e_grad_guard_workspace_bytes(long n);
+int s2e_grad_guard(const float* g, long n, const float* hyper, float* guard, int* first_bad, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int s2e_adam_flat_guarded(float* p, const float* g, float* m, float* v, long n, float* hyper, const float* guard, void* stream);
+int s2e_adam_flat_ema_guarded(float* p, const float* g, float* m, float* v, float* ema, long n, float* hyper,
+                              const float* ema_hyper, const float* guard, void* stream);
 
 /* ------------------------------------------------------------------ data-parallel gradient exchange (new: the reference is single-GPU;
  * its only multi-GPU hook is the nn.DataParallel wrap of models/networks/__init__.py:46-47)

@@ -19,7 +19,7 @@ ACT_NONE, ACT_LRELU, ACT_TANH = 0, 1, 2
 AUX_NONE, AUX_RELU_MASK, AUX_LRELU_GRAD = 0, 1, 2
 NORM_SPADE_STYLE, NORM_PLAIN_IN, NORM_SPADE_STYLE_BATCH = 0, 1, 2
 NORM_ACCUMULATE_DX = 0x100
-LOSS_NEG_MEAN, LOSS_HINGE_REAL, LOSS_HINGE_FAKE, LOSS_L1 = 0, 1, 2, 3
+LOSS_NEG_MEAN, LOSS_HINGE_REAL, LOSS_HINGE_FAKE, LOSS_L1, LOSS_L1_NANGRAD = 0, 1, 2, 3, 4
 
 
 class ConvDesc(C.Structure):
@@ -186,6 +186,10 @@ SIGNATURES = {
     's2e_fc_head_bwd': [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     's2e_adam_flat': [_vp, _vp, _vp, _vp, _l, _vp, _vp],
     's2e_adam_flat_ema': [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp],
+    's2e_grad_guard_workspace_bytes': [_l],
+    's2e_grad_guard': [_vp, _l, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
+    's2e_adam_flat_guarded': [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp],
+    's2e_adam_flat_ema_guarded': [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp],
     's2e_shard_sum': [_i, _vp, _vp, _i, _l, _vp],
     's2e_resize_bicubic_u8': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     's2e_resize_nearest_u8': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],

@@ -62,7 +62,9 @@ class NLayerDiscriminator(BaseNetwork):
             if feat_terms is None:
                 feats.append(h)
                 return h
-            h, term = ops.feat_tap(h, feat_lambda / (h.numel() // 2), pooled=True)     # (the terms are stacked and summed by the caller)
+            # (the terms are stacked and summed by the caller; under --skip_nonfinite_grads a NaN difference gives a NaN gradient, so
+            # that a corrupt real image reaches the generator's gradient guard: DESIGN 3.13)
+            h, term = ops.feat_tap(h, feat_lambda / (h.numel() // 2), pooled=True, nan_grad=bool(getattr(self.opt, 'skip_nonfinite_grads', False)))
             feat_terms.append(term)
             feats.append(h.detach())
             return h

@@ -3,7 +3,7 @@ metric kernels."""
 import torch
 
 from .. import _lib as L
-from .._lib import LOSS_L1
+from .._lib import LOSS_L1, LOSS_L1_NANGRAD
 from .core import LaunchProfiler, ZeroPool, _dt, _need, _p, _single_channel, _stream
 from .conv import _live_tail_buffer
 
@@ -130,10 +130,12 @@ class FeatTapFn(torch.autograd.Function):
     Why not slice-then-loss: the slice's backward materialises a zero (2N,...) tensor, copies the half in and
     autograd then ADDS it to the gradient arriving from the next layer -- three passes over every feature map
     (~0.65 ms per G step).  Here the next layer's gradient arrives first (this node sits on the only path to
-    it) and the L1 gradient is accumulated into its fake half in place by s2e_loss_grad(accumulate=1)."""
+    it) and the L1 gradient is accumulated into its fake half in place by s2e_loss_grad(accumulate=1).
+    nan_grad: the gradient of a NaN difference is NaN (LOSS_L1_NANGRAD) and not torch's sign(NaN) = 0: for use under the gradient
+    guard, which can only skip a step whose non-finite features reached the gradient arena.  Finite inputs give the same bits."""
 
     @staticmethod
-    def forward(ctx, h, scale, pooled=False):
+    def forward(ctx, h, scale, pooled=False, nan_grad=False):
         _need(h)
         n = h.shape[0] // 2
         a, b = h[:n], h[n:]
@@ -141,6 +143,7 @@ class FeatTapFn(torch.autograd.Function):
         L.check(L.lib().s2e_loss_reduce(_dt(h), LOSS_L1, _p(a), _p(b), a.numel(), float(scale), _p(out), _stream()),
                 's2e_loss_reduce')
         ctx.scale = float(scale)
+        ctx.grad_mode = LOSS_L1_NANGRAD if nan_grad else LOSS_L1
         ctx.save_for_backward(h)
         ctx.set_materialize_grads(False)
         return h.view_as(h), out
@@ -150,21 +153,21 @@ class FeatTapFn(torch.autograd.Function):
         h, = ctx.saved_tensors
         n = h.shape[0] // 2
         if gloss is None:
-            return gh, None, None
+            return gh, None, None, None
         if gh is None:
             gh = torch.zeros_like(h)
         elif not gh.is_contiguous():
             gh = gh.contiguous()
         a, b, ga = h[:n], h[n:], gh[:n]
         gs = gloss.detach().float().contiguous()
-        L.check(L.lib().s2e_loss_grad(_dt(h), LOSS_L1, _p(a), _p(b), a.numel(), ctx.scale, _p(gs), _p(ga), 1, _stream()),
+        L.check(L.lib().s2e_loss_grad(_dt(h), ctx.grad_mode, _p(a), _p(b), a.numel(), ctx.scale, _p(gs), _p(ga), 1, _stream()),
                 's2e_loss_grad')
-        return gh, None, None
+        return gh, None, None, None
 
 
-def feat_tap(h, scale, pooled=False):
+def feat_tap(h, scale, pooled=False, nan_grad=False):
     """-> (h, term): see FeatTapFn.  pooled: as in loss_sum."""
-    return FeatTapFn.apply(h, scale, pooled)
+    return FeatTapFn.apply(h, scale, pooled, nan_grad)
 
 
 # ------------------------------------------------------------------------------ optimizer
@@ -189,6 +192,50 @@ def adam_flat_ema_step(p, g, m, v, ema, hyper, ema_hyper, skips_m=False):
         L.lib().s2e_adam_flat_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), _p(ema_hyper), _stream()), 's2e_adam_flat_ema'),
         # adam_flat_step's bytes + the average's own read and write: 7 floats per parameter without the first moment, 9 with it
         nbytes=float((7 if skips_m else 9) * 4 * p.numel()))
+
+
+def grad_guard_workspace(n, device):
+    """The workspace s2e_grad_guard needs for an arena of n elements: per-block {fp64 sum, first index} records."""
+    return torch.empty(int(L.lib().s2e_grad_guard_workspace_bytes(int(n))) // 8, dtype=torch.float64, device=device)
+
+
+def guard_coefficient(norm, max_norm, has_nonfinite=False, skip_nonfinite=False):
+    """The rule s2e_grad_guard applies, restated on the host (the kernel is the implementation, this is its documentation): the
+    coefficient the guarded Adam step multiplies the gradient by.  norm: |grad_scale| * sqrt(sum g^2) over the finite elements."""
+    if has_nonfinite:
+        return 0.0 if skip_nonfinite else float('nan')         # a skipped step / the unguarded behaviour
+    if max_norm > 0:
+        return min(1.0, float(max_norm) / (float(norm) + 1e-6))  # torch.nn.utils.clip_grad_norm_, norm_type = 2
+    return 1.0
+
+
+def grad_guard(g, hyper, guard, first_bad, workspace):
+    """Examine the gradient arena g (flat fp32) and write the guard record: guard (8 fp32, DEVICE) = {max_norm, skip_nonfinite | norm,
+    coefficient, skipped, clipped, consecutive skips, 0}, first_bad (1 int32, DEVICE) = index of the first non-finite element or -1
+    (seg2eye_hip.h: s2e_grad_guard).  Two launches, no atomics, no synchronisation; hyper[5] (grad_scale) enters the norm."""
+    _need(g, hyper, guard, first_bad, workspace)
+    LaunchProfiler.run('adam', 0.0, lambda: L.check(
+        L.lib().s2e_grad_guard(_p(g), g.numel(), _p(hyper), _p(guard), _p(first_bad), _p(workspace),
+                               workspace.numel() * workspace.element_size(), _stream()), 's2e_grad_guard'),
+        nbytes=float(4 * g.numel()))                             # the guard reads g once
+
+
+def adam_flat_guarded_step(p, g, m, v, hyper, guard, skips_m=False):
+    """adam_flat_step under the guard record grad_guard wrote: coefficient guard[3] == 0 leaves p, m, v and the step count alone,
+    any other multiplies grad_scale (1 gives adam_flat_step's bits)."""
+    _need(p, g, m, v, hyper, guard)
+    LaunchProfiler.run('adam', 0.0, lambda: L.check(
+        L.lib().s2e_adam_flat_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(guard), _stream()), 's2e_adam_flat_guarded'),
+        nbytes=float((5 if skips_m else 7) * 4 * p.numel()))     # (adam_flat_step's; a skipped step moves nothing)
+
+
+def adam_flat_ema_guarded_step(p, g, m, v, ema, hyper, ema_hyper, guard, skips_m=False):
+    """adam_flat_ema_step under the guard record: a skipped step leaves the average alone too."""
+    _need(p, g, m, v, ema, hyper, ema_hyper, guard)
+    LaunchProfiler.run('adam', 0.0, lambda: L.check(
+        L.lib().s2e_adam_flat_ema_guarded(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), _p(ema_hyper), _p(guard), _stream()),
+        's2e_adam_flat_ema_guarded'),
+        nbytes=float((7 if skips_m else 9) * 4 * p.numel()))     # (adam_flat_ema_step's)
 
 
 def openeds_error(produced, target):

@@ -2,6 +2,7 @@
 so the optimizer step is a single HIP launch (s2e_adam_flat) and the data-parallel gradient exchange is
 an all-reduce over contiguous slices with no packing.  Mirrors torch.optim.Adam as the reference
 configures it (models/pix2pix_model.py:92-110): TTUR betas (0, 0.9), eps 1e-8, weight_decay 0."""
+import bisect
 import os
 
 import torch
@@ -26,7 +27,7 @@ def _arena_view(flat, off, p, cl):
 
 class FlatAdam:
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, never_updated=(), channels_last=None,
-                 ema_decay=None, ema_start=0):
+                 ema_decay=None, ema_start=0, clip_norm=None, skip_nonfinite=False):
         """channels_last (default: on, S2E_WEIGHTS_CL): a conv weight whose input-channel count is a multiple of 8 is stored
         [Cout][KH][KW][Cin] in the arenas -- the order the MFMA kernels' packed matrices and weight gradients use -- and exposed
         as a (Cout, Cin, KH, KW) view: state_dict values, shapes and every element-wise use are unchanged, while the
@@ -38,7 +39,12 @@ class FlatAdam:
         the parameters in a fifth arena `flat_ema`, updated by the Adam launch itself (s2e_adam_flat_ema: 8 more bytes per
         parameter, no second pass over p).  It starts as a copy of flat_p -- so the never-updated tail holds its parameters from
         the first moment on --; step t (1-based, this optimizer's own count) copies p into it while t <= ema_start and averages
-        afterwards, ema = decay * ema + (1 - decay) * p.  `ema_views()` are the per-parameter views."""
+        afterwards, ema = decay * ema + (1 - decay) * p.  `ema_views()` are the per-parameter views.
+        clip_norm / skip_nonfinite (default None / False: off, nothing is allocated and step() is the launch it is without them): the
+        gradient guard.  step() first examines the active gradient arena (ops.grad_guard: its norm times grad_scale, the first non-finite
+        element) and the Adam launch then reads the coefficient from device memory: 0 -- skip_nonfinite and a non-finite element -- leaves
+        parameters, moments, the average and the step count alone; min(1, clip_norm / (norm + 1e-6)) scales the gradient as
+        torch.nn.utils.clip_grad_norm_ would.  No host round trip per step: `guard_stats()` reads the record when asked."""
         skip = {id(p) for p in never_updated}
         seen, plist = set(), []
         for p in list(params) + [p for p in never_updated]:
@@ -97,10 +103,45 @@ class FlatAdam:
             self.flat_ema = self.flat_p.clone()
             # device-resident {decay, start_step}: read by the launch, like `hyper`
             self.ema_hyper = torch.tensor([self.ema_decay, float(self.ema_start)], dtype=torch.float32, device=dev)
+        clip = 0.0 if clip_norm is None else float(clip_norm)
+        if clip < 0.0:
+            raise ValueError('FlatAdam: clip_norm must not be negative')
+        if clip > 0.0 or skip_nonfinite:
+            self.clip_norm, self.skip_nonfinite = clip, bool(skip_nonfinite)
+            # device-resident guard record (seg2eye_hip.h: s2e_grad_guard): {max_norm, skip_nonfinite | norm, coefficient, skipped,
+            # clipped, consecutive skips, 0}, the index of the first non-finite element, and the reduction's workspace
+            self.guard = torch.tensor([clip, float(self.skip_nonfinite), 0.0, 1.0, 0.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=dev)
+            self.first_bad = torch.full((1,), -1, dtype=torch.int32, device=dev)
+            self.guard_ws = ops.grad_guard_workspace(self.numel_active, dev)
+            self._clip_host = clip
 
     @property
     def has_ema(self):
         return 'flat_ema' in self.__dict__
+
+    @property
+    def has_guard(self):
+        return 'guard' in self.__dict__
+
+    def guard_stats(self):
+        """The guard record of the last step, by ONE small device-to-host copy (it waits for the stream): {'norm': the gradient's
+        norm times grad_scale, 'coef': the coefficient applied (0: skipped), 'skipped' / 'clipped': steps so far, 'consecutive':
+        skipped steps in a row, 'first_bad': arena index of the first non-finite element or -1}.  Also sets `step_count` to the
+        device's count of COMPLETED steps (hyper[4]): a skipped step is not a step, and only the device knows which were."""
+        if not self.has_guard:
+            raise RuntimeError('FlatAdam.guard_stats: this optimizer has no gradient guard (clip_norm=None, skip_nonfinite=False)')
+        rec = torch.cat([self.guard, self.first_bad.view(torch.float32), self.hyper[4:5]]).cpu()
+        self.step_count = int(rec[9])
+        return {'norm': float(rec[2]), 'coef': float(rec[3]), 'skipped': int(rec[4]), 'clipped': int(rec[5]), 'consecutive': int(rec[6]),
+                'first_bad': int(rec[8:9].view(torch.int32))}
+
+    def param_at(self, flat_index):
+        """Position in `params` of the parameter that owns arena element `flat_index` (guard_stats()['first_bad']); None for an
+        element of an alignment gap."""
+        if not 0 <= flat_index < self.numel:
+            raise IndexError('FlatAdam.param_at: %d is outside the arena of %d elements' % (flat_index, self.numel))
+        i = bisect.bisect_right(self.offsets, flat_index) - 1
+        return i if flat_index < self.offsets[i] + self.params[i].numel() else None
 
     def ema_views(self):
         """The averaged value of every parameter, in `params` order: views into flat_ema of the parameter's logical shape and --
@@ -137,12 +178,15 @@ class FlatAdam:
             p.grad = want
 
     def sync_hyper(self, grad_scale=1.0):
-        """Push lr / grad_scale to the device only when they changed (never inside a graph)."""
+        """Push lr / grad_scale -- and a changed `clip_norm` -- to the device only when they changed (never inside a graph)."""
         cur = (float(self.param_groups[0]['lr']), float(grad_scale))
         if cur != self._hyper_host:
             self.hyper[0:1].fill_(cur[0])
             self.hyper[5:6].fill_(cur[1])
             self._hyper_host = cur
+        if self.has_guard and float(self.clip_norm) != self._clip_host:
+            self.guard[0:1].fill_(float(self.clip_norm))
+            self._clip_host = float(self.clip_norm)
 
     def step(self, grad_scale=1.0):
         self.rebind_grads()
@@ -150,7 +194,16 @@ class FlatAdam:
         self.step_count += 1
         k = self.numel_active
         skips_m = self.betas[0] == 0.0 and self._wd == 0.0
-        if self.has_ema:
+        if self.has_guard:
+            # (step_count counts this step as done; guard_stats() corrects it when the device skipped some)
+            ops.grad_guard(self.flat_g[:k], self.hyper, self.guard, self.first_bad, self.guard_ws)
+            if self.has_ema:
+                ops.adam_flat_ema_guarded_step(self.flat_p[:k], self.flat_g[:k], self.flat_m[:k], self.flat_v[:k], self.flat_ema[:k],
+                                               self.hyper, self.ema_hyper, self.guard, skips_m=skips_m)
+            else:
+                ops.adam_flat_guarded_step(self.flat_p[:k], self.flat_g[:k], self.flat_m[:k], self.flat_v[:k], self.hyper, self.guard,
+                                           skips_m=skips_m)
+        elif self.has_ema:
             ops.adam_flat_ema_step(self.flat_p[:k], self.flat_g[:k], self.flat_m[:k], self.flat_v[:k], self.flat_ema[:k], self.hyper,
                                    self.ema_hyper, skips_m=skips_m)
         else:
@@ -164,27 +217,40 @@ class FlatAdam:
         return {'offsets': list(self.offsets), 'channels_last': [bool(c) for c in self.cl],
                 'shapes': [tuple(int(d) for d in p.shape) for p in self.params]}
 
-    def _first_moment(self):
+    def _first_moment(self, formed=None):
         """The first-moment arena as torch.optim.Adam would hold it.  With beta1 == 0 and no weight decay (the reference's TTUR
         setting) s2e_adam_flat does not touch flat_m -- m_t = g_t * grad_scale exactly, whatever m was -- so it is formed here from
         the gradient arena when that still holds the gradients of the last step (between step() and the next zero_grad()).
-        (With beta1 == 0 the saved m never influences a resumed run: the next step overwrites it.)"""
-        if self.betas[0] == 0.0 and self._wd == 0.0 and self.step_count > 0 and self.__dict__.get('_g_is_last_step', False):
+        (With beta1 == 0 the saved m never influences a resumed run: the next step overwrites it.)
+        Under the gradient guard the launch consumed g * (grad_scale * c), c the guard's coefficient -- formed here by the kernel's
+        own fp32 multiply, on the device -- and a SKIPPED last step consumed nothing: m is then not formed (state_dict: m_valid).
+        formed: _m_from_last_step()'s answer when the caller already has it (it costs a read of the guard record)."""
+        if self.betas[0] == 0.0 and self._wd == 0.0 and self.step_count > 0 and (self._m_from_last_step() if formed is None else formed):
             k = self.numel_active
             m = self.flat_m.clone()
-            m[:k] = self.flat_g[:k] * self._hyper_host[1]
+            m[:k] = self.flat_g[:k] * (self.hyper[5] * self.guard[3] if self.has_guard else self._hyper_host[1])
             return m
         return self.flat_m
 
+    def _m_from_last_step(self, stats=None):
+        """The gradient arena still holds the gradient the last step consumed: between step() and the next zero_grad(), and -- under
+        the guard -- only when that step was not skipped (`stats`: a guard_stats() record just read, else one is read here)."""
+        if not self.__dict__.get('_g_is_last_step', False):
+            return False
+        return not self.has_guard or (stats or self.guard_stats())['coef'] != 0.0
+
     def state_dict(self):
         """`m_valid`: False when the saved first moment is NOT the optimizer's -- beta1 == 0 / no weight decay steps leave
-        flat_m untouched, and outside the window between step() and the next zero_grad() the gradient it would be formed from is
-        gone.  Harmless for a resume at beta1 == 0 (the next step overwrites m); a run resumed with another beta1 (--no_TTUR: 0.5)
+        flat_m untouched, and outside the window between step() and the next zero_grad() -- or after a step the gradient guard
+        skipped -- the gradient it would be formed from is gone.  Harmless for a resume at beta1 == 0 (the next step overwrites m); a run resumed with another beta1 (--no_TTUR: 0.5)
         must not trust an invalid m: load_state_dict then starts it from zeros.
         With an average (ema_decay) the state also carries `ema`, the flat_ema arena in the layout of m and v."""
+        # ONE read of the guard record: step_count then follows the device (skipped steps are not steps) and the coefficient says
+        # whether the last step consumed the gradient arena
+        formed = self._m_from_last_step(self.guard_stats() if self.has_guard else None)
         skipped = self.betas[0] == 0.0 and self._wd == 0.0 and self.step_count > 0
-        valid = (not skipped) or bool(self.__dict__.get('_g_is_last_step', False))
-        sd = {'step': self.step_count, 'm': self._first_moment(), 'v': self.flat_v, 'lr': self.param_groups[0]['lr'], 'layout': self._layout(),
+        valid = (not skipped) or formed
+        sd = {'step': self.step_count, 'm': self._first_moment(formed), 'v': self.flat_v, 'lr': self.param_groups[0]['lr'], 'layout': self._layout(),
               'm_valid': valid}
         if self.has_ema:
             sd['ema'] = self.flat_ema                        # (same layout as m and v; absent without an average)

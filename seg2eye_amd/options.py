@@ -37,6 +37,9 @@ _DEFAULTS = dict(
     use_ema=False,             # test.py: load <epoch>_net_{G,E}_ema.pth instead of the live weights
     device_preprocess=False,   # openeds: the dataset hands out raw frames; resize / flip / normalise run on the GPU (ops.preprocess)
     visuals=False,             # train.py: loss_log.txt + side-by-side validation panels (seg2eye_amd/visualizer.py)
+    grad_clip_norm=0.0,        # > 0: each optimizer's gradient is clipped to this global norm inside the Adam step (optim.FlatAdam); 0 = off
+    skip_nonfinite_grads=False,  # a step whose gradient holds an inf / NaN changes nothing: parameters, moments, average, step count
+    max_consecutive_skips=100,  # train.py stops after this many skipped steps in a row (0 = never); a policy default, not a measurement
 )
 
 
@@ -118,6 +121,8 @@ _CLI_TRAIN_BUILD = [
     ('ema_decay', _F, 0.0, None), ('ema_start', _I, 0, None),        # averaged generator weights; 0 = off
     # the visualiser: loss_log.txt, PNG panels at every quick validation, `visualisation` in the error log; off = none of it
     ('visuals', 'flag', False, None),
+    # the gradient guard: clip by global norm, skip steps with non-finite gradients; off = the Adam step as it was
+    ('grad_clip_norm', _F, 0.0, None), ('skip_nonfinite_grads', 'flag', False, None), ('max_consecutive_skips', _I, 100, None),
 ]
 _CLI_TEST_BUILD = [
     ('use_ema', 'flag', False, None),                                 # score / generate with the averaged weights' checkpoint files
@@ -168,6 +173,8 @@ def parse(argv=None, is_train=True):
                          "that dataset's host transform on the GPU" % (opt.dataset_mode, opt.preprocess_mode))
     if not 0.0 <= opt.ema_decay < 1.0 or opt.ema_start < 0:
         raise ValueError('--ema_decay must lie in [0, 1) (0 = off) and --ema_start must not be negative')
+    if not opt.grad_clip_norm >= 0.0 or opt.max_consecutive_skips < 0:
+        raise ValueError('--grad_clip_norm (0 = off) and --max_consecutive_skips (0 = never stop) must not be negative')
     # train.py replays each step as hipGraphs BY DEFAULT (round 4: the replayed step is 15 % faster than ~900 individual launches
     # on a slow host, and the overlapped gradient exchange replays graph segments); --no_hip_graphs launches eagerly.  A failed
     # capture falls back to eager launches by itself, a batch of another shape runs eagerly for that step.  (--hip_graphs is

@@ -117,8 +117,12 @@ class Pix2PixModel(nn.Module):
             beta1, beta2, G_lr, D_lr = 0.0, 0.9, opt.lr / 2, opt.lr * 2
         # --ema_decay: the average of netG + netE (only: D keeps none) lives in optimizer G's fifth arena, kept by its Adam launch
         ema = float(getattr(opt, 'ema_decay', 0.0) or 0.0)
+        # --grad_clip_norm / --skip_nonfinite_grads: the gradient guard of BOTH optimizers, each over its own arena (as two
+        # clip_grad_norm_ calls would); off = FlatAdam allocates nothing and launches what it always did
+        clip = float(getattr(opt, 'grad_clip_norm', 0.0) or 0.0)
+        guard = dict(clip_norm=clip if clip > 0 else None, skip_nonfinite=bool(getattr(opt, 'skip_nonfinite_grads', False)))
         optimizer_G = FlatAdam(G_params, lr=G_lr, betas=(beta1, beta2), weight_decay=opt.weight_decay, never_updated=dead,
-                               ema_decay=ema if ema > 0 else None, ema_start=int(getattr(opt, 'ema_start', 0) or 0))
+                               ema_decay=ema if ema > 0 else None, ema_start=int(getattr(opt, 'ema_start', 0) or 0), **guard)
         bounds, k = [0], 0
         for cnt in self._arena_groups_G:
             k += cnt
@@ -126,7 +130,7 @@ class Pix2PixModel(nn.Module):
         bounds[-1] = optimizer_G.numel                              # (the never-updated tail rides with the last group)
         self.grad_groups_G = [(a, b) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
         optimizer_D = FlatAdam(list(self.netD.parameters()), lr=D_lr, betas=(beta1, beta2),
-                               weight_decay=opt.weight_decay) if opt.isTrain else None
+                               weight_decay=opt.weight_decay, **guard) if opt.isTrain else None
         return optimizer_G, optimizer_D
 
     def save(self, epoch, ema_of=None):

@@ -328,6 +328,31 @@ class Pix2PixTrainer:
     def save(self, epoch):
         self.pix2pix_model_on_one_gpu.save(epoch, ema_of=self._ema_of() if self.has_ema else None)
 
+    # ---- the gradient guard (--grad_clip_norm / --skip_nonfinite_grads) -----------------------
+    @property
+    def has_guard(self):
+        return bool(self.opt.isTrain and self.optimizer_G.has_guard)
+
+    def grad_health(self):
+        """{'G': optimizer_G.guard_stats(), 'D': optimizer_D.guard_stats()} plus, per optimizer, 'param': the state-dict name of
+        the parameter that owns the first non-finite gradient element (e.g. 'netG.up_0.conv_1.weight_orig'; None when the last
+        gradient was finite or the element lies in an alignment gap).  Two small device-to-host copies: for the progress line, not
+        for every step.  The guard itself sits inside FlatAdam.step(), after the gradient exchange."""
+        if not self.has_guard:
+            raise RuntimeError('grad_health: this trainer has no gradient guard (--grad_clip_norm 0, no --skip_nonfinite_grads)')
+        names = self.__dict__.get('_param_names')
+        if names is None:
+            m = self.pix2pix_model
+            names = self.__dict__['_param_names'] = {id(p): '%s.%s' % (tag, k) for tag, net in (('netG', m.netG), ('netE', m.netE), ('netD', m.netD))
+                                                     for k, p in net.named_parameters()}
+        out = {}
+        for tag, o in (('G', self.optimizer_G), ('D', self.optimizer_D)):
+            st = o.guard_stats()
+            i = o.param_at(st['first_bad']) if st['first_bad'] >= 0 else None
+            st['param'] = names.get(id(o.params[i])) if i is not None else None
+            out[tag] = st
+        return out
+
     # ---- averaged generator weights (--ema_decay, DESIGN 3.10) ------------------------------------------
     @property
     def has_ema(self):

@@ -11,6 +11,10 @@ generated image | error heat map, built on the GPU: DESIGN 3.12) as PNG files un
 gains the `visualisation` dataset.  Not carried over (out of scope): TF logging / HTML pages, source-tree copy.
 Data: `--dataset_mode synthetic` (default) or `openeds` (an H5 file at `--dataroot`; needs h5py); with `--device_preprocess` the
 OpenEDS frames are resized, flipped and normalised on the GPU, bit-identical to the host transform.
+`--grad_clip_norm F` clips each optimizer's gradient to the global norm F and `--skip_nonfinite_grads` makes a step whose gradient
+holds an inf / NaN change nothing, both inside the Adam step and without a host round trip; the progress line then
+carries `grad_norm/{G,D}` and `grad_skipped/{G,D}`, and `--max_consecutive_skips` skipped steps in a row end the run with the
+offending parameter's name -- `latest` is left as it was.
 
     python train.py --name run1 --batchSize 8 --aspect_ratio 1.0 --niter 1 --niter_decay 0
     python train.py --name run1 --batchSize 8 --aspect_ratio 1.0 --display_freq 1000 --visuals     # + loss_log.txt and PNG panels
@@ -30,6 +34,10 @@ from seg2eye_amd.options import parse
 from seg2eye_amd.pix2pix_trainer import Pix2PixTrainer
 from seg2eye_amd.tester import Tester
 from seg2eye_amd.visualizer import Visualizer
+
+
+class NonFiniteGradients(RuntimeError):
+    """--max_consecutive_skips steps in a row were skipped for non-finite gradients: the run ends and `latest` stays as it is."""
 
 
 class TrainingRun:
@@ -54,13 +62,32 @@ class TrainingRun:
         self.duties = ((c.needs_printing, self.report), (c.needs_displaying, self.quick_validation),
                        (c.needs_saving, self.save_latest), (c.needs_full_validation, self.full_validation))
         self.epoch = c.current_epoch
+        self._skips_seen = set()                                 # optimizers whose first skip has been announced
 
     # ---- duties
+    def grad_health(self):
+        """The guard's figures for the progress line -- read at --print_freq cadence only: no step waits for the host -- and the run's
+        policy: announce each optimizer's first skip seen (with the parameter's name when the record still holds it), stop at --max_consecutive_skips.  Every rank decides alike (the guard's
+        decision is a function of the exchanged gradient)."""
+        health = self.trainer.grad_health()
+        for tag, st in health.items():
+            # (the record names the element only while the LAST step was a bad one: a clean step resets first_bad to -1)
+            where = ' in %s (arena element %d)' % (st['param'], st['first_bad']) if st['first_bad'] >= 0 else ''
+            if st['skipped'] and tag not in self._skips_seen:
+                self._skips_seen.add(tag)
+                if not self.rank:
+                    print('optimizer %s skipped %d step(s) so far: non-finite gradient%s' % (tag, st['skipped'], where), flush=True)
+            if 0 < self.opt.max_consecutive_skips <= st['consecutive']:
+                raise NonFiniteGradients('optimizer %s skipped %d steps in a row (--max_consecutive_skips %d): non-finite gradient%s'
+                                         % (tag, st['consecutive'], self.opt.max_consecutive_skips, where))
+        return {'grad_%s/%s' % (k, tag): torch.tensor(float(health[tag][k])) for k in ('norm', 'skipped') for tag in ('G', 'D')}
+
     def report(self):
+        health = self.grad_health() if self.trainer.has_guard else {}
         if self.rank:
             return
         c = self.counter
-        losses = self.trainer.get_latest_losses(include_log_losses=True)
+        losses = {**self.trainer.get_latest_losses(include_log_losses=True), **health}
         if self.visualizer is not None:
             self.visualizer.print_current_errors(self.epoch, c.total_steps_so_far, losses, c.time_per_iter)
             return self.visualizer.plot_current_errors(losses, c.total_steps_so_far)
@@ -123,6 +150,7 @@ class TrainingRun:
             trainer.save(epoch)
 
     def fit(self):
+        keep_latest = False
         try:
             for epoch in self.counter.training_epochs():
                 self.one_epoch(epoch)
@@ -130,8 +158,11 @@ class TrainingRun:
         except (KeyboardInterrupt, SystemExit):
             print('KeyboardInterrupt. Shutting down.')
             print(traceback.format_exc())
+        except NonFiniteGradients:
+            keep_latest = True                                   # the last good checkpoint is worth more than this state
+            raise
         finally:
-            if self.rank == 0:
+            if self.rank == 0 and not keep_latest:
                 print('saving the model before quitting')
                 self.trainer.save('latest')
                 self.counter.record_current_iter()
