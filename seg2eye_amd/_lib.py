@@ -89,112 +89,117 @@ class SnGradJob(C.Structure):
 
 
 _vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
-# name -> argtypes; every entry returns int except the two noted below.  Must list EVERY symbol
-# declared in include/seg2eye_hip.h (tests/test_abi.py checks header <-> table <-> .so).
+# What a function returns, by the kind its table entry names (read from its definition, not from its name):
+#   STATUS  int: 0, or a negative S2E_ERR_* with s2e_last_error() set      COUNT  long: >= 0, or a negative S2E_ERR_* (no error text)
+#   SIZE    size_t                    VALUE  a plain int answer (*_supported, *_kind, *_slots, *_pad, ...)                  TEXT  const char*
+STATUS, COUNT, SIZE, VALUE, TEXT = 'status', 'count', 'size', 'value', 'text'
+_RESTYPE = {STATUS: C.c_int, COUNT: C.c_long, SIZE: C.c_size_t, VALUE: C.c_int, TEXT: C.c_char_p}
+# name -> (kind, argtypes).  Must list EVERY symbol declared in include/seg2eye_hip.h, as the header declares it
+# (tests/test_abi_and_host.py compares names, arguments, return types and the job structures: header <-> table <-> .so).
 SIGNATURES = {
-    's2e_version': [],
-    's2e_last_error': [],
-    's2e_conv_cout_pad': [_i],
-    's2e_conv_k_pad': [_i, _i],
-    's2e_pack_conv_weight': [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    's2e_sn_block_shape': [_i, _vp, _vp],
-    's2e_sn_chain_max_cols': [],
-    's2e_sn_power_iteration': [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, _i, _i, _f, _i, _vp],
-    's2e_sn_weight_grad': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    's2e_grad_block_map': [_vp, _i, _vp],
-    's2e_sngrad_block_map': [_vp, _i, _vp],
-    's2e_sngrad_scratch_floats': [_vp, _i],
-    's2e_sn_grads_inplace': [_vp, _vp, _i, _vp, _vp],
-    's2e_weight_grads_batched': [_vp, _vp, _i, _i, _i, _vp, _vp],
-    's2e_unpack_weight_grad': [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp],
-    's2e_pack_block_map': [_i, _vp, _i, _vp],
-    's2e_pack_conv_weights': [_i, _vp, _vp, _i, _i, _vp, _vp],
-    's2e_conv2d_workspace_bytes': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d_kernel_kind': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d_wgrad_kernel_kind': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d': [_i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, C.c_size_t, _vp],
-    's2e_conv2d_plane_supported': [_i, C.POINTER(ConvDesc)],
-    's2e_conv_plane_weight_elems': [C.POINTER(ConvDesc)],
-    's2e_conv2d_plane': [_i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp],
-    's2e_conv2d_stats_slots': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d_stats': [_i, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, _vp],
-    's2e_in_stats_from_partials': [_vp, _i, _i, _i, _i, _f, _vp, _vp, _vp],
-    's2e_label_rect_lists_bwd': [_vp, _i, _i, _i, _vp, _vp, _vp, _vp],
-    's2e_conv2d_rects_supported': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d_rects': [_i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, _vp, _vp],
-    's2e_conv2d_wgrad_rects_workspace_bytes': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d_wgrad_rects': [_i, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, _vp, _vp, C.c_size_t, _vp],
-    's2e_spade_uniform_sums': [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    's2e_spade_uniform_grads': [_vp, _i, _vp],
-    's2e_conv2d_wgrad_workspace_bytes': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d_wgrad': [_i, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, C.c_size_t, _vp],
-    's2e_conv2d_wgrad_multi_supported': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d_wgrad_multi_kind': [_i, C.POINTER(ConvDesc)],
-    's2e_conv2d_wgrad_multi_workspace_bytes': [_i, _vp, _i],
-    's2e_conv2d_wgrad_multi': [_i, _vp, _i, _vp, C.c_size_t, _vp],
-    's2e_in_stats_workspace_bytes': [_i, _i, _i, _i],
-    's2e_modulate_bwd_workspace_bytes': [_i, _i, _i, _i],
-    's2e_instance_norm_fwd': [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp],
-    's2e_instance_norm_bwd': [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
-    's2e_in_stats_counters': [_i, _i, _i, _i],
-    's2e_in_stats': [_i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp],
-    's2e_modulate_fwd': [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    's2e_modulate_bwd': [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    's2e_modulate_bwd_gamma': [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    's2e_modulate_bwd_staged': [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp],
-    's2e_modulate_bwd_relay': [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp],
-    's2e_spade_conv_modulate_rect': [_i, _i, _i, _i, _i, _i, _i, _vp, _vp],
-    's2e_label_rect_classify': [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp],
-    's2e_spade_conv_modulate_sparse': [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp],
-    's2e_spade_class_table': [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
-    's2e_spade_modulate_uniform': [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    's2e_spade_conv_modulate_supported': [_i, _i, _i, _i, _i, _i, _i],
-    's2e_spade_conv_modulate': [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    's2e_colsum': [_i, _vp, _l, _i, _vp, _vp],
-    's2e_wgrad_c8_batch_supported': [_i, _i, _i, _i],
-    's2e_wgrad_c8_batch_workspace_bytes': [_i, _vp, _i],
-    's2e_wgrad_c8_batch': [_i, _i, _vp, _i, _vp, C.c_size_t, _vp],
-    's2e_wgrad_batch_supported': [_i, _i, _i, _i, _i, _i],
-    's2e_wgrad_batch_workspace_bytes': [],
-    's2e_wgrad_batch': [_i, _vp, _i, _vp, C.c_size_t, _vp],
-    's2e_label_conv_block_map': [_i, _vp, _i, _i, _vp],
-    's2e_label_conv3x3_batch': [_i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp],
-    's2e_class_table_block_map': [_vp, _i, _vp],
-    's2e_spade_class_table_batch': [_i, _vp, _vp, _i, _vp, _i, _vp],
-    's2e_label_conv3x3': [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp],
-    's2e_onehot_nhwc': [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
-    's2e_openeds_error': [_i, _vp, _vp, _i, _i, _i, _vp, _vp],
-    's2e_openeds_error_u8': [_vp, _vp, _i, _i, _i, _vp, _vp],
-    's2e_resize_to255': [_i, _vp, _i, _i, _i, _vp, _i, _i, _vp],
-    's2e_bilinear_resize_fwd': [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    's2e_bilinear_resize_bwd': [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp],
-    's2e_upsample2x_fwd': [_i, _vp, _vp, _i, _i, _i, _i, _vp],
-    's2e_upsample2x_bwd': [_i, _vp, _vp, _i, _i, _i, _i, _vp],
-    's2e_avgpool3x3s2_fwd': [_i, _vp, _vp, _i, _i, _i, _i, _vp],
-    's2e_avgpool3x3s2_bwd': [_i, _vp, _vp, _i, _i, _i, _i, _vp],
-    's2e_tanh_bwd': [_i, _vp, _vp, _vp, _l, _vp],
-    's2e_lrelu_bwd': [_i, _vp, _vp, _vp, _l, _vp],
-    's2e_loss_reduce': [_i, _i, _vp, _vp, _l, _f, _vp, _vp],
-    's2e_loss_grad': [_i, _i, _vp, _vp, _l, _f, _vp, _vp, _i, _vp],
-    's2e_style_fc_supported': [_i, _i],
-    's2e_style_fc_bwd_workspace_bytes': [_i, _i, _i],
-    's2e_style_fc_fwd': [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp],
-    's2e_style_fc_bwd': [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, _f, _vp],
-    's2e_fc_head_supported': [_i, _i],
-    's2e_fc_head_fwd_workspace_bytes': [_i, _i, _i, _i],
-    's2e_fc_head_fwd': [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, C.c_size_t, _vp],
-    's2e_fc_head_bwd': [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
-    's2e_adam_flat': [_vp, _vp, _vp, _vp, _l, _vp, _vp],
-    's2e_adam_flat_ema': [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp],
-    's2e_grad_guard_workspace_bytes': [_l],
-    's2e_grad_guard': [_vp, _l, _vp, _vp, _vp, _vp, C.c_size_t, _vp],
-    's2e_adam_flat_guarded': [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp],
-    's2e_adam_flat_ema_guarded': [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp],
-    's2e_shard_sum': [_i, _vp, _vp, _i, _l, _vp],
-    's2e_resize_bicubic_u8': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    's2e_resize_nearest_u8': [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp],
-    's2e_sidebyside_ws_bytes': [_i, _i, _i],
-    's2e_sidebyside_u8': [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _l, _vp, _vp, _vp, _vp],
+    's2e_version': (VALUE, []),
+    's2e_last_error': (TEXT, []),
+    's2e_conv_cout_pad': (VALUE, [_i]),
+    's2e_conv_k_pad': (VALUE, [_i, _i]),
+    's2e_pack_conv_weight': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_sn_block_shape': (STATUS, [_i, _vp, _vp]),
+    's2e_sn_chain_max_cols': (VALUE, []),
+    's2e_sn_power_iteration': (STATUS, [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, _i, _i, _f, _i, _vp]),
+    's2e_sn_weight_grad': (STATUS, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_grad_block_map': (COUNT, [_vp, _i, _vp]),
+    's2e_sngrad_block_map': (COUNT, [_vp, _i, _vp]),
+    's2e_sngrad_scratch_floats': (COUNT, [_vp, _i]),
+    's2e_sn_grads_inplace': (STATUS, [_vp, _vp, _i, _vp, _vp]),
+    's2e_weight_grads_batched': (STATUS, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    's2e_unpack_weight_grad': (STATUS, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_pack_block_map': (COUNT, [_i, _vp, _i, _vp]),
+    's2e_pack_conv_weights': (STATUS, [_i, _vp, _vp, _i, _i, _vp, _vp]),
+    's2e_conv2d_workspace_bytes': (SIZE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d_kernel_kind': (VALUE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d_wgrad_kernel_kind': (VALUE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, C.c_size_t, _vp]),
+    's2e_conv2d_plane_supported': (VALUE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv_plane_weight_elems': (SIZE, [C.POINTER(ConvDesc)]),
+    's2e_conv2d_plane': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp]),
+    's2e_conv2d_stats_slots': (VALUE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d_stats': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, _vp]),
+    's2e_in_stats_from_partials': (STATUS, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _vp]),
+    's2e_label_rect_lists_bwd': (STATUS, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    's2e_conv2d_rects_supported': (VALUE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d_rects': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, _vp, _vp]),
+    's2e_conv2d_wgrad_rects_workspace_bytes': (SIZE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d_wgrad_rects': (STATUS, [_i, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, _vp, _vp, C.c_size_t, _vp]),
+    's2e_spade_uniform_sums': (STATUS, [_i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    's2e_spade_uniform_grads': (STATUS, [_vp, _i, _vp]),
+    's2e_conv2d_wgrad_workspace_bytes': (SIZE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d_wgrad': (STATUS, [_i, _vp, _vp, _vp, _vp, C.POINTER(ConvDesc), _vp, C.c_size_t, _vp]),
+    's2e_conv2d_wgrad_multi_supported': (VALUE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d_wgrad_multi_kind': (VALUE, [_i, C.POINTER(ConvDesc)]),
+    's2e_conv2d_wgrad_multi_workspace_bytes': (SIZE, [_i, _vp, _i]),
+    's2e_conv2d_wgrad_multi': (STATUS, [_i, _vp, _i, _vp, C.c_size_t, _vp]),
+    's2e_in_stats_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_modulate_bwd_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_instance_norm_fwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
+    's2e_instance_norm_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    's2e_in_stats_counters': (VALUE, [_i, _i, _i, _i]),
+    's2e_in_stats': (STATUS, [_i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    's2e_modulate_fwd': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    's2e_modulate_bwd': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    's2e_modulate_bwd_gamma': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    's2e_modulate_bwd_staged': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp]),
+    's2e_modulate_bwd_relay': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp]),
+    's2e_spade_conv_modulate_rect': (VALUE, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    's2e_label_rect_classify': (STATUS, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    's2e_spade_conv_modulate_sparse': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    's2e_spade_class_table': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    's2e_spade_modulate_uniform': (STATUS, [_i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_spade_conv_modulate_supported': (VALUE, [_i, _i, _i, _i, _i, _i, _i]),
+    's2e_spade_conv_modulate': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_colsum': (STATUS, [_i, _vp, _l, _i, _vp, _vp]),
+    's2e_wgrad_c8_batch_supported': (VALUE, [_i, _i, _i, _i]),
+    's2e_wgrad_c8_batch_workspace_bytes': (SIZE, [_i, _vp, _i]),
+    's2e_wgrad_c8_batch': (STATUS, [_i, _i, _vp, _i, _vp, C.c_size_t, _vp]),
+    's2e_wgrad_batch_supported': (VALUE, [_i, _i, _i, _i, _i, _i]),
+    's2e_wgrad_batch_workspace_bytes': (SIZE, []),
+    's2e_wgrad_batch': (STATUS, [_i, _vp, _i, _vp, C.c_size_t, _vp]),
+    's2e_label_conv_block_map': (COUNT, [_i, _vp, _i, _i, _vp]),
+    's2e_label_conv3x3_batch': (STATUS, [_i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    's2e_class_table_block_map': (COUNT, [_vp, _i, _vp]),
+    's2e_spade_class_table_batch': (STATUS, [_i, _vp, _vp, _i, _vp, _i, _vp]),
+    's2e_label_conv3x3': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_onehot_nhwc': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_openeds_error': (STATUS, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    's2e_openeds_error_u8': (STATUS, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    's2e_resize_to255': (STATUS, [_i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    's2e_bilinear_resize_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    's2e_bilinear_resize_bwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    's2e_upsample2x_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    's2e_upsample2x_bwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    's2e_avgpool3x3s2_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    's2e_avgpool3x3s2_bwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),
+    's2e_tanh_bwd': (STATUS, [_i, _vp, _vp, _vp, _l, _vp]),
+    's2e_lrelu_bwd': (STATUS, [_i, _vp, _vp, _vp, _l, _vp]),
+    's2e_loss_reduce': (STATUS, [_i, _i, _vp, _vp, _l, _f, _vp, _vp]),
+    's2e_loss_grad': (STATUS, [_i, _i, _vp, _vp, _l, _f, _vp, _vp, _i, _vp]),
+    's2e_style_fc_supported': (VALUE, [_i, _i]),
+    's2e_style_fc_bwd_workspace_bytes': (SIZE, [_i, _i, _i]),
+    's2e_style_fc_fwd': (STATUS, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp]),
+    's2e_style_fc_bwd': (STATUS, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _i, _i, _i, _f, _vp]),
+    's2e_fc_head_supported': (VALUE, [_i, _i]),
+    's2e_fc_head_fwd_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_fc_head_fwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, C.c_size_t, _vp]),
+    's2e_fc_head_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
+    's2e_adam_flat': (STATUS, [_vp, _vp, _vp, _vp, _l, _vp, _vp]),
+    's2e_adam_flat_ema': (STATUS, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp]),
+    's2e_grad_guard_workspace_bytes': (SIZE, [_l]),
+    's2e_grad_guard': (STATUS, [_vp, _l, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    's2e_adam_flat_guarded': (STATUS, [_vp, _vp, _vp, _vp, _l, _vp, _vp, _vp]),
+    's2e_adam_flat_ema_guarded': (STATUS, [_vp, _vp, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
+    's2e_shard_sum': (STATUS, [_i, _vp, _vp, _i, _l, _vp]),
+    's2e_resize_bicubic_u8': (STATUS, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    's2e_resize_nearest_u8': (STATUS, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    's2e_sidebyside_ws_bytes': (COUNT, [_i, _i, _i]),
+    's2e_sidebyside_u8': (STATUS, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _l, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None
@@ -204,22 +209,27 @@ class Seg2EyeHipError(RuntimeError):
     pass
 
 
+def _bind(errcheck):
+    """A CDLL of the library with every table entry's argtypes / restype set (handles of one library share the dlopen handle
+    and have their own function objects).  errcheck: kind -> ctypes errcheck hook, for the kinds that get one."""
+    if not os.path.exists(LIB_PATH):
+        raise Seg2EyeHipError(
+            'libseg2eye_hip.so not found at %s -- build it with `python -m seg2eye_amd.build` '
+            '(or __graft_entry__.build()).  There is no fallback path.' % LIB_PATH)
+    dll = C.CDLL(LIB_PATH)
+    for name, (kind, argtypes) in SIGNATURES.items():
+        fn = getattr(dll, name)
+        fn.argtypes, fn.restype = argtypes, _RESTYPE[kind]
+        if kind in errcheck:
+            fn.errcheck = errcheck[kind]
+    return dll
+
+
 def lib():
-    """Load (once) and return the CDLL.  Raises if the extension has not been built."""
+    """Load (once) and return the raw CDLL: integers come back as integers.  Raises if the extension has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise Seg2EyeHipError(
-                'libseg2eye_hip.so not found at %s -- build it with `python -m seg2eye_amd.build` '
-                '(or __graft_entry__.build()).  There is no fallback path.' % LIB_PATH)
-        L = C.CDLL(LIB_PATH)
-        for name, argtypes in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.argtypes = argtypes
-            fn.restype = (C.c_char_p if name == 's2e_last_error' else
-                          C.c_size_t if (name.endswith('_workspace_bytes') or name == 's2e_conv_plane_weight_elems') else
-                          C.c_long if name in ('s2e_pack_block_map', 's2e_grad_block_map', 's2e_sngrad_block_map', 's2e_sngrad_scratch_floats', 's2e_label_conv_block_map', 's2e_class_table_block_map', 's2e_sidebyside_ws_bytes') else C.c_int)
-        _lib = L
+        _lib = _bind({})
     return _lib
 
 
@@ -227,3 +237,29 @@ def check(rc, what=''):
     if rc != 0:
         msg = lib().s2e_last_error()
         raise Seg2EyeHipError('%s failed (%d): %s' % (what, rc, msg.decode() if msg else '?'))
+
+
+def _status(rc, func, args):
+    if rc:
+        check(rc, func.__name__)
+    return rc
+
+
+def _count(n, func, args):
+    if n < 0:                                                # (the planners return the code without setting the error text)
+        raise Seg2EyeHipError('%s failed (%d)' % (func.__name__, n))
+    return n
+
+
+class _Checked:
+    """L.call.s2e_x(...): the same symbols with the error handling installed as ctypes' errcheck -- a STATUS entry raises
+    Seg2EyeHipError with the library's message on a non-zero result, a COUNT entry on a negative one; the others are plain.
+    Bound on the first attribute access; after that every function is an entry of the instance dictionary."""
+
+    def __getattr__(self, name):
+        dll = _bind({STATUS: _status, COUNT: _count})
+        self.__dict__.update((n, getattr(dll, n)) for n in SIGNATURES)
+        return getattr(dll, name)
+
+
+call = _Checked()

@@ -168,8 +168,9 @@ class FlatGradSync:
             # ... which adds the P copies in rank order (fp32 accumulation, one rounding for a bf16 payload): one launch on the GPU ...
             if st['recv'].is_cuda:
                 from . import _lib as L
-                L.check(L.lib().s2e_shard_sum(L.S2E_BF16 if self.payload == 'bf16' else L.S2E_F32, st['recv'].data_ptr(), st['sum'].data_ptr(),
-                                              world, shard, torch.cuda.current_stream().cuda_stream), 's2e_shard_sum')
+                from .ops import _dt
+                L.call.s2e_shard_sum(_dt(st['recv']), st['recv'].data_ptr(), st['sum'].data_ptr(),      # (the payload's dtype: bf16, or the arena's fp32)
+                                     world, shard, torch.cuda.current_stream().cuda_stream)
             else:                                            # (CPU arenas: the gloo dry runs of tests/test_distributed_gloo.py)
                 acc = st['recv'].view(world, shard).to(torch.float32).sum(dim=0) if self.payload == 'bf16' else \
                     st['recv'].view(world, shard).sum(dim=0)

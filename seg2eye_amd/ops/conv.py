@@ -1,7 +1,5 @@
 """Convolutions: weight packs, the raw launchers (s2e_conv2d / s2e_conv2d_wgrad), Conv2dFn with its data / weight / bias gradients
 (spectral norm's chain rule included), the live-prefix gate of the G step's discriminator pass, the encoder's FC head."""
-import ctypes as C
-
 import torch
 
 from .. import _lib as L
@@ -19,6 +17,7 @@ PLANE_LAYOUT = 4            # S2E_PACK_PLANE: the weight layout of s2e_conv2d_pl
 def pack_weight(w_oihw, dtype, cin_pad=None, transposed=False, sigma=None, plane=False):
     """OIHW fp32 -> MFMA B-operand matrix in the compute dtype; divided by the device scalar `sigma`
     (spectral norm) on the fly when given.  plane: the PLANE layout (the weight operand of s2e_conv2d_plane: plane_mode())."""
+    dt = _dt(dtype)                                          # (first: before any tensor is inspected or allocated)
     w = w_oihw.detach()
     cout, cin, kh, kw = w.shape
     cin_pad = cin if cin_pad is None else cin_pad
@@ -31,8 +30,8 @@ def pack_weight(w_oihw, dtype, cin_pad=None, transposed=False, sigma=None, plane
         _need(_cl_rows(w) if cl else w, sigma)
         rows = cin if transposed else cout
         out = torch.empty((rows + 63) // 64 * 64, kh * kw * (cout if transposed else cin), dtype=dtype, device=w.device)
-        L.check(L.lib().s2e_pack_conv_weight(L.S2E_BF16, _p(w), _p(out), _p(sigma), cout, cin, kh, kw, cin, int(bool(transposed)) | (2 if cl else 0) | PLANE_LAYOUT,
-                                             _stream()), 's2e_pack_conv_weight')
+        L.call.s2e_pack_conv_weight(dt, _p(w), _p(out), _p(sigma), cout, cin, kh, kw, cin, int(bool(transposed)) | (2 if cl else 0) | PLANE_LAYOUT,
+                                    _stream())
         return out
     # a weight stored channels-last (optim.FlatAdam) is packed from where it lies: rows in, rows out
     cl = w.dtype == torch.float32 and not w.is_contiguous() and _cl_dense(w) and cin_pad == cin and cin % 8 == 0
@@ -40,13 +39,10 @@ def pack_weight(w_oihw, dtype, cin_pad=None, transposed=False, sigma=None, plane
         w = w.float().contiguous()
     _need(_cl_rows(w) if cl else w, sigma)
     transposed = int(bool(transposed)) | (2 if cl else 0)
-    dt = L.S2E_BF16 if dtype == torch.bfloat16 else L.S2E_F32
-    lib = L.lib()
-    rows = lib.s2e_conv_cout_pad(cin_pad if (transposed & 1) else cout)
-    kpad = lib.s2e_conv_k_pad(dt, kh * kw * (cout if (transposed & 1) else cin_pad))
+    rows = L.call.s2e_conv_cout_pad(cin_pad if (transposed & 1) else cout)
+    kpad = L.call.s2e_conv_k_pad(dt, kh * kw * (cout if (transposed & 1) else cin_pad))
     out = torch.empty(rows, kpad, dtype=dtype, device=w.device)
-    L.check(lib.s2e_pack_conv_weight(dt, _p(w), _p(out), _p(sigma), cout, cin, kh, kw, cin_pad, int(transposed), _stream()),
-            's2e_pack_conv_weight')
+    L.call.s2e_pack_conv_weight(dt, _p(w), _p(out), _p(sigma), cout, cin, kh, kw, cin_pad, int(transposed), _stream())
     return out
 
 
@@ -66,7 +62,7 @@ def packed_weight(w, dtype, cin_pad, transposed, sigma, plan, generation=None, s
 
 def _plane_query(shape):
     d = ConvDesc(*shape)
-    return int(L.lib().s2e_conv2d_plane_supported(L.S2E_BF16, C.byref(d)))
+    return int(L.call.s2e_conv2d_plane_supported(L.S2E_BF16, d))
 
 
 def plane_mode(x_dtype, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, transposed, in_act=ACT_NONE, out_act=ACT_NONE, aux_mode=AUX_NONE,
@@ -94,7 +90,7 @@ def _conv_plan(wgrad, dt, *shape):
     ent = _CONV_PLANS.get(key)
     if ent is None:
         d = ConvDesc(*shape)
-        wsb = (L.lib().s2e_conv2d_wgrad_workspace_bytes if wgrad else L.lib().s2e_conv2d_workspace_bytes)(dt, C.byref(d))
+        wsb = (L.call.s2e_conv2d_wgrad_workspace_bytes if wgrad else L.call.s2e_conv2d_workspace_bytes)(dt, d)
         if len(_CONV_PLANS) > 8192:
             _CONV_PLANS.clear()
         ent = _CONV_PLANS[key] = (d, wsb)
@@ -107,7 +103,7 @@ def _conv_stats_slots(dt, d, *shape):
 
 
 def _stats_slots_query(dt, d):
-    return int(L.lib().s2e_conv2d_stats_slots(dt, C.byref(d)))
+    return int(L.call.s2e_conv2d_stats_slots(dt, d))
 
 
 def conv2d_raw(x, wp, bias, residual, aux, out_hw_c, kh, kw, stride, pad, transposed=False,
@@ -129,8 +125,8 @@ def conv2d_raw(x, wp, bias, residual, aux, out_hw_c, kh, kw, stride, pad, transp
     pix = hi * wi if transposed else ho * wo
     flops = 2.0 * n * pix * cin * cout * kh * kw
     if plane:
-        LaunchProfiler.run('conv_plane', flops, lambda: L.check(
-            L.lib().s2e_conv2d_plane(dt, _p(x), _p(wp), _p(bias), _p(residual), _p(aux), _p(y), C.byref(d), _stream()), 's2e_conv2d_plane'),
+        LaunchProfiler.run(
+            'conv_plane', flops, L.call.s2e_conv2d_plane, (dt, _p(x), _p(wp), _p(bias), _p(residual), _p(aux), _p(y), d, _stream()),
             tag=lambda: '%s n%d %dx%d c%d->%d k%d s%d' % ('D' if transposed else 'F', n, hi, wi, cin, cout, kh, stride),
             nbytes=lambda: float((x.numel() + y.numel() + wp.numel() + (residual.numel() if residual is not None else 0)
                                   + (aux.numel() if aux is not None else 0)) * x.element_size()))
@@ -139,21 +135,20 @@ def conv2d_raw(x, wp, bias, residual, aux, out_hw_c, kh, kw, stride, pad, transp
         slots = _conv_stats_slots(dt, d, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, in_act, out_act)
         if slots:
             part = torch.empty(n * slots * cout * 2, dtype=torch.float32, device=x.device)
-            LaunchProfiler.run('conv_patch', flops, lambda: L.check(
-                L.lib().s2e_conv2d_stats(dt, _p(x), _p(wp), _p(bias), _p(residual), _p(y), C.byref(d), _p(part), _stream()), 's2e_conv2d_stats'),
+            LaunchProfiler.run(
+                'conv_patch', flops, L.call.s2e_conv2d_stats, (dt, _p(x), _p(wp), _p(bias), _p(residual), _p(y), d, _p(part), _stream()),
                 tag=lambda: 'F n%d %dx%d c%d->%d k%d s%d +stats' % (n, hi, wi, cin, cout, kh, stride),
                 nbytes=lambda: float((x.numel() + y.numel() + wp.numel() + (residual.numel() if residual is not None else 0)) * x.element_size()))
             ws = torch.empty(n * cout * 2, dtype=torch.float64, device=x.device)
             stats = torch.empty(n, cout, 2, dtype=torch.float32, device=x.device)
-            LaunchProfiler.run('in_stats', 0.0, lambda: L.check(
-                L.lib().s2e_in_stats_from_partials(_p(part), n, slots, cout, ho * wo, IN_EPS, _p(ws), _p(stats), _stream()),
-                's2e_in_stats_from_partials'), nbytes=float(part.numel() * 4))
+            LaunchProfiler.run('in_stats', 0.0, L.call.s2e_in_stats_from_partials,
+                               (_p(part), n, slots, cout, ho * wo, IN_EPS, _p(ws), _p(stats), _stream()), nbytes=float(part.numel() * 4))
             stats_out.append(stats)
             return y
     ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device) if wsb else None
-    LaunchProfiler.run(lambda: _CONV_FAMILY[L.lib().s2e_conv2d_kernel_kind(dt, C.byref(d))], flops, lambda: L.check(
-        L.lib().s2e_conv2d(dt, _p(x), _p(wp), _p(bias), _p(residual), _p(aux), _p(y), C.byref(d), _p(ws), wsb,
-                           _stream()), 's2e_conv2d'),
+    LaunchProfiler.run(
+        lambda: _CONV_FAMILY[L.call.s2e_conv2d_kernel_kind(dt, d)], flops,
+        L.call.s2e_conv2d, (dt, _p(x), _p(wp), _p(bias), _p(residual), _p(aux), _p(y), d, _p(ws), wsb, _stream()),
         tag=lambda: '%s n%d %dx%d c%d->%d k%d s%d' % ('D' if transposed else 'F', n, hi, wi, cin, cout, kh, stride),
         # algorithmic bytes: every operand once (x, packed w, y, + residual / mask tensor when present)
         nbytes=lambda: float((x.numel() + y.numel() + wp.numel() + (residual.numel() if residual is not None else 0)
@@ -193,10 +188,9 @@ def conv2d_wgrad_raw(x, gy, kh, kw, stride, pad, in_act=ACT_NONE, want_bias=Fals
         return dw, db
     d, wsb = _conv_plan(True, _dt(x), n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, 0, in_act, ACT_NONE, AUX_NONE)
     ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device) if wsb else None
-    LaunchProfiler.run(lambda: _WGRAD_FAMILY[L.lib().s2e_conv2d_wgrad_kernel_kind(_dt(x), C.byref(d))],
-                       2.0 * n * ho * wo * cin * cout * kh * kw, lambda: L.check(
-        L.lib().s2e_conv2d_wgrad(_dt(x), _p(x), _p(gy), _p(dw), _p(dbp), C.byref(d), _p(ws), wsb, _stream()),
-        's2e_conv2d_wgrad'),
+    LaunchProfiler.run(
+        lambda: _WGRAD_FAMILY[L.call.s2e_conv2d_wgrad_kernel_kind(_dt(x), d)], 2.0 * n * ho * wo * cin * cout * kh * kw,
+        L.call.s2e_conv2d_wgrad, (_dt(x), _p(x), _p(gy), _p(dw), _p(dbp), d, _p(ws), wsb, _stream()),
         tag=lambda: 'W n%d %dx%d c%d->%d k%d s%d' % (n, hi, wi, cin, cout, kh, stride),
         nbytes=lambda: float((x.numel() + gy.numel()) * x.element_size() + dw.numel() * 4))
     return dw, db
@@ -205,8 +199,7 @@ def conv2d_wgrad_raw(x, gy, kh, kw, stride, pad, in_act=ACT_NONE, want_bias=Fals
 def unpack_weight_grad_into(dwp, dst, cout, cin, kh, kw, cin_pad, accumulate=True):
     if accumulate and GradSink.push(dwp, dst, cout, cin, kh * kw, cin_pad):
         return
-    L.check(L.lib().s2e_unpack_weight_grad(_p(dwp), _p(dst), cout, cin, kh, kw, cin_pad, int(accumulate), _stream()),
-            's2e_unpack_weight_grad')
+    L.call.s2e_unpack_weight_grad(_p(dwp), _p(dst), cout, cin, kh, kw, cin_pad, int(accumulate), _stream())
 
 
 def _unpack_dw(dw, cout, cin, kh, kw, cin_pad):
@@ -320,7 +313,7 @@ class Conv2dFn(torch.autograd.Function):
             gl = g[:live]
             if out_act == ACT_LRELU:
                 g2 = torch.empty_like(gl)
-                L.check(L.lib().s2e_lrelu_bwd(_dt(gl), _p(gl), _p(y), _p(g2), gl.numel(), _stream()), 's2e_lrelu_bwd')
+                L.call.s2e_lrelu_bwd(_dt(gl), _p(gl), _p(y), _p(g2), gl.numel(), _stream())
                 gl = g2
             gx = _live_tail_buffer(x, live)                    # (samples live.. are zero already)
             am = AUX_LRELU_GRAD if in_act == ACT_LRELU else AUX_NONE
@@ -331,11 +324,11 @@ class Conv2dFn(torch.autograd.Function):
             return gx, None, None, None, None, None, None, None, None, None, None, None
         if out_act == ACT_TANH:
             g2 = torch.empty_like(g)
-            L.check(L.lib().s2e_tanh_bwd(_dt(g), _p(g), _p(y), _p(g2), g.numel(), _stream()), 's2e_tanh_bwd')
+            L.call.s2e_tanh_bwd(_dt(g), _p(g), _p(y), _p(g2), g.numel(), _stream())
             g = g2
         elif out_act == ACT_LRELU:
             g2 = torch.empty_like(g)
-            L.check(L.lib().s2e_lrelu_bwd(_dt(g), _p(g), _p(y), _p(g2), g.numel(), _stream()), 's2e_lrelu_bwd')
+            L.call.s2e_lrelu_bwd(_dt(g), _p(g), _p(y), _p(g2), g.numel(), _stream())
             g = g2
         gx = gw = gb = gres = None
         if ctx.needs_input_grad[0]:
@@ -375,8 +368,8 @@ class Conv2dFn(torch.autograd.Function):
                 if not (acc and GradSink.push(dwp, wdst, cout, cin, kh * kw, cx, w_oihw, u, v, sigma)):
                     out = wdst if acc else torch.empty(cout, cin, kh, kw, dtype=torch.float32, device=x.device)
                     dot = ZeroPool.take(1, torch.float32, x.device)
-                    L.check(L.lib().s2e_sn_weight_grad(_p(dwp), _p(w_oihw), _p(u), _p(v), _p(sigma), _p(dot), _p(out),
-                                                       cout, cin, kh, kw, cx, int(acc), _stream()), 's2e_sn_weight_grad')
+                    L.call.s2e_sn_weight_grad(_p(dwp), _p(w_oihw), _p(u), _p(v), _p(sigma), _p(dot), _p(out),
+                                              cout, cin, kh, kw, cx, int(acc), _stream())
                     gw = None if acc else out
         elif want_b:
             gb = colsum(g)
@@ -410,10 +403,9 @@ class FcHeadFn(torch.autograd.Function):
         m, h, w, c = x.shape
         n = weight.shape[0]
         y = torch.empty(m, n, dtype=torch.float32, device=x.device)
-        wsb = L.lib().s2e_fc_head_fwd_workspace_bytes(m, h * w, c, n)
+        wsb = L.call.s2e_fc_head_fwd_workspace_bytes(m, h * w, c, n)
         ws = torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=x.device)
-        L.check(L.lib().s2e_fc_head_fwd(_dt(x), _p(x), _p(weight), _p(bias), _p(y), m, h * w, c, n, float(slope), _p(ws), wsb, _stream()),
-                's2e_fc_head_fwd')
+        L.call.s2e_fc_head_fwd(_dt(x), _p(x), _p(weight), _p(bias), _p(y), m, h * w, c, n, float(slope), _p(ws), wsb, _stream())
         ctx.slope = float(slope)
         ctx.wdst, ctx.bdst = _grad_dst(weight), _grad_dst(bias)
         ctx.save_for_backward(x, weight)
@@ -429,14 +421,13 @@ class FcHeadFn(torch.autograd.Function):
         wdst = ctx.wdst if (ctx.wdst is not None and ctx.wdst.is_contiguous()) else None
         dw = wdst if wdst is not None else (torch.zeros_like(weight) if ctx.needs_input_grad[1] else None)
         db = ctx.bdst if ctx.bdst is not None else (torch.zeros(n, dtype=torch.float32, device=x.device) if ctx.needs_input_grad[2] else None)
-        L.check(L.lib().s2e_fc_head_bwd(_dt(x), _p(x), _p(weight), _p(g), _p(dx), _p(dw), _p(db), m, h * w, c, n, ctx.slope, _stream()),
-                's2e_fc_head_bwd')
+        L.call.s2e_fc_head_bwd(_dt(x), _p(x), _p(weight), _p(g), _p(dx), _p(dw), _p(db), m, h * w, c, n, ctx.slope, _stream())
         return dx, (None if wdst is not None else dw), (None if ctx.bdst is not None else db), None
 
 
 def fc_head(x, weight, bias, slope=0.2):
     """-> (M, N) fp32, or None when the shape is outside the kernel's range (the caller then takes the convolution form)."""
     if (weight.dtype != torch.float32 or not weight.is_contiguous() or bias is None or weight.shape[1] != x.shape[1] * x.shape[2] * x.shape[3]
-            or weight.shape[1] * 4 > 48 * 1024 or not L.lib().s2e_fc_head_supported(x.shape[0], weight.shape[0])):
+            or weight.shape[1] * 4 > 48 * 1024 or not L.call.s2e_fc_head_supported(x.shape[0], weight.shape[0])):
         return None
     return FcHeadFn.apply(x.contiguous(), weight, bias, slope)

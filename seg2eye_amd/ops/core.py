@@ -1,8 +1,6 @@
 """What every op family shares: dtype / pointer / stream helpers, the memo of per-shape library queries, the upload of host-built
 job tables, the per-launch profiler, the trainer step's zero-filled scratch (ZeroPool; its queue of deferred weight-side launches is
 sink.GradSink) and the views of channels-last parameter memory."""
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -12,11 +10,13 @@ IN_EPS = 1e-5      # nn.InstanceNorm2d default (models/networks/normalization.py
 
 
 def _dt(t):
-    if t.dtype == torch.bfloat16:
+    """The library's dtype code of a tensor or a torch.dtype."""
+    dtype = t if isinstance(t, torch.dtype) else t.dtype
+    if dtype == torch.bfloat16:
         return L.S2E_BF16
-    if t.dtype == torch.float32:
+    if dtype == torch.float32:
         return L.S2E_F32
-    raise TypeError('seg2eye_amd ops take bf16 or fp32 tensors, got %s' % t.dtype)
+    raise TypeError('seg2eye_amd ops take bf16 or fp32 tensors, got %s' % dtype)
 
 
 def _p(t):
@@ -91,15 +91,16 @@ class LaunchProfiler:
         return cls.current is not None
 
     @classmethod
-    def run(cls, family, flops, fn, tag='', nbytes=0.0, executed=None):
-        """executed: the FLOPs the launch really performs when that is less than its algorithmic count (the label-sparse
+    def run(cls, family, flops, fn, args, tag='', nbytes=0.0, executed=None):
+        """fn(*args) is the launch (L.call.s2e_x and its arguments: nothing is built per launch while no profiler is installed).
+        executed: the FLOPs the launch really performs when that is less than its algorithmic count (the label-sparse
         SPADE launch computes only the rectangles that cross a label boundary); default = flops."""
         prof = cls.current
         if prof is None:
-            return fn()
+            return fn(*args)
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
-        r = fn()
+        r = fn(*args)
         e.record()
         # (family / tag / nbytes may be callables: evaluated only here, i.e. only while a profiler is installed -- formatting a
         # tag string and summing tensor sizes for each of ~1000 launches cost ~2 ms of host time per eager step)
@@ -319,9 +320,8 @@ def colsum(g):
     _need(g)
     c = g.shape[-1]
     out = torch.zeros(c, dtype=torch.float32, device=g.device)
-    L.check(L.lib().s2e_colsum(_dt(g), _p(g), g.numel() // c, c, _p(out), _stream()), 's2e_colsum')
+    L.call.s2e_colsum(_dt(g), _p(g), g.numel() // c, c, _p(out), _stream())
     return out
-_byref = C.byref          # (functions below use C for a channel count)
 
 
 # ------------------------------------------------------------------------------ OpenEDS validation metric

@@ -25,8 +25,7 @@ class LossSumFn(torch.autograd.Function):
     def forward(ctx, a, b, mode, scale, pooled=False):
         _need(a, b)
         out = _loss_slot(a.device, pooled)
-        L.check(L.lib().s2e_loss_reduce(_dt(a), mode, _p(a), _p(b), a.numel(), float(scale), _p(out), _stream()),
-                's2e_loss_reduce')
+        L.call.s2e_loss_reduce(_dt(a), mode, _p(a), _p(b), a.numel(), float(scale), _p(out), _stream())
         ctx.cfg = (mode, float(scale))
         ctx.save_for_backward(a, b)
         return out
@@ -37,8 +36,7 @@ class LossSumFn(torch.autograd.Function):
         mode, scale = ctx.cfg
         gs = gout.detach().float().contiguous()
         da = torch.empty_like(a)
-        L.check(L.lib().s2e_loss_grad(_dt(a), mode, _p(a), _p(b), a.numel(), scale, _p(gs), _p(da), 0, _stream()),
-                's2e_loss_grad')
+        L.call.s2e_loss_grad(_dt(a), mode, _p(a), _p(b), a.numel(), scale, _p(gs), _p(da), 0, _stream())
         return da, None, None, None, None
 
 
@@ -54,7 +52,7 @@ class HalfLossFn(torch.autograd.Function):
         n = t.shape[0] // 2
         half = t[n:] if second else t[:n]
         out = _loss_slot(t.device, pooled)
-        L.check(L.lib().s2e_loss_reduce(_dt(t), mode, _p(half), None, half.numel(), float(scale), _p(out), _stream()), 's2e_loss_reduce')
+        L.call.s2e_loss_reduce(_dt(t), mode, _p(half), None, half.numel(), float(scale), _p(out), _stream())
         ctx.cfg = (bool(second), mode, float(scale), n)
         ctx.save_for_backward(t)
         return out
@@ -71,7 +69,7 @@ class HalfLossFn(torch.autograd.Function):
         else:
             gt = _live_tail_buffer(t, n)
             dst, src = gt[:n], t[:n]
-        L.check(L.lib().s2e_loss_grad(_dt(t), mode, _p(src), None, src.numel(), scale, _p(gs), _p(dst), 0, _stream()), 's2e_loss_grad')
+        L.call.s2e_loss_grad(_dt(t), mode, _p(src), None, src.numel(), scale, _p(gs), _p(dst), 0, _stream())
         return gt, None, None, None, None
 
 
@@ -86,7 +84,7 @@ class PairLossFn(torch.autograd.Function):
         outs = []
         for half, mode in ((t[:n], mode_a), (t[n:], mode_b)):
             out = _loss_slot(t.device, pooled)
-            L.check(L.lib().s2e_loss_reduce(_dt(t), mode, _p(half), None, half.numel(), float(scale), _p(out), _stream()), 's2e_loss_reduce')
+            L.call.s2e_loss_reduce(_dt(t), mode, _p(half), None, half.numel(), float(scale), _p(out), _stream())
             outs.append(out)
         ctx.cfg = (mode_a, mode_b, float(scale), n)
         ctx.set_materialize_grads(False)
@@ -105,7 +103,7 @@ class PairLossFn(torch.autograd.Function):
                 dst.zero_()
                 continue
             gs = g.detach().float().contiguous()
-            L.check(L.lib().s2e_loss_grad(_dt(t), mode, _p(src), None, src.numel(), scale, _p(gs), _p(dst), 0, _stream()), 's2e_loss_grad')
+            L.call.s2e_loss_grad(_dt(t), mode, _p(src), None, src.numel(), scale, _p(gs), _p(dst), 0, _stream())
         return gt, None, None, None, None
 
 
@@ -140,8 +138,7 @@ class FeatTapFn(torch.autograd.Function):
         n = h.shape[0] // 2
         a, b = h[:n], h[n:]
         out = _loss_slot(h.device, pooled)
-        L.check(L.lib().s2e_loss_reduce(_dt(h), LOSS_L1, _p(a), _p(b), a.numel(), float(scale), _p(out), _stream()),
-                's2e_loss_reduce')
+        L.call.s2e_loss_reduce(_dt(h), LOSS_L1, _p(a), _p(b), a.numel(), float(scale), _p(out), _stream())
         ctx.scale = float(scale)
         ctx.grad_mode = LOSS_L1_NANGRAD if nan_grad else LOSS_L1
         ctx.save_for_backward(h)
@@ -160,8 +157,7 @@ class FeatTapFn(torch.autograd.Function):
             gh = gh.contiguous()
         a, b, ga = h[:n], h[n:], gh[:n]
         gs = gloss.detach().float().contiguous()
-        L.check(L.lib().s2e_loss_grad(_dt(h), ctx.grad_mode, _p(a), _p(b), a.numel(), ctx.scale, _p(gs), _p(ga), 1, _stream()),
-                's2e_loss_grad')
+        L.call.s2e_loss_grad(_dt(h), ctx.grad_mode, _p(a), _p(b), a.numel(), ctx.scale, _p(gs), _p(ga), 1, _stream())
         return gh, None, None, None
 
 
@@ -177,10 +173,9 @@ def adam_flat_step(p, g, m, v, hyper, skips_m=False):
     hyper: 7-float DEVICE tensor {lr, beta1, beta2, eps, completed steps, grad_scale, weight_decay}.
     skips_m: the caller knows beta1 == 0 and weight_decay == 0 (the kernel then leaves m alone): only the profiler's byte count uses it."""
     _need(p, g, m, v, hyper)
-    LaunchProfiler.run('adam', 0.0, lambda: L.check(
-        L.lib().s2e_adam_flat(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _stream()), 's2e_adam_flat'),
-        # SURVEY 8(d): read p, g, m, v + write p, m, v = 28 B per parameter; without the first moment 20 B
-        nbytes=float((5 if skips_m else 7) * 4 * p.numel()))
+    LaunchProfiler.run('adam', 0.0, L.call.s2e_adam_flat, (_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _stream()),
+                       # SURVEY 8(d): read p, g, m, v + write p, m, v = 28 B per parameter; without the first moment 20 B
+                       nbytes=float((5 if skips_m else 7) * 4 * p.numel()))
 
 
 def adam_flat_ema_step(p, g, m, v, ema, hyper, ema_hyper, skips_m=False):
@@ -188,15 +183,14 @@ def adam_flat_ema_step(p, g, m, v, ema, hyper, ema_hyper, skips_m=False):
     the bits adam_flat_step gives them.  ema_hyper: 2-float DEVICE tensor {decay, start_step}; the step t = completed steps + 1
     copies p into ema while t <= start_step and averages afterwards, ema = decay * ema + (1 - decay) * p."""
     _need(p, g, m, v, ema, hyper, ema_hyper)
-    LaunchProfiler.run('adam', 0.0, lambda: L.check(
-        L.lib().s2e_adam_flat_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), _p(ema_hyper), _stream()), 's2e_adam_flat_ema'),
-        # adam_flat_step's bytes + the average's own read and write: 7 floats per parameter without the first moment, 9 with it
-        nbytes=float((7 if skips_m else 9) * 4 * p.numel()))
+    LaunchProfiler.run('adam', 0.0, L.call.s2e_adam_flat_ema, (_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), _p(ema_hyper), _stream()),
+                       # adam_flat_step's bytes + the average's own read and write: 7 floats per parameter without the first moment, 9 with it
+                       nbytes=float((7 if skips_m else 9) * 4 * p.numel()))
 
 
 def grad_guard_workspace(n, device):
     """The workspace s2e_grad_guard needs for an arena of n elements: per-block {fp64 sum, first index} records."""
-    return torch.empty(int(L.lib().s2e_grad_guard_workspace_bytes(int(n))) // 8, dtype=torch.float64, device=device)
+    return torch.empty(int(L.call.s2e_grad_guard_workspace_bytes(int(n))) // 8, dtype=torch.float64, device=device)
 
 
 def guard_coefficient(norm, max_norm, has_nonfinite=False, skip_nonfinite=False):
@@ -214,28 +208,25 @@ def grad_guard(g, hyper, guard, first_bad, workspace):
     coefficient, skipped, clipped, consecutive skips, 0}, first_bad (1 int32, DEVICE) = index of the first non-finite element or -1
     (seg2eye_hip.h: s2e_grad_guard).  Two launches, no atomics, no synchronisation; hyper[5] (grad_scale) enters the norm."""
     _need(g, hyper, guard, first_bad, workspace)
-    LaunchProfiler.run('adam', 0.0, lambda: L.check(
-        L.lib().s2e_grad_guard(_p(g), g.numel(), _p(hyper), _p(guard), _p(first_bad), _p(workspace),
-                               workspace.numel() * workspace.element_size(), _stream()), 's2e_grad_guard'),
-        nbytes=float(4 * g.numel()))                             # the guard reads g once
+    LaunchProfiler.run('adam', 0.0, L.call.s2e_grad_guard,
+                       (_p(g), g.numel(), _p(hyper), _p(guard), _p(first_bad), _p(workspace), workspace.numel() * workspace.element_size(), _stream()),
+                       nbytes=float(4 * g.numel()))                             # the guard reads g once
 
 
 def adam_flat_guarded_step(p, g, m, v, hyper, guard, skips_m=False):
     """adam_flat_step under the guard record grad_guard wrote: coefficient guard[3] == 0 leaves p, m, v and the step count alone,
     any other multiplies grad_scale (1 gives adam_flat_step's bits)."""
     _need(p, g, m, v, hyper, guard)
-    LaunchProfiler.run('adam', 0.0, lambda: L.check(
-        L.lib().s2e_adam_flat_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(guard), _stream()), 's2e_adam_flat_guarded'),
-        nbytes=float((5 if skips_m else 7) * 4 * p.numel()))     # (adam_flat_step's; a skipped step moves nothing)
+    LaunchProfiler.run('adam', 0.0, L.call.s2e_adam_flat_guarded, (_p(p), _p(g), _p(m), _p(v), p.numel(), _p(hyper), _p(guard), _stream()),
+                       nbytes=float((5 if skips_m else 7) * 4 * p.numel()))     # (adam_flat_step's; a skipped step moves nothing)
 
 
 def adam_flat_ema_guarded_step(p, g, m, v, ema, hyper, ema_hyper, guard, skips_m=False):
     """adam_flat_ema_step under the guard record: a skipped step leaves the average alone too."""
     _need(p, g, m, v, ema, hyper, ema_hyper, guard)
-    LaunchProfiler.run('adam', 0.0, lambda: L.check(
-        L.lib().s2e_adam_flat_ema_guarded(_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), _p(ema_hyper), _p(guard), _stream()),
-        's2e_adam_flat_ema_guarded'),
-        nbytes=float((7 if skips_m else 9) * 4 * p.numel()))     # (adam_flat_ema_step's)
+    LaunchProfiler.run('adam', 0.0, L.call.s2e_adam_flat_ema_guarded,
+                       (_p(p), _p(g), _p(m), _p(v), _p(ema), p.numel(), _p(hyper), _p(ema_hyper), _p(guard), _stream()),
+                       nbytes=float((7 if skips_m else 9) * 4 * p.numel()))     # (adam_flat_ema_step's)
 
 
 def openeds_error(produced, target):
@@ -245,7 +236,7 @@ def openeds_error(produced, target):
     _need(a, b)
     n, h, w = a.shape
     err = torch.empty(n, dtype=torch.float32, device=a.device)
-    L.check(L.lib().s2e_openeds_error(_dt(a), _p(a), _p(b), n, h, w, _p(err), _stream()), 's2e_openeds_error')
+    L.call.s2e_openeds_error(_dt(a), _p(a), _p(b), n, h, w, _p(err), _stream())
     return err
 
 
@@ -257,7 +248,7 @@ def openeds_error_u8(produced, target):
     _need(a, b)
     n, h, w = a.shape
     err = torch.empty(n, dtype=torch.float32, device=a.device)
-    L.check(L.lib().s2e_openeds_error_u8(_p(a), _p(b), n, h, w, _p(err), _stream()), 's2e_openeds_error_u8')
+    L.call.s2e_openeds_error_u8(_p(a), _p(b), n, h, w, _p(err), _stream())
     return err
 
 
@@ -268,5 +259,5 @@ def resize_to255(x, w=400, h=640):
     _need(a)
     n, hi, wi = a.shape
     out = torch.empty(n, 1, h, w, dtype=torch.uint8, device=a.device)
-    L.check(L.lib().s2e_resize_to255(_dt(a), _p(a), n, hi, wi, _p(out), h, w, _stream()), 's2e_resize_to255')
+    L.call.s2e_resize_to255(_dt(a), _p(a), n, hi, wi, _p(out), h, w, _stream())
     return out

@@ -145,8 +145,8 @@ def resize_bicubic_u8(frames_u8, Ho, Wo, flip, return_u8=False):
     ky, by = _bicubic_tables(H, Ho, dev)
     out = torch.empty(M, Ho, Wo, dtype=torch.float32, device=dev)
     out_u8 = torch.empty(M, Ho, Wo, dtype=torch.uint8, device=dev) if return_u8 else None
-    L.check(L.lib().s2e_resize_bicubic_u8(_p(frames_u8), _p(flip), M, H, W, Ho, Wo, _p(kx), _p(bx), _p(ky), _p(by), _p(_lut(dev)),
-                                          _p(out), _p(out_u8), _stream()), 's2e_resize_bicubic_u8')
+    L.call.s2e_resize_bicubic_u8(_p(frames_u8), _p(flip), M, H, W, Ho, Wo, _p(kx), _p(bx), _p(ky), _p(by), _p(_lut(dev)),
+                                 _p(out), _p(out_u8), _stream())
     return (out, out_u8) if return_u8 else out
 
 
@@ -156,8 +156,8 @@ def resize_nearest_u8(frames_u8, Ho, Wo, flip):
     M, H, W = frames_u8.shape
     dev = frames_u8.device
     out = torch.empty(M, Ho, Wo, dtype=torch.uint8, device=dev)
-    L.check(L.lib().s2e_resize_nearest_u8(_p(frames_u8), _p(flip), M, H, W, Ho, Wo, _p(_nearest_table(H, Ho, dev)),
-                                          _p(_nearest_table(W, Wo, dev)), _p(out), _stream()), 's2e_resize_nearest_u8')
+    L.call.s2e_resize_nearest_u8(_p(frames_u8), _p(flip), M, H, W, Ho, Wo, _p(_nearest_table(H, Ho, dev)),
+                                 _p(_nearest_table(W, Wo, dev)), _p(out), _stream())
     return out
 
 

@@ -15,9 +15,8 @@ class Upsample2xFn(torch.autograd.Function):
         _need(x)
         n, h, w, c = x.shape
         y = torch.empty(n, 2 * h, 2 * w, c, dtype=x.dtype, device=x.device)
-        LaunchProfiler.run('resample', 0.0, lambda: L.check(
-            L.lib().s2e_upsample2x_fwd(_dt(x), _p(x), _p(y), n, h, w, c, _stream()), 's2e_upsample2x_fwd'),
-            nbytes=float(5 * x.numel() * x.element_size()))
+        LaunchProfiler.run('resample', 0.0, L.call.s2e_upsample2x_fwd, (_dt(x), _p(x), _p(y), n, h, w, c, _stream()),
+                           nbytes=float(5 * x.numel() * x.element_size()))
         return y
 
     @staticmethod
@@ -25,7 +24,7 @@ class Upsample2xFn(torch.autograd.Function):
         gy = gy.contiguous()
         n, h2, w2, c = gy.shape
         gx = torch.empty(n, h2 // 2, w2 // 2, c, dtype=gy.dtype, device=gy.device)
-        L.check(L.lib().s2e_upsample2x_bwd(_dt(gy), _p(gy), _p(gx), n, h2 // 2, w2 // 2, c, _stream()), 's2e_upsample2x_bwd')
+        L.call.s2e_upsample2x_bwd(_dt(gy), _p(gy), _p(gx), n, h2 // 2, w2 // 2, c, _stream())
         return gx
 
 
@@ -43,7 +42,7 @@ class BilinearResizeFn(torch.autograd.Function):
         _need(a)
         n, H, W = a.shape
         y = torch.empty(n, h, w, 1, dtype=dtype, device=a.device)
-        L.check(L.lib().s2e_bilinear_resize_fwd(_dt(y), _p(a), _p(y), n, H, W, h, w, _stream()), 's2e_bilinear_resize_fwd')
+        L.call.s2e_bilinear_resize_fwd(_dt(y), _p(a), _p(y), n, H, W, h, w, _stream())
         ctx.shape = (tuple(x.shape), H, W)
         return y
 
@@ -53,7 +52,7 @@ class BilinearResizeFn(torch.autograd.Function):
         gy = gy.contiguous()
         n, h, w, _ = gy.shape
         gx = torch.zeros(n, H, W, dtype=torch.float32, device=gy.device)
-        L.check(L.lib().s2e_bilinear_resize_bwd(_dt(gy), _p(gy), _p(gx), n, H, W, h, w, _stream()), 's2e_bilinear_resize_bwd')
+        L.call.s2e_bilinear_resize_bwd(_dt(gy), _p(gy), _p(gx), n, H, W, h, w, _stream())
         return gx.view(shape), None, None, None
 
 
@@ -67,7 +66,7 @@ class AvgPool3x3s2Fn(torch.autograd.Function):
         _need(x)
         n, h, w, c = x.shape
         y = torch.empty(n, (h + 1) // 2, (w + 1) // 2, c, dtype=x.dtype, device=x.device)
-        L.check(L.lib().s2e_avgpool3x3s2_fwd(_dt(x), _p(x), _p(y), n, h, w, c, _stream()), 's2e_avgpool3x3s2_fwd')
+        L.call.s2e_avgpool3x3s2_fwd(_dt(x), _p(x), _p(y), n, h, w, c, _stream())
         ctx.hw = (h, w)
         return y
 
@@ -77,7 +76,7 @@ class AvgPool3x3s2Fn(torch.autograd.Function):
         h, w = ctx.hw
         n, _, _, c = gy.shape
         gx = torch.empty(n, h, w, c, dtype=gy.dtype, device=gy.device)
-        L.check(L.lib().s2e_avgpool3x3s2_bwd(_dt(gy), _p(gy), _p(gx), n, h, w, c, _stream()), 's2e_avgpool3x3s2_bwd')
+        L.call.s2e_avgpool3x3s2_bwd(_dt(gy), _p(gy), _p(gx), n, h, w, c, _stream())
         return gx
 
 
@@ -119,8 +118,7 @@ class DInputFn(torch.autograd.Function):
         _need(label, f, r)
         out = torch.empty(2 * n, H, W, cpad, dtype=fake.dtype, device=label.device)
         for half, img in ((out[:n], f), (out[n:], r)):
-            L.check(L.lib().s2e_onehot_nhwc(_dt(out), _p(label), _p(img), _p(half), n, H, W, H, W, ncls, cpad, _stream()),
-                    's2e_onehot_nhwc')
+            L.call.s2e_onehot_nhwc(_dt(out), _p(label), _p(img), _p(half), n, H, W, H, W, ncls, cpad, _stream())
         ctx.ncls, ctx.shape = ncls, fake.shape
         return out
 

@@ -58,12 +58,12 @@ class WgradJob:
 
 def _wgrad_batch_ok(key):
     n, h, w, cin, cout, sparse = key
-    return bool(L.lib().s2e_wgrad_batch_supported(L.S2E_BF16, n, h, w, cin, cout)) and (not sparse or (h % 16 == 0 and w % 16 == 0))
+    return bool(L.call.s2e_wgrad_batch_supported(L.S2E_BF16, n, h, w, cin, cout)) and (not sparse or (h % 16 == 0 and w % 16 == 0))
 
 
 def _wgrad_multi_ok(desc_key):
     d = L.ConvDesc(*desc_key)
-    return bool(L.lib().s2e_conv2d_wgrad_multi_supported(L.S2E_BF16, C.byref(d)))
+    return bool(L.call.s2e_conv2d_wgrad_multi_supported(L.S2E_BF16, d))
 
 
 class GradSink:
@@ -150,13 +150,13 @@ class GradSink:
                     nsn += 1
                 else:
                     a.dot_index = -1
-            return device_job_table(arr, lambda bm: L.lib().s2e_grad_block_map(C.byref(arr), len(jobs), bm), 3, dev) \
+            return device_job_table(arr, lambda bm: L.call.s2e_grad_block_map(C.byref(arr), len(jobs), bm), 3, dev) \
                 + (max(j.taps for j in jobs), nsn)
         jobs_dev, map_dev, nb, max_taps, nsn = self._table('jobs', key, build)
         dots = ZeroPool.take(max(nsn, 1), torch.float32, dev)
-        LaunchProfiler.run('weight_grad_relayout', 0.0, lambda: L.check(
-            L.lib().s2e_weight_grads_batched(jobs_dev.data_ptr(), map_dev.data_ptr(), nb, max_taps, int(nsn > 0),
-                                             dots.data_ptr(), _stream()), 's2e_weight_grads_batched'),
+        LaunchProfiler.run(
+            'weight_grad_relayout', 0.0, L.call.s2e_weight_grads_batched,
+            (jobs_dev.data_ptr(), map_dev.data_ptr(), nb, max_taps, int(nsn > 0), dots.data_ptr(), _stream()),
             nbytes=lambda: float(sum(j.dwp.numel() * 4 * (3 if j.w_orig is not None else 2) + (j.dwp.numel() * 4 if j.w_orig is not None else 0)
                                      for j in jobs)))
         self.keep_jobs = jobs
@@ -200,13 +200,12 @@ class GradSink:
             for a, j in zip(arr, jobs):
                 a.g, a.w, a.u, a.v, a.sigma = j.g.data_ptr(), j.w.data_ptr(), j.u.data_ptr(), j.v.data_ptr(), j.sigma.data_ptr()
                 a.rows, a.cin, a.taps = j.rows, j.cin, j.taps
-            table = device_job_table(arr, lambda bm: L.lib().s2e_sngrad_block_map(C.byref(arr), len(jobs), bm), 2, dev)
-            nscratch = int(L.lib().s2e_sngrad_scratch_floats(C.byref(arr), len(jobs)))
+            table = device_job_table(arr, lambda bm: L.call.s2e_sngrad_block_map(C.byref(arr), len(jobs), bm), 2, dev)
+            nscratch = int(L.call.s2e_sngrad_scratch_floats(C.byref(arr), len(jobs)))
             return table + (torch.empty(nscratch, dtype=torch.float32, device=dev),)
         jobs_dev, map_dev, nb, partials = self._table('inplace', key, build)
-        LaunchProfiler.run('weight_grad_relayout', 0.0, lambda: L.check(
-            L.lib().s2e_sn_grads_inplace(jobs_dev.data_ptr(), map_dev.data_ptr(), nb, partials.data_ptr(), _stream()),
-            's2e_sn_grads_inplace'),
+        LaunchProfiler.run(
+            'weight_grad_relayout', 0.0, L.call.s2e_sn_grads_inplace, (jobs_dev.data_ptr(), map_dev.data_ptr(), nb, partials.data_ptr(), _stream()),
             nbytes=lambda: float(sum(j.g.numel() * 16 for j in jobs)))     # g and W read for the dot product, g read and written
         self.keep_inplace = jobs
 
@@ -267,12 +266,11 @@ class GradSink:
             executed += f * frac
             nbytes += (j.x.numel() + j.gy.numel()) * 2.0 * frac + j.dw.numel() * 4.0
         ws = self.wg_ws
-        wsb = L.lib().s2e_wgrad_batch_workspace_bytes()
+        wsb = L.call.s2e_wgrad_batch_workspace_bytes()
         if ws is None or ws.device != dev or ws.numel() * 4 < wsb:
             ws = self.wg_ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)      # (3 slots x 256 workgroups x 288 KB)
-        LaunchProfiler.run('conv_wgrad_patch', flops, lambda: L.check(
-            L.lib().s2e_wgrad_batch(L.S2E_BF16, C.byref(arr), len(jobs), _p(ws), wsb, _stream()), 's2e_wgrad_batch'),
-            tag=lambda: 'W k3 s1 x%d batched' % len(jobs), nbytes=nbytes, executed=executed)
+        LaunchProfiler.run('conv_wgrad_patch', flops, L.call.s2e_wgrad_batch, (L.S2E_BF16, C.byref(arr), len(jobs), _p(ws), wsb, _stream()),
+                           tag=lambda: 'W k3 s1 x%d batched' % len(jobs), nbytes=nbytes, executed=executed)
         self.keep_wg = jobs
 
     @staticmethod
@@ -317,7 +315,7 @@ class GradSink:
             n, _, _, cin, ho, wo, cout, kh, kw = j.desc[:9]
             flops += 2.0 * n * ho * wo * cin * cout * kh * kw
             nbytes += (j.x.numel() + j.gy.numel()) * 2.0 + j.dw.numel() * 4.0
-        wsb = int(L.lib().s2e_conv2d_wgrad_multi_workspace_bytes(L.S2E_BF16, C.byref(arr), len(jobs)))
+        wsb = int(L.call.s2e_conv2d_wgrad_multi_workspace_bytes(L.S2E_BF16, C.byref(arr), len(jobs)))
         ws = self.gwg_ws
         if wsb and (ws is None or ws.device != dev or ws.numel() * 4 < wsb):
             pool = ZeroPool.active()
@@ -325,8 +323,8 @@ class GradSink:
                 ws, wsb = None, 0                            # (a captured graph must not start using new memory: those jobs add with atomics)
             else:
                 ws = self.gwg_ws = torch.empty(wsb // 4 + 64, dtype=torch.float32, device=dev)
-        LaunchProfiler.run('conv_wgrad', flops, lambda: L.check(
-            L.lib().s2e_conv2d_wgrad_multi(L.S2E_BF16, C.byref(arr), len(jobs), _p(ws) if wsb else None, wsb, _stream()), 's2e_conv2d_wgrad_multi'),
+        LaunchProfiler.run(
+            'conv_wgrad', flops, L.call.s2e_conv2d_wgrad_multi, (L.S2E_BF16, C.byref(arr), len(jobs), _p(ws) if wsb else None, wsb, _stream()),
             tag=lambda: 'W generic x%d multi' % len(jobs), nbytes=nbytes)
         self.keep_gwg = jobs
 
@@ -335,7 +333,7 @@ class GradSink:
     def c8_would_queue(dtype, h, w, dw, db):
         """Would push_c8 take this layer (so that its caller may leave d(actv) undefined outside the rectangle list it passes)?"""
         return (ZeroPool.active() is not None and dw is not None and db is not None and dtype == torch.bfloat16
-                and bool(L.lib().s2e_wgrad_c8_batch_supported(L.S2E_BF16, h, w, 128)))
+                and bool(L.call.s2e_wgrad_c8_batch_supported(L.S2E_BF16, h, w, 128)))
 
     @staticmethod
     def push_c8(oh, dactv, dw, db, ncls, rects=None):
@@ -348,7 +346,7 @@ class GradSink:
         if pool is None or dw is None or db is None or oh.dtype != torch.bfloat16:
             return False
         n, h, w, _ = oh.shape
-        if dactv.shape[-1] != 128 or not L.lib().s2e_wgrad_c8_batch_supported(L.S2E_BF16, h, w, 128):
+        if dactv.shape[-1] != 128 or not L.call.s2e_wgrad_c8_batch_supported(L.S2E_BF16, h, w, 128):
             return False
         if rects is not None and ((h | w) & 15):
             return False
@@ -368,10 +366,11 @@ class GradSink:
             a.H, a.W, a.ncls = j.oh.shape[1], j.oh.shape[2], j.ncls
             if j.rects is not None:
                 a.rect_list, a.rect_count = j.rects[0].data_ptr(), j.rects[1].data_ptr()
-        wsb = L.lib().s2e_wgrad_c8_batch_workspace_bytes(n, C.byref(arr), len(c8))
+        wsb = L.call.s2e_wgrad_c8_batch_workspace_bytes(n, C.byref(arr), len(c8))
         ws = torch.empty(wsb // 4, dtype=torch.float32, device=c8[0].oh.device)
-        LaunchProfiler.run('conv_wgrad_patch', sum(2.0 * n * j.oh.shape[1] * j.oh.shape[2] * 8 * 128 * 9 for j in c8), lambda: L.check(
-            L.lib().s2e_wgrad_c8_batch(L.S2E_BF16, n, C.byref(arr), len(c8), _p(ws), wsb, _stream()), 's2e_wgrad_c8_batch'),
+        LaunchProfiler.run(
+            'conv_wgrad_patch', sum(2.0 * n * j.oh.shape[1] * j.oh.shape[2] * 8 * 128 * 9 for j in c8),
+            L.call.s2e_wgrad_c8_batch, (L.S2E_BF16, n, C.byref(arr), len(c8), _p(ws), wsb, _stream()),
             tag=lambda: 'W n%d c8->128 k3 s1 x%d batched' % (n, len(c8)),
             nbytes=lambda: float(sum((j.oh.numel() + j.dactv.numel()) * 2 for j in c8)))
         self.keep_c8 = (c8, ws, self.keep_c8 if rest else None)   # (with the workspace; a round of another batch size chains the one before it)
@@ -417,7 +416,6 @@ class GradSink:
                 a.w_sh, a.b_sh = j.w_sh.data_ptr(), j.b_sh.data_ptr()
                 a.dw_sh, a.db_sh, a.dw_gb, a.db_gb = _p(j.dw_sh), _p(j.db_sh), _p(j.dw_gb), _p(j.db_gb)
                 a.C2, a.nh, a.ncls, a.act_bf16 = j.c2, j.nh, j.ncls, j.act_bf16
-            LaunchProfiler.run('spade_uniform_bwd', 0.0, lambda: L.check(
-                L.lib().s2e_spade_uniform_grads(C.byref(arr), len(chunk), _stream()), 's2e_spade_uniform_grads'),
-                nbytes=lambda: float(sum(j.w_gb.numel() * 4 for j in chunk)))
+            LaunchProfiler.run('spade_uniform_bwd', 0.0, L.call.s2e_spade_uniform_grads, (C.byref(arr), len(chunk), _stream()),
+                               nbytes=lambda: float(sum(j.w_gb.numel() * 4 for j in chunk)))
         self.keep_uni = jobs

@@ -8,7 +8,7 @@ from .. import _lib as L
 from .. import packing
 from .._lib import NORM_SPADE_STYLE_BATCH, NORM_ACCUMULATE_DX, ACT_NONE, AUX_NONE, AUX_RELU_MASK, NORM_SPADE_STYLE
 from . import switches
-from .core import (IN_EPS, LaunchProfiler, ZeroPool, _adjacent, _byref, _cl_dense, _cl_rows, _dt, _grad_dst, _need, _p, _span2, _stream,
+from .core import (IN_EPS, LaunchProfiler, ZeroPool, _adjacent, _cl_dense, _cl_rows, _dt, _grad_dst, _need, _p, _span2, _stream,
                    device_job_table, memo)
 from .sink import GradSink
 from .conv import _conv_plan, _unpack_dw, conv2d_raw, conv2d_wgrad_raw, packed_weight, unpack_weight_grad_into
@@ -20,12 +20,11 @@ def in_stats(x, return_sums=False):
     return_sums: also the raw fp64 per-sample sums (N,C,2) {sum x, sum x^2} (BatchNorm SPADE combines them over the batch)."""
     _need(x)
     n, h, w, c = x.shape
-    ws = torch.empty(L.lib().s2e_in_stats_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
+    ws = torch.empty(L.call.s2e_in_stats_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
     stats = torch.empty(n, c, 2, dtype=torch.float32, device=x.device)
     cnt = None          # (the C ABI's one-launch form -- zeroed block counters -- measured slower: include/seg2eye_hip.h)
-    LaunchProfiler.run('in_stats', 0.0, lambda: L.check(
-        L.lib().s2e_in_stats(_dt(x), _p(x), n, h * w, c, IN_EPS, _p(ws), _p(stats), _p(cnt), _stream()), 's2e_in_stats'),
-        nbytes=float(x.numel() * x.element_size()))                   # algorithmic: x read once
+    LaunchProfiler.run('in_stats', 0.0, L.call.s2e_in_stats, (_dt(x), _p(x), n, h * w, c, IN_EPS, _p(ws), _p(stats), _p(cnt), _stream()),
+                       nbytes=float(x.numel() * x.element_size()))                   # algorithmic: x read once
     return (stats, ws[:n * c * 2].view(n, c, 2)) if return_sums else stats
 
 
@@ -34,9 +33,8 @@ def label_conv3x3_raw(label, weight, bias, n, H, W, h, w, cout, relu, dtype):
     _need(label, weight, bias)
     out = torch.empty(n, h, w, cout, dtype=dtype, device=label.device)
     ncls = weight.shape[1]
-    LaunchProfiler.run('label_conv', 0.0, lambda: L.check(
-        L.lib().s2e_label_conv3x3(_dt(out), _p(label), _p(weight), _p(bias), _p(out), n, H, W, h, w, ncls, cout,
-                                  int(relu), _stream()), 's2e_label_conv3x3'),
+    LaunchProfiler.run(
+        'label_conv', 0.0, L.call.s2e_label_conv3x3, (_dt(out), _p(label), _p(weight), _p(bias), _p(out), n, H, W, h, w, ncls, cout, int(relu), _stream()),
         nbytes=float(out.numel() * out.element_size() + n * h * w))     # algorithmic: the output written once (+ the label bytes)
     return out
 
@@ -99,10 +97,9 @@ class SpadePrepass:
 
     # ------------------------------------------------------------------ plan
     def _build(self, rec, label, dtype):
-        lib = L.lib()
+        dt = _dt(dtype)
         n = label.shape[0]
         dev = label.device
-        dt = L.S2E_BF16 if dtype == torch.bfloat16 else L.S2E_F32
         esz = 2 if dtype == torch.bfloat16 else 4
         plan = {'pins': [], 'conv': None, 'table': None}
         if rec['conv']:
@@ -115,7 +112,7 @@ class SpadePrepass:
                 off += (n * h * w * cout * esz + 255) // 256 * 256
                 plan['pins'] += [(w_sh, w_sh.data_ptr())] + ([(b_sh, b_sh.data_ptr())] if b_sh is not None else [])   # (the objects the ops were handed: a re-homed Parameter shows here)
             jobs_dev, map_dev, nb = device_job_table(
-                jobs, lambda bm: lib.s2e_label_conv_block_map(dt, C.byref(jobs), len(rec['conv']), n, bm), 3, dev)
+                jobs, lambda bm: L.call.s2e_label_conv_block_map(dt, C.byref(jobs), len(rec['conv']), n, bm), 3, dev)
             plan['conv'] = dict(jobs=jobs_dev, map=map_dev, nb=nb, bytes=off, entries=entries, ncls=rec['conv'][0][0].shape[1])
         if rec['table']:
             jobs = (L.ClassTableJob * len(rec['table']))()
@@ -127,27 +124,25 @@ class SpadePrepass:
                 off += ncls * 25 * 2 * c * 4
                 plan['pins'] += [(w_sh, w_sh.data_ptr()), (b_sh, b_sh.data_ptr()), (wp, wp.data_ptr()), (b_f, b_f.data_ptr())]
             jobs_dev, map_dev, nb = device_job_table(
-                jobs, lambda bm: lib.s2e_class_table_block_map(C.byref(jobs), len(rec['table']), bm), 2, dev)
+                jobs, lambda bm: L.call.s2e_class_table_block_map(C.byref(jobs), len(rec['table']), bm), 2, dev)
             plan['table'] = dict(jobs=jobs_dev, map=map_dev, nb=nb, bytes=off, entries=entries, ncls=rec['table'][0][6])
         return plan
 
     def _run(self, plan, label, dtype):
+        dt = _dt(dtype)
         n, H, W = label.shape
-        dt = L.S2E_BF16 if dtype == torch.bfloat16 else L.S2E_F32
         pc = plan['conv']
         if pc is not None:
             buf = torch.empty(pc['bytes'], dtype=torch.uint8, device=label.device)
-            LaunchProfiler.run('label_conv', 0.0, lambda: L.check(
-                L.lib().s2e_label_conv3x3_batch(dt, _p(label), _p(pc['jobs']), _p(pc['map']), pc['nb'], _p(buf), n, H, W, pc['ncls'],
-                                                _stream()), 's2e_label_conv3x3_batch'), nbytes=float(pc['bytes']))
+            LaunchProfiler.run('label_conv', 0.0, L.call.s2e_label_conv3x3_batch,
+                               (dt, _p(label), _p(pc['jobs']), _p(pc['map']), pc['nb'], _p(buf), n, H, W, pc['ncls'], _stream()), nbytes=float(pc['bytes']))
             for ptr, h, w, off, shape in pc['entries']:
                 numel = shape[0] * shape[1] * shape[2] * shape[3]
                 self.pre[('a', ptr, h, w)] = buf[off:off + numel * (2 if dtype == torch.bfloat16 else 4)].view(dtype).view(shape)
         pt = plan['table']
         if pt is not None:
             tb = torch.empty(pt['bytes'] // 4, dtype=torch.float32, device=label.device)
-            L.check(L.lib().s2e_spade_class_table_batch(dt, _p(pt['jobs']), _p(pt['map']), pt['nb'], _p(tb), pt['ncls'], _stream()),
-                    's2e_spade_class_table_batch')
+            L.call.s2e_spade_class_table_batch(dt, _p(pt['jobs']), _p(pt['map']), pt['nb'], _p(tb), pt['ncls'], _stream())
             for ptr, off, shape in pt['entries']:
                 self.pre[('t', ptr)] = tb[off // 4:off // 4 + shape[0] * 25 * shape[3]].view(shape)
 
@@ -171,6 +166,7 @@ class SpadePrepass:
     def table(cls, x_dtype, w_sh, b_sh, wp, b_f, ncls, nh, c, stable):
         """The per-class [gamma | beta] table of a label-sparse layer (s2e_spade_class_table), from the batched launch if planned.
         stable: wp and b_f are persistent buffers (PackPlan pack / arena view), i.e. worth pointing a job at."""
+        dt = _dt(x_dtype)
         wt, bt = _table_of(w_sh), b_sh.detach().float().contiguous()
         cur = cls.current
         if cur is not None:
@@ -182,8 +178,7 @@ class SpadePrepass:
             if cur.rec is not None and stable and wt.data_ptr() == w_sh.data_ptr() and bt.data_ptr() == b_sh.data_ptr():
                 cur.rec['table'].append((w_sh, b_sh, wp, b_f, c, nh, ncls))
         table = torch.empty(ncls, 5, 5, 2 * c, dtype=torch.float32, device=wp.device)
-        dt = L.S2E_BF16 if x_dtype == torch.bfloat16 else L.S2E_F32
-        L.check(L.lib().s2e_spade_class_table(dt, _p(wt), _p(bt), _p(wp), _p(b_f), _p(table), ncls, nh, c, _stream()), 's2e_spade_class_table')
+        L.call.s2e_spade_class_table(dt, _p(wt), _p(bt), _p(wp), _p(b_f), _p(table), ncls, nh, c, _stream())
         return table
 
 
@@ -197,8 +192,7 @@ def onehot_nhwc_raw(label, img, h, w, ncls, cpad, dtype):
     if key is not None and key in pool.step_cache:
         return pool.step_cache[key]
     out = torch.empty(n, h, w, cpad, dtype=dtype, device=label.device)
-    L.check(L.lib().s2e_onehot_nhwc(_dt(out), _p(label), _p(img), _p(out), n, H, W, h, w, ncls, cpad, _stream()),
-            's2e_onehot_nhwc')
+    L.call.s2e_onehot_nhwc(_dt(out), _p(label), _p(img), _p(out), n, H, W, h, w, ncls, cpad, _stream())
     if key is not None:
         pool.step_cache[key] = out
     return out
@@ -326,15 +320,14 @@ def _sparse_bwd_lists(ctx, g, h, w, cch, nh, ncls):
         return None
     n = g.shape[0]
     d, _ = _conv_plan(False, _dt(g), n, h, w, 2 * cch, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK)
-    if not memo('rects_supported', (n, h, w, cch, nh), lambda: bool(L.lib().s2e_conv2d_rects_supported(_dt(g), _byref(d)))):
+    if not memo('rects_supported', (n, h, w, cch, nh), lambda: bool(L.call.s2e_conv2d_rects_supported(_dt(g), d))):
         return None
     ck = ('rects_bwd', cls.data_ptr(), h, w)
     ent = pool.step_cache.get(ck)
     if ent is None:
         lists = torch.empty(2, cls.numel(), dtype=torch.int32, device=g.device)
         counts = torch.empty(2, dtype=torch.int32, device=g.device)
-        L.check(L.lib().s2e_label_rect_lists_bwd(_p(cls), n, h // 16, w // 16, _p(lists[0]), _p(lists[1]), _p(counts), _stream()),
-                's2e_label_rect_lists_bwd')
+        L.call.s2e_label_rect_lists_bwd(_p(cls), n, h // 16, w // 16, _p(lists[0]), _p(lists[1]), _p(counts), _stream())
         ent = pool.step_cache[ck] = (cls, lists[0], lists[1], counts)
     return ent
 
@@ -346,7 +339,7 @@ def _sparse_wgrad(g, actv, gb_dst, sp):
     n, h, w, nh = actv.shape
     c2 = g.shape[-1]
     d, _ = _conv_plan(True, _dt(g), n, h, w, nh, h, w, c2, 3, 3, 1, 1, 0, ACT_NONE, ACT_NONE, AUX_NONE)
-    wsb = memo('wgrad_rects_ws', (n, h, w, nh, c2), lambda: int(L.lib().s2e_conv2d_wgrad_rects_workspace_bytes(_dt(g), _byref(d))))
+    wsb = memo('wgrad_rects_ws', (n, h, w, nh, c2), lambda: int(L.call.s2e_conv2d_wgrad_rects_workspace_bytes(_dt(g), d)))
     dw, db = gb_dst
     if not wsb or db is None or w_strides_differ(dw):
         return False
@@ -358,9 +351,9 @@ def _sparse_wgrad(g, actv, gb_dst, sp):
     frac = 1.0
     if LaunchProfiler.active():
         frac = float(int(counts[0])) / max(cls.numel(), 1)
-    LaunchProfiler.run('conv_wgrad_patch', flops, lambda: L.check(
-        L.lib().s2e_conv2d_wgrad_rects(_dt(g), _p(actv), _p(g), _p(_cl_rows(dw)), _p(db), _byref(d), _p(work_list), _p(counts),
-                                       _p(ws), wsb, _stream()), 's2e_conv2d_wgrad_rects'),
+    LaunchProfiler.run(
+        'conv_wgrad_patch', flops, L.call.s2e_conv2d_wgrad_rects,
+        (_dt(g), _p(actv), _p(g), _p(_cl_rows(dw)), _p(db), d, _p(work_list), _p(counts), _p(ws), wsb, _stream()),
         tag=lambda: 'W n%d %dx%d c%d->%d k3 s1 sparse' % (n, h, w, nh, c2),
         nbytes=lambda: float((actv.numel() + g.numel()) * frac * g.element_size()), executed=flops * frac)
     return True
@@ -412,15 +405,16 @@ def _spade_param_grads(ctx, g, label, w_sh, w_gb, actv):
         frac = 1.0
         if LaunchProfiler.active():
             frac = float(int(counts[0])) / max(cls.numel(), 1)
-        LaunchProfiler.run('conv_patch', flops, lambda: L.check(
-            L.lib().s2e_conv2d_rects(_dt(g), _p(g), _p(wpt), None, None, _p(actv), _p(dactv), _byref(d), _p(work_list), _p(counts), _stream()),
-            's2e_conv2d_rects'), tag=lambda: 'D n%d %dx%d c%d->%d k3 s1 sparse' % (n, h, w, nh, c2),
+        LaunchProfiler.run(
+            'conv_patch', flops, L.call.s2e_conv2d_rects,
+            (_dt(g), _p(g), _p(wpt), None, None, _p(actv), _p(dactv), d, _p(work_list), _p(counts), _stream()),
+            tag=lambda: 'D n%d %dx%d c%d->%d k3 s1 sparse' % (n, h, w, nh, c2),
             nbytes=lambda: float((g.numel() + 2 * dactv.numel()) * frac * g.element_size() + wpt.numel() * g.element_size()), executed=flops * frac)
         R = ZeroPool.take(L.UNI_REPLICAS * ncls * 9 * c2, torch.float32, g.device)
         A = ZeroPool.take(ncls * nh, torch.float32, g.device)
-        LaunchProfiler.run('spade_uniform_bwd', 0.0, lambda: L.check(
-            L.lib().s2e_spade_uniform_sums(_dt(g), _p(g), n, h, w, c2, ncls, _p(cls), _p(ui_list), _p(counts), _p(R), _stream()),
-            's2e_spade_uniform_sums'), nbytes=float(g.numel() * g.element_size() * (1.0 - frac) * 1.27))
+        LaunchProfiler.run(
+            'spade_uniform_bwd', 0.0, L.call.s2e_spade_uniform_sums,
+            (_dt(g), _p(g), n, h, w, c2, ncls, _p(cls), _p(ui_list), _p(counts), _p(R), _stream()), nbytes=float(g.numel() * g.element_size() * (1.0 - frac) * 1.27))
         wdst, bdst = ctx.sh_dst
         assert uni_gb is None or tuple(w_gb.stride()) == tuple(uni_gb[0].stride()), 'weight and gradient arenas are laid out alike'
         dw_gb, db_gb = uni_gb if uni_gb is not None else (None, None)
@@ -467,9 +461,8 @@ class ModulateFn(torch.autograd.Function):
         out = torch.empty_like(x)
         ld = 0 if off is None else style.shape[1]
         sp = style.data_ptr() + 4 * (off or 0)
-        LaunchProfiler.run('modulate_fwd', 0.0, lambda: L.check(
-            L.lib().s2e_modulate_fwd(_dt(x), NORM_SPADE_STYLE, _p(x), _p(gb), _p(stats), sp, _p(out),
-                                     n, h * w, c, int(lrelu), ld, _stream()), 's2e_modulate_fwd'),
+        LaunchProfiler.run(
+            'modulate_fwd', 0.0, L.call.s2e_modulate_fwd, (_dt(x), NORM_SPADE_STYLE, _p(x), _p(gb), _p(stats), sp, _p(out), n, h * w, c, int(lrelu), ld, _stream()),
             nbytes=float(2 * x.numel() * x.element_size()))           # algorithmic: x read, out written (gamma/beta are not)
         ctx.lrelu, ctx.off, ctx.dbig, ctx.batch, ctx.relay = lrelu, off, dbig, bool(batch), bool(relay)
         ctx.save_for_backward(x, gb, style, stats)
@@ -509,7 +502,7 @@ def _modulate_grads(ctx, g, g_relay, x, gb, fout, style, stats):
             raise RuntimeError('ModulateFn: banked style without a gradient accumulator')
         dstyle, dsp, ld = None, ctx.dbig.data_ptr() + 4 * ctx.off, style.shape[1]
     sp = style.data_ptr() + 4 * (ctx.off or 0)
-    ws = torch.empty(L.lib().s2e_modulate_bwd_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
+    ws = torch.empty(L.call.s2e_modulate_bwd_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
     mode = (NORM_SPADE_STYLE_BATCH if ctx.batch else NORM_SPADE_STYLE) | (NORM_ACCUMULATE_DX if acc else 0)
     # algorithmic bytes: the two-pass structure is forced by the per-(n,c) sums, so g, x, gamma are read by
     # both passes; dgamma, dbeta and dx are written once: 9 accesses per element of x
@@ -519,17 +512,13 @@ def _modulate_grads(ctx, g, g_relay, x, gb, fout, style, stats):
     world = sdist.sync_world_size() if ctx.batch else 1
 
     def launch(stage, count):
-        if apart:
-            return L.check(L.lib().s2e_modulate_bwd_relay(_dt(x), mode, _p(g), _p(x), _p(gb), _p(fout), _p(stats), sp, _p(dx), _p(g_relay), _p(dgb), dsp,
-                                                          _p(ws), n, h * w, c, int(ctx.lrelu), ld, stage, float(count),
-                                                          int(getattr(ctx, 'x_up_w', 0)), quad, _stream()),
-                           's2e_modulate_bwd_relay')
-        return L.check(L.lib().s2e_modulate_bwd_staged(_dt(x), mode, _p(g), _p(x), _p(gb), _p(fout), _p(stats), sp, _p(dx), _p(dgb), dsp,
-                                                       _p(ws), n, h * w, c, int(ctx.lrelu), ld, stage, float(count),
-                                                       int(getattr(ctx, 'x_up_w', 0)), quad, _stream()),
-                       's2e_modulate_bwd_staged')
+        head = (_dt(x), mode, _p(g), _p(x), _p(gb), _p(fout), _p(stats), sp, _p(dx))
+        tail = (_p(dgb), dsp, _p(ws), n, h * w, c, int(ctx.lrelu), ld, stage, float(count), int(getattr(ctx, 'x_up_w', 0)), quad, _stream())
+        if apart:                                            # (the relay form takes g_relay between dx and dgb, and is otherwise the staged one)
+            return L.call.s2e_modulate_bwd_relay(*head, _p(g_relay), *tail)
+        return L.call.s2e_modulate_bwd_staged(*head, *tail)
     if world == 1:
-        LaunchProfiler.run('modulate_bwd', 0.0, lambda: launch(0, 0.0), nbytes=nb)
+        LaunchProfiler.run('modulate_bwd', 0.0, launch, (0, 0.0), nbytes=nb)
     else:
         # BatchNorm SPADE under data parallelism: the normalisation's backward sums (S0, S1 per channel) run over the samples of
         # ALL replicas -- one 2*C-double all-reduce between the two passes (the backward half of SURVEY 8 f4's exchange)
@@ -550,14 +539,14 @@ def label_rects(label, h, w, dtype, c, nh, flags=0):
     (s2e_label_rect_classify) -> (cls, dense_list, uni_list, counts, tw, th), or None when the label-sparse form is off
     / not worth it for this size.  Inside a trainer step the result is shared by every SPADE of the resolution (and by both
     forwards' layers: it depends on the label batch only)."""
+    dt = _dt(dtype)
     if switches.SPARSE_OFF:
         return None
     n, H, W = label.shape
     if h < 8 or w < 8:
         return None
     tw, th = C.c_int(0), C.c_int(0)
-    dt = L.S2E_BF16 if dtype == torch.bfloat16 else L.S2E_F32
-    if not L.lib().s2e_spade_conv_modulate_rect(dt, n, h, w, c, nh, int(flags), C.byref(tw), C.byref(th)):
+    if not L.call.s2e_spade_conv_modulate_rect(dt, n, h, w, c, nh, int(flags), C.byref(tw), C.byref(th)):
         return None
     tw, th = tw.value, th.value
     rects = n * ((h + th - 1) // th) * ((w + tw - 1) // tw)
@@ -571,8 +560,7 @@ def label_rects(label, h, w, dtype, c, nh, flags=0):
     cls = torch.empty(rects, dtype=torch.uint8, device=dev)
     lists = torch.empty(2, rects, dtype=torch.int32, device=dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
-    L.check(L.lib().s2e_label_rect_classify(_p(label), n, H, W, h, w, tw, th, _p(cls), _p(lists[0]), _p(lists[1]), _p(counts), _stream()),
-            's2e_label_rect_classify')
+    L.call.s2e_label_rect_classify(_p(label), n, H, W, h, w, tw, th, _p(cls), _p(lists[0]), _p(lists[1]), _p(counts), _stream())
     res = (cls, lists[0], lists[1], counts, tw, th)
     if pool is not None:
         pool.step_cache[key] = res
@@ -619,10 +607,9 @@ class SpadeFusedFn(torch.autograd.Function):
         flops = 2.0 * n * h * w * nh * 2 * c * 9
         sparse = None if (flags & 2) else label_rects(label, h, w, x.dtype, c, nh, flags)
         if sparse is None:
-            LaunchProfiler.run('conv_patch', flops, lambda: L.check(
-                L.lib().s2e_spade_conv_modulate(_dt(x), _p(actv), _p(wp), _p(b_f), _p(xr), _p(stats), sp, ld,
-                                                _p(out), _p(gamma), n, h, w, c, nh, int(lrelu), int(flags), _stream()),
-                's2e_spade_conv_modulate'),
+            LaunchProfiler.run(
+                'conv_patch', flops, L.call.s2e_spade_conv_modulate,
+                (_dt(x), _p(actv), _p(wp), _p(b_f), _p(xr), _p(stats), sp, ld, _p(out), _p(gamma), n, h, w, c, nh, int(lrelu), int(flags), _stream()),
                 tag=lambda: 'F n%d %dx%d c%d->%d k3 s1 +mod%s' % (n, h, w, nh, 2 * c, '' if train else ' nograd'),
                 # algorithmic bytes: actv, packed w, x in; out (and gamma when it is kept) out
                 nbytes=lambda: float((actv.numel() + wp.numel() + xr.numel() + out.numel() * (2 if train else 1)) * x.element_size()))
@@ -636,16 +623,17 @@ class SpadeFusedFn(torch.autograd.Function):
             if LaunchProfiler.active():                         # executed work of this launch (a sync: profiling runs only)
                 rects = cls.numel()
                 frac = float(int(counts[0])) / max(rects, 1)
-            LaunchProfiler.run('conv_patch', flops, lambda: L.check(
-                L.lib().s2e_spade_conv_modulate_sparse(_dt(x), _p(actv), _p(wp), _p(b_f), _p(xr), _p(stats), sp, ld, _p(out), _p(gamma),
-                                                       n, h, w, c, nh, int(lrelu), int(flags), _p(dense_list), _p(counts), _stream()),
-                's2e_spade_conv_modulate_sparse'),
+            LaunchProfiler.run(
+                'conv_patch', flops, L.call.s2e_spade_conv_modulate_sparse,
+                (_dt(x), _p(actv), _p(wp), _p(b_f), _p(xr), _p(stats), sp, ld, _p(out), _p(gamma),
+                 n, h, w, c, nh, int(lrelu), int(flags), _p(dense_list), _p(counts), _stream()),
                 tag=lambda: 'F n%d %dx%d c%d->%d k3 s1 +mod sparse%s' % (n, h, w, nh, 2 * c, '' if train else ' nograd'),
                 nbytes=lambda: float((actv.numel() + xr.numel() + out.numel() * (2 if train else 1)) * frac * x.element_size() + wp.numel() * x.element_size()),
                 executed=flops * frac)
-            LaunchProfiler.run('modulate_fwd', 0.0, lambda: L.check(
-                L.lib().s2e_spade_modulate_uniform(_dt(x), _p(xr), _p(stats), sp, ld, _p(table), _p(cls), _p(uni_list), _p(counts), _p(out),
-                                                   _p(gamma), n, h, w, c, tw, th, int(lrelu), int(bool(flags & 8)), _stream()), 's2e_spade_modulate_uniform'),
+            LaunchProfiler.run(
+                'modulate_fwd', 0.0, L.call.s2e_spade_modulate_uniform,
+                (_dt(x), _p(xr), _p(stats), sp, ld, _p(table), _p(cls), _p(uni_list), _p(counts), _p(out),
+                 _p(gamma), n, h, w, c, tw, th, int(lrelu), int(bool(flags & 8)), _stream()),
                 nbytes=float((xr.numel() + out.numel() * (2 if train else 1)) * (1.0 - frac) * x.element_size()))
         ctx.cfg = (h, w, c)
         ctx.lrelu, ctx.off, ctx.dbig, ctx.batch, ctx.relay = lrelu, off, dbig, bool(batch), bool(relay)
@@ -679,7 +667,7 @@ def spade_fused_supported(x, nh, flags=0):
         h, w = 2 * h, 2 * w
     if switches.FUSED_OFF:
         return False
-    return bool(L.lib().s2e_spade_conv_modulate_supported(_dt(x), n, h, w, c, nh, int(flags)))
+    return bool(L.call.s2e_spade_conv_modulate_supported(_dt(x), n, h, w, c, nh, int(flags)))
 
 
 def spade_style_fused(x, label, w_sh, b_sh, w_g, b_g, w_b, b_b, style, stats, lrelu, off=None, dbig=None, batch=False,
@@ -708,12 +696,11 @@ class InstanceNormFn(torch.autograd.Function):
     def forward(ctx, x, lrelu):
         _need(x)
         n, h, w, c = x.shape
-        ws = torch.empty(L.lib().s2e_in_stats_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
+        ws = torch.empty(L.call.s2e_in_stats_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
         stats = torch.empty(n, c, 2, dtype=torch.float32, device=x.device)
         out = torch.empty_like(x)
-        LaunchProfiler.run('modulate_fwd', 0.0, lambda: L.check(
-            L.lib().s2e_instance_norm_fwd(_dt(x), _p(x), _p(out), _p(stats), _p(ws), n, h * w, c, IN_EPS, int(lrelu), _stream()),
-            's2e_instance_norm_fwd'),
+        LaunchProfiler.run(
+            'modulate_fwd', 0.0, L.call.s2e_instance_norm_fwd, (_dt(x), _p(x), _p(out), _p(stats), _p(ws), n, h * w, c, IN_EPS, int(lrelu), _stream()),
             nbytes=float(3 * x.numel() * x.element_size()))           # algorithmic: x read for the statistics and again to normalise, out written
         ctx.lrelu = lrelu
         ctx.save_for_backward(x, stats)
@@ -725,10 +712,9 @@ class InstanceNormFn(torch.autograd.Function):
         n, h, w, c = x.shape
         g = g.contiguous()
         dx = torch.empty_like(x)
-        ws = torch.empty(L.lib().s2e_modulate_bwd_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
-        LaunchProfiler.run('modulate_bwd', 0.0, lambda: L.check(
-            L.lib().s2e_instance_norm_bwd(_dt(x), _p(g), _p(x), _p(stats), _p(dx), _p(ws), n, h * w, c, int(ctx.lrelu), _stream()),
-            's2e_instance_norm_bwd'),
+        ws = torch.empty(L.call.s2e_modulate_bwd_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
+        LaunchProfiler.run(
+            'modulate_bwd', 0.0, L.call.s2e_instance_norm_bwd, (_dt(x), _p(g), _p(x), _p(stats), _p(dx), _p(ws), n, h * w, c, int(ctx.lrelu), _stream()),
             nbytes=float(5 * x.numel() * x.element_size()))           # algorithmic: g, x read twice (sums, then dx), dx written
         return dx, None
 

@@ -7,7 +7,7 @@ it).  There is no CPU path: the ops raise on CPU tensors like every other op."""
 import torch
 
 from .. import _lib as L
-from .core import _need, _p, _stream
+from .core import _dt, _need, _p, _stream
 
 SIDEBYSIDE_STATUS_NAMES = ('style_image', 'label', 'target_original', 'fake')      # bit i of the status word the launches write
 
@@ -51,11 +51,9 @@ def _sidebyside_launch(label, fake, target_original, style_image, w, h, caption_
     panels = flat[:body].view(n, 1, rows, pw)
     if caption_rows:
         panels[:, :, h:].zero_()
-    lib = L.lib()
-    ws = torch.empty(lib.s2e_sidebyside_ws_bytes(n, h, w), dtype=torch.uint8, device=dev)
-    L.check(lib.s2e_sidebyside_u8(L.S2E_BF16 if fake.dtype == torch.bfloat16 else L.S2E_F32, _p(fake), _p(style), ns, _p(label),
-                                  _p(target), n, H, W, Ht, Wt, h, w, pw, rows * pw, _p(ws), flat.data_ptr() + flat.numel() - 4,
-                                  _p(flat), _stream()), 's2e_sidebyside_u8')
+    ws = torch.empty(L.call.s2e_sidebyside_ws_bytes(n, h, w), dtype=torch.uint8, device=dev)
+    L.call.s2e_sidebyside_u8(_dt(fake), _p(fake), _p(style), ns, _p(label), _p(target), n, H, W, Ht, Wt, h, w, pw, rows * pw,
+                             _p(ws), flat.data_ptr() + flat.numel() - 4, _p(flat), _stream())
     return flat, panels, flat[-4:]
 
 

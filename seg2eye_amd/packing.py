@@ -41,11 +41,12 @@ class PackPlan:
 
     # ---------------------------------------------------------------- learning
     def record(self, w, dtype, cin_pad, transposed, sigma, plane=False):
+        from .ops import _cl_dense, _dt
+        _dt(dtype)                                           # (a dtype the library has no code for is refused here, before it is learned)
         k = self.key(w, dtype, cin_pad, transposed, plane)
         if k in self.jobs:
             return
         sidx = -1 if sigma is None else int(sigma.storage_offset())
-        from .ops import _cl_dense
         wd = w.detach()
         cl = bool(wd.dtype == torch.float32 and not wd.is_contiguous() and _cl_dense(wd) and int(cin_pad) == wd.shape[1] and wd.shape[1] % 8 == 0)
         if not cl and (wd.dtype != torch.float32 or not wd.is_contiguous()):
@@ -68,12 +69,13 @@ class PackPlan:
 
     # ---------------------------------------------------------------- per forward
     def _build(self):
-        lib = L.lib()
+        from .ops import _dt, upload_structs
         by_dtype = {}
         for k, j in self.jobs.items():
             by_dtype.setdefault(j['dtype'], []).append(j)
         self.tables = {}
         for dtype, jobs in by_dtype.items():
+            dt = _dt(dtype)
             # A forward pack whose weight ALSO has a transposed pack from a channels-last master (both row-major layouts) is written by
             # the transposed job's blocks when both are wanted (one read of the fp32 master): such "covered" forward jobs come first,
             # a launch with autograd on starts behind them.
@@ -88,13 +90,12 @@ class PackPlan:
                     j['covered'] = True
                     tr_of[wkey(j)]['dual'] = j
             jobs.sort(key=lambda j: (j['transposed'], not j['covered']))     # covered forward packs, the other forward packs, transposed packs
-            dt = L.S2E_BF16 if dtype == torch.bfloat16 else L.S2E_F32
             dev = jobs[0]['w'].device
             arr = (L.PackJob * len(jobs))()
             for i, j in enumerate(jobs):
                 cout, cin, kh, kw = j['w'].shape
-                rows = lib.s2e_conv_cout_pad(j['cin_pad'] if j['transposed'] else cout)
-                kpad = lib.s2e_conv_k_pad(dt, kh * kw * (cout if j['transposed'] else j['cin_pad']))
+                rows = L.call.s2e_conv_cout_pad(j['cin_pad'] if j['transposed'] else cout)
+                kpad = L.call.s2e_conv_k_pad(dt, kh * kw * (cout if j['transposed'] else j['cin_pad']))
                 if j['plane']:                               # the PLANE layout (csrc/conv_plane.h): 64-row groups, no K padding
                     rows = ((j['cin_pad'] if j['transposed'] else cout) + 63) // 64 * 64
                     kpad = kh * kw * (cout if j['transposed'] else j['cin_pad'])
@@ -110,17 +111,16 @@ class PackPlan:
                     arr[i].out_fwd = j['dual']['out'].data_ptr()
             n_fwd = sum(1 for j in jobs if not j['transposed'])
             n_cov = sum(1 for j in jobs if j['covered'])
-            nb_fwd = lib.s2e_pack_block_map(dt, C.byref(arr), n_fwd, None) if n_fwd else 0
+            nb_fwd = L.call.s2e_pack_block_map(dt, C.byref(arr), n_fwd, None) if n_fwd else 0
             bm = np.zeros(3 * max(nb_fwd, 1), dtype=np.int32)
             if n_fwd:
-                lib.s2e_pack_block_map(dt, C.byref(arr), n_fwd, bm.ctypes.data)
+                L.call.s2e_pack_block_map(dt, C.byref(arr), n_fwd, bm.ctypes.data)
             # with autograd on: the jobs behind the covered ones (job indices of that map count from arr[n_cov])
             rest = (L.PackJob * (len(jobs) - n_cov)).from_buffer(arr, n_cov * C.sizeof(L.PackJob)) if len(jobs) > n_cov else None
-            nb_all = lib.s2e_pack_block_map(dt, C.byref(rest), len(jobs) - n_cov, None) if rest is not None else 0
+            nb_all = L.call.s2e_pack_block_map(dt, C.byref(rest), len(jobs) - n_cov, None) if rest is not None else 0
             bm_all = np.zeros(3 * max(nb_all, 1), dtype=np.int32)
             if nb_all:
-                lib.s2e_pack_block_map(dt, C.byref(rest), len(jobs) - n_cov, bm_all.ctypes.data)
-            from .ops import upload_structs
+                L.call.s2e_pack_block_map(dt, C.byref(rest), len(jobs) - n_cov, bm_all.ctypes.data)
             jobs_dev = upload_structs(arr, dev)                  # (two block maps over this one array: filled by hand above)
             map_dev = (torch.from_numpy(bm).to(dev), torch.from_numpy(bm_all).to(dev), n_cov * C.sizeof(L.PackJob))
             max_taps = max(j['w'].shape[2] * j['w'].shape[3] for j in jobs)
@@ -150,10 +150,8 @@ class PackPlan:
             esz = 2 if dt == L.S2E_BF16 else 4
             # (algorithmic: the fp32 master read, the packed copy written; a covered forward pack costs its write only)
             nbytes = float(sum(j['w'].numel() * ((esz if (want_tr and j['covered']) else 4 + esz)) for i, j in enumerate(jobs) if want_tr or i < n_fwd))
-            LaunchProfiler.run('weight_pack', 0.0, lambda: L.check(
-                L.lib().s2e_pack_conv_weights(dt, jobs_ptr, map_ptr, nb, max_taps,
-                                              None if sigma_base is None else sigma_base.data_ptr(), st),
-                's2e_pack_conv_weights'), nbytes=nbytes)                # fp32 master read, packed copy written
+            LaunchProfiler.run('weight_pack', 0.0, L.call.s2e_pack_conv_weights,
+                               (dt, jobs_ptr, map_ptr, nb, max_taps, None if sigma_base is None else sigma_base.data_ptr(), st), nbytes=nbytes)
             for i, j in enumerate(jobs):
                 j['stale'] = not (want_tr or i < n_fwd)
 

@@ -22,7 +22,7 @@ _CHAIN_OFF = False      # (S2E_SN_CHAIN, retired in round 5: the two-launch powe
 
 
 def lib_chain_max_cols():
-    return L.lib().s2e_sn_chain_max_cols()
+    return L.call.s2e_sn_chain_max_cols()
 
 
 def sn_convs(root):
@@ -78,11 +78,10 @@ class SpectralBank:
         tot = int(offs[-1])
         self.scratch = torch.zeros(2 * tot, dtype=torch.int64, device=dev)
         self.chain = int(max(cols) <= lib_chain_max_cols() and not _CHAIN_OFF)
-        lib = L.lib()
         shapes = []
         for which in (0, 1):                                  # the W tile one workgroup takes: W v pass, W^T u pass
             br, bc = C.c_int(), C.c_int()
-            lib.s2e_sn_block_shape(which, C.byref(br), C.byref(bc))
+            L.call.s2e_sn_block_shape(which, C.byref(br), C.byref(bc))
             shapes.append((br.value, bc.value))
         table = (L.SnLayer * self.n)()
         maps = ([], [])
@@ -157,11 +156,11 @@ class SpectralBank:
             self.sigma = torch.empty(self.n, dtype=torch.float32, device=w.device)
         from .ops import LaunchProfiler
         wbytes = 4.0 * sum(r * c for r, c in zip(self.rows, self.cols))
-        LaunchProfiler.run('spectral_norm', 0.0, lambda: L.check(L.lib().s2e_sn_power_iteration(
+        LaunchProfiler.run('spectral_norm', 0.0, L.call.s2e_sn_power_iteration, (
             self.table_dev.data_ptr(), self.n, self.block_map_t.data_ptr(), self.block_map_t.shape[0],
             self.block_map.data_ptr(), self.block_map.shape[0],
             self.scratch.data_ptr(), self.scratch.numel() * 8, self.sigma.data_ptr(), int(bool(training)),
-            int(iterations), SN_EPS, self.chain, torch.cuda.current_stream().cuda_stream), 's2e_sn_power_iteration'),
+            int(iterations), SN_EPS, self.chain, torch.cuda.current_stream().cuda_stream),
             nbytes=wbytes * (2 * int(iterations) if training else 1))     # algorithmic: W^T u and W v each read W once per iteration
         # the backward of this forward needs u, v as they are NOW (later forwards update them in place)
         if not torch.is_grad_enabled():

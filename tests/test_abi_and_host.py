@@ -583,3 +583,136 @@ def test_dtype_entry_points_reject_bad_calls_before_any_launch():
     assert not wrong, wrong
     for name, args, want in HOST_QUERY_TABLE:
         assert getattr(L, name)(*args) == want, (name, args)
+
+
+# ------------------------------------------------------------------------------------------------ the binding against the header
+# the 11 job structures of include/seg2eye_hip.h and the ctypes classes that mirror them
+STRUCTS = {'s2e_conv_desc': 'ConvDesc', 's2e_pack_job': 'PackJob', 's2e_wgrad_multi_job': 'WgradMultiJob', 's2e_sn_layer': 'SnLayer',
+           's2e_sngrad_job': 'SnGradJob', 's2e_grad_job': 'GradJob', 's2e_wgrad_c8_job': 'WgradC8Job', 's2e_wgrad_batch_job': 'WgradBatchJob',
+           's2e_spade_uni_job': 'SpadeUniJob', 's2e_class_table_job': 'ClassTableJob', 's2e_label_conv_job': 'LabelConvJob'}
+_SCALARS = ('int', 'long', 'size_t', 'float', 'double')
+
+
+def _header_text():
+    text = open(os.path.join(ROOT, 'include', 'seg2eye_hip.h')).read()
+    return re.sub(r'//[^\n]*', '', re.sub(r'/\*.*?\*/', '', text, flags=re.S))
+
+
+def _c_class(ctype, returned=False):
+    """The class of a C type spelled as in the header, stars included ('const float*'): a scalar's name, 'ptr', 'conv_desc*',
+    'conv_desc' (nested) or, for a returned const char*, 'text'."""
+    words = [w for w in ctype.replace('*', ' ').split() if w not in ('const', 'struct')]
+    if '*' in ctype:
+        assert ctype.count('*') == 1, ctype
+        return 'text' if (returned and words == ['char']) else 'conv_desc*' if words == ['s2e_conv_desc'] else 'ptr'
+    if words == ['s2e_conv_desc']:
+        return 'conv_desc'
+    assert len(words) == 1 and words[0] in _SCALARS, 'a type this test has no class for: %r' % ctype
+    return words[0]
+
+
+def _declarators(decl):
+    """'const float *a, *b' / 'int N, Hi' / 'const void* x' -> [(class, name), ...]"""
+    first, *more = decl.split(',')
+    m = re.fullmatch(r'\s*(.*?)(\w+)\s*', first)
+    assert m and m.group(1).strip(), decl
+    base = m.group(1).replace('*', '')
+    return [(_c_class(m.group(1)), m.group(2))] + [(_c_class(base + '*' * d.count('*')), d.replace('*', '').strip()) for d in more]
+
+
+def _ctypes_class(t):
+    from seg2eye_amd import _lib
+    table = {ctypes.c_int: 'int', ctypes.c_long: 'long', ctypes.c_size_t: 'size_t', ctypes.c_float: 'float', ctypes.c_double: 'double',
+             ctypes.c_void_p: 'ptr', _lib.ConvDesc: 'conv_desc', ctypes.POINTER(_lib.ConvDesc): 'conv_desc*'}
+    assert ctypes.c_size_t is not ctypes.c_long                  # (distinct classes here: the comparison below tells them apart)
+    return table[t]
+
+
+def test_binding_agrees_with_the_header_in_arguments_return_types_and_structures():
+    """_lib.SIGNATURES and the ctypes structures are a second copy of include/seg2eye_hip.h: compare them position by position --
+    argument count, the class of every argument, the return class against the entry's kind, and every field of the job structures."""
+    from seg2eye_amd import _lib
+    text = _header_text()
+    decls = re.findall(r'(?m)^\s*((?:const\s+)?\w+)\s*(\*?)\s*(s2e_\w+)\s*\(([^)]*)\)\s*;', text)
+    assert len(decls) >= 100 and sorted(n for _, _, n, _ in decls) == sorted(_lib.SIGNATURES), len(decls)
+    returns = {_lib.STATUS: 'int', _lib.VALUE: 'int', _lib.COUNT: 'long', _lib.SIZE: 'size_t', _lib.TEXT: 'text'}
+    wrong = []
+    for rtype, rstar, name, params in decls:
+        kind, argtypes = _lib.SIGNATURES[name]
+        if _c_class(rtype + rstar, returned=True) != returns[kind]:
+            wrong.append((name, 'returns', rtype + rstar, kind))
+        params = [] if params.strip() in ('', 'void') else [p.strip() for p in params.split(',')]
+        if len(params) != len(argtypes):
+            wrong.append((name, 'argument count', len(params), len(argtypes)))
+            continue
+        for i, (p, t) in enumerate(zip(params, argtypes)):
+            (want, _), = _declarators(p)
+            got = _ctypes_class(t)
+            if not (got == want or (got == 'ptr' and want == 'conv_desc*')):
+                wrong.append((name, 'argument %d' % i, p, got))
+    assert not wrong, wrong
+    structs = re.findall(r'typedef\s+struct\s*\w*\s*\{([^}]*)\}\s*(\w+)\s*;', text)
+    assert len(structs) == 11 and sorted(n for _, n in structs) == sorted(STRUCTS), [n for _, n in structs]
+    for body, name in structs:
+        want = [f for decl in body.split(';') if decl.strip() for f in _declarators(decl.strip())]
+        got = [(_ctypes_class(t), n) for n, t in getattr(_lib, STRUCTS[name])._fields_]
+        assert got == want, (name, [(g, w) for g, w in zip(got, want) if g != w], len(got), len(want))
+
+
+def test_checked_handle_raises_where_the_raw_one_returns_a_code():
+    from seg2eye_amd import _lib
+    raw = _lib.lib()
+    assert raw.s2e_colsum(_lib.S2E_BF16, None, 10, 8, None, None) == -1
+    with pytest.raises(_lib.Seg2EyeHipError) as e:
+        _lib.check(-1, 's2e_colsum')
+    with pytest.raises(_lib.Seg2EyeHipError) as e2:
+        _lib.call.s2e_colsum(_lib.S2E_BF16, None, 10, 8, None, None)
+    assert str(e2.value) == str(e.value) and str(e2.value).startswith('s2e_colsum failed (-1): ')
+    assert raw.s2e_last_error().decode() in str(e2.value) and 's2e_colsum: bad argument' in str(e2.value)
+    # a COUNT planner: the code comes back as the count (no error text is set): name and code only
+    jobs = (_lib.LabelConvJob * 1)()
+    jobs[0].weight, jobs[0].h, jobs[0].w, jobs[0].cout = 64, 16, 16, 129          # (cout > 128: S2E_ERR_ARG; the weight is never read)
+    args = (_lib.S2E_BF16, ctypes.byref(jobs), 1, 2, None)
+    assert raw.s2e_label_conv_block_map(*args) == -1
+    with pytest.raises(_lib.Seg2EyeHipError) as e3:
+        _lib.call.s2e_label_conv_block_map(*args)
+    assert str(e3.value) == 's2e_label_conv_block_map failed (-1)'
+    jobs[0].cout = 128
+    assert _lib.call.s2e_label_conv_block_map(*args) == raw.s2e_label_conv_block_map(*args) > 0
+    # the checked handle is bound once and then served from its instance dictionary; lib() stays raw
+    assert _lib.call.__dict__['s2e_colsum'] is _lib.call.s2e_colsum and _lib.call.s2e_colsum is not raw.s2e_colsum
+    assert _lib.call.s2e_sn_block_shape(0, None, None) == 0 and _lib.call.s2e_version() == raw.s2e_version()
+
+
+def test_dtype_code_takes_tensors_and_dtypes_and_refuses_the_rest_first():
+    from seg2eye_amd import _lib, ops
+    from seg2eye_amd.packing import PackPlan
+    assert ops._dt(torch.bfloat16) == ops._dt(torch.zeros(1, dtype=torch.bfloat16)) == _lib.S2E_BF16
+    assert ops._dt(torch.float32) == ops._dt(torch.zeros(1)) == _lib.S2E_F32
+    for bad in (torch.float16, torch.float64):
+        with pytest.raises(TypeError, match='bf16 or fp32'):
+            ops._dt(bad)
+        with pytest.raises(TypeError, match='bf16 or fp32'):
+            ops._dt(torch.zeros(1, dtype=bad))
+    w = torch.zeros(8, 8, 3, 3)                                  # a CPU tensor: the "GPU only" error would come next
+    for plane in (False, True):
+        with pytest.raises(TypeError, match='bf16 or fp32'):
+            ops.pack_weight(w, torch.float16, plane=plane)
+    with pytest.raises(_lib.Seg2EyeHipError, match='GPU only'):
+        ops.pack_weight(w, torch.bfloat16)
+    with pytest.raises(TypeError, match='bf16 or fp32'):
+        PackPlan().record(w, torch.float16, 8, False, None)
+    with pytest.raises(TypeError, match='bf16 or fp32'):
+        ops.label_rects(torch.zeros(1, 16, 16, dtype=torch.uint8), 16, 16, torch.float16, 64, 128)
+    with pytest.raises(TypeError, match='bf16 or fp32'):
+        ops.SpadePrepass.table(torch.float16, w, w, w, w, 4, 128, 64, False)
+
+
+def test_profiler_off_is_a_plain_call():
+    from seg2eye_amd.ops import LaunchProfiler
+
+    def boom():
+        raise AssertionError('evaluated with no profiler installed')
+    assert not LaunchProfiler.active()
+    assert LaunchProfiler.run('x', 1.0, lambda a, b: (a, b), (1, 2), tag=boom, nbytes=boom) == (1, 2)
+    assert LaunchProfiler.run(boom, 1.0, max, (1, 2), executed=3.0) == 2

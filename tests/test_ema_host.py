@@ -19,7 +19,7 @@ def test_adam_flat_ema_is_declared_exported_and_checks_its_arguments():
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     assert re.search(r'\bint\s+s2e_adam_flat_ema\s*\(', text)
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), 's2e_adam_flat_ema')
-    assert len(_lib.SIGNATURES['s2e_adam_flat_ema']) == 9
+    assert _lib.SIGNATURES['s2e_adam_flat_ema'][0] == _lib.STATUS and len(_lib.SIGNATURES['s2e_adam_flat_ema'][1]) == 9
     L = _lib.lib()
     # host buffers: every call below must return S2E_ERR_ARG (-1) from the argument checks, before any launch
     buf = (ctypes.c_float * 64)()

@@ -45,7 +45,7 @@ def test_guard_symbols_are_declared_exported_bound_and_check_their_arguments():
     for name, nargs in NEW.items():
         assert re.search(r'\b(int|size_t)\s+%s\s*\(' % name, text), name
         assert hasattr(so, name), name
-        assert len(_lib.SIGNATURES[name]) == nargs, name
+        assert len(_lib.SIGNATURES[name][1]) == nargs, name
     L = _lib.lib()
     # host buffers: every call below must return S2E_ERR_ARG (-1) from the argument checks, before any launch
     buf = (ctypes.c_float * 96)()

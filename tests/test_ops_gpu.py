@@ -1402,3 +1402,31 @@ def test_fc_head_matches_torch_linear_on_leaky_relu_of_nchw_flatten(cfg, dtype):
     L.check(L.lib().s2e_fc_head_fwd(ops._dt(xd), xd.data_ptr(), w.data_ptr(), b.data_ptr(), y1.data_ptr(), M, so * so, C, N, 0.2, None, 0,
                                     torch.cuda.current_stream().cuda_stream), 's2e_fc_head_fwd')
     _close(y1, yr, torch.float32, what='fc head y (no workspace)')
+
+
+def test_an_installed_profiler_records_one_conv_launch():
+    """The installed path of LaunchProfiler.run(family, flops, fn, args, ...): one conv2d_raw at the smallest shape that reaches it
+    (below the duo and patch thresholds: the generic kernel) leaves exactly one record with the launch's family, FLOPs, tag and bytes."""
+    from seg2eye_amd import ops
+    dev = _dev()
+    x = _rnd((1, 16, 16, 64), 51, torch.bfloat16).to(dev)
+    wp = ops.pack_weight(_rnd((64, 64, 3, 3), 52, torch.float32, 0.05).to(dev), torch.bfloat16, 64, False)
+    y0 = ops.conv2d_raw(x, wp, None, None, None, (16, 16, 64), 3, 3, 1, 1)
+    prof = ops.LaunchProfiler()
+    ops.LaunchProfiler.install(prof)
+    try:
+        assert ops.LaunchProfiler.active()
+        y = ops.conv2d_raw(x, wp, None, None, None, (16, 16, 64), 3, 3, 1, 1)
+        torch.cuda.synchronize()
+        summary = prof.summary()
+    finally:
+        ops.LaunchProfiler.install(None)
+    assert not ops.LaunchProfiler.active()
+    assert len(prof.records) == 1
+    family, flops, _, _, tag, nbytes, executed = prof.records[0]
+    assert family in ops.conv._CONV_FAMILY
+    assert flops == 2 * 1 * 256 * 64 * 64 * 9 and executed == flops
+    assert tag == 'F n1 16x16 c64->64 k3 s1'
+    assert nbytes == (x.numel() + y.numel() + wp.numel()) * 2
+    assert list(summary) == [family] and summary[family]['launches'] == 1 and summary[family]['ms'] > 0
+    assert torch.equal(y, y0)
