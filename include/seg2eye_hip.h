@@ -485,6 +485,30 @@ int s2e_label_conv3x3(int dtype, const uint8_t* label, const float* weight, cons
  * the mlp_shared / fc weight gradients. */
 int s2e_onehot_nhwc(int dtype, const uint8_t* label, const void* img, void* out,
                     int N, int H, int W, int h, int w, int ncls, int cpad, void* stream);
+/* Differentiable augmentation of the discriminator's input (an extension: the reference has none).
+ * s2e_d_input_aug writes what two s2e_onehot_nhwc calls (h = H, w = W, cpad = 8) write -- out (2N,H,W,8) of T, images [0, N) from
+ * `fake`, [N, 2N) from `real`, both (N,H,W) of T -- through a per-sample transform.  params: (N, 8) fp32 rows
+ * [b, c, ty, tx, y0, x0, ch, cw], the last six integers stored exactly; row i serves fake i AND real i.  Output pixel (y, x) of
+ * sample n has the source (sy, sx) = (y - ty, x - tx) and is VISIBLE when the source lies inside the image and (y, x) lies
+ * outside the rectangle [y0, y0 + ch) x [x0, x0 + cw) (which may stick out of the image).  A visible pixel carries the one-hot
+ * of label[n, sy, sx], the image channel c * v[sy, sx] + o with o = (1 - c) * mean(v) + b (the mean of THAT image, fake's and
+ * real's apart; one fp32 multiply-add per pixel, o computed once per image) and zero pad channels; every other pixel is 8
+ * zeros.  The row [0, 1, 0, 0, 0, 0, 0, 0] gives s2e_onehot_nhwc's bits.
+ * color == 0: b and c are NOT read (taken as 0 and 1): no mean, one launch; color != 0: the means of the 2N images first (per-block
+ * fp64 partial sums in ws, plain stores, folded in index order by the launch that consumes them): two launches.  The launches
+ * depend on `color` alone, never on the rows' values (a captured graph keeps its shape).
+ * s2e_d_input_aug_bwd: gout = the gradient of out, (2N,H,W,8) of T; dfake (N,H,W) of T =
+ *   c * gout[n, sy + ty, sx + tx, ncls] where that output pixel is visible (else 0)  +  (1 - c) / (H W) * S_n,
+ * S_n = the sum of gout[n, :, :, ncls] over sample n's visible pixels (first half only).  color == 0: one launch, no sum;
+ * otherwise two.  Bit-reproducible: no atomics.
+ * ws: s2e_d_input_aug_workspace_bytes(N, H, W) bytes (either call; 0 for a size <= 0), uninitialised; may be NULL when color == 0.
+ * Before any launch: S2E_ERR_ARG on a null pointer, a size <= 0, a bad dtype or a misaligned out; S2E_ERR_UNSUPPORTED on
+ * cpad != 8, ncls >= 8 or 2 N H W >= 2^31 pixels. */
+size_t s2e_d_input_aug_workspace_bytes(int N, int H, int W);
+int s2e_d_input_aug(int dtype, const uint8_t* label, const void* fake, const void* real, const float* params, void* out,
+                    double* ws, int N, int H, int W, int ncls, int cpad, int color, void* stream);
+int s2e_d_input_aug_bwd(int dtype, const void* gout, const float* params, void* dfake, double* ws,
+                        int N, int H, int W, int ncls, int cpad, int color, void* stream);
 /* nn.Upsample(scale_factor=2) nearest (generator.py:50): (N,h,w,C) -> (N,2h,2w,C); bwd sums 2x2. */
 int s2e_upsample2x_fwd(int dtype, const void* x, void* y, int N, int h, int w, int C, void* stream);
 int s2e_upsample2x_bwd(int dtype, const void* gy, void* gx, int N, int h, int w, int C, void* stream);

@@ -168,6 +168,9 @@ SIGNATURES = {
     's2e_spade_class_table_batch': (STATUS, [_i, _vp, _vp, _i, _vp, _i, _vp]),
     's2e_label_conv3x3': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     's2e_onehot_nhwc': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_d_input_aug_workspace_bytes': (SIZE, [_i, _i, _i]),
+    's2e_d_input_aug': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    's2e_d_input_aug_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     's2e_openeds_error': (STATUS, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     's2e_openeds_error_u8': (STATUS, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     's2e_resize_to255': (STATUS, [_i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),

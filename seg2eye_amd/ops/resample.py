@@ -1,9 +1,9 @@
 """Resampling and tensor plumbing: nearest 2x upsampling, bilinear resize, 3x3 stride-2 average pooling, the discriminator's
-8-channel [one-hot | image] input and the split of its [fake | real] batch."""
+8-channel [one-hot | image] input (plain, and through the differentiable augmentation) and the split of its [fake | real] batch."""
 import torch
 
 from .. import _lib as L
-from .core import LaunchProfiler, _dt, _need, _p, _single_channel, _stream
+from .core import LaunchProfiler, _dt, _need, _p, _single_channel, _stream, memo
 from .spade import onehot_nhwc_raw
 
 
@@ -131,6 +131,52 @@ class DInputFn(torch.autograd.Function):
 def d_input(label, fake, real, ncls=4, cpad=8):
     """label (N,H,W) uint8, fake / real (N,1,H,W) or (N,H,W) -> (2N,H,W,cpad): see DInputFn."""
     return DInputFn.apply(label, fake, real, ncls, cpad)
+
+
+class DInputAugFn(torch.autograd.Function):
+    """DInputFn through the differentiable augmentation of DESIGN 3.14: the same (2N,H,W,cpad) tensor, each sample seen through its
+    row of `params` -- (N, 8) fp32 [b, c, ty, tx, y0, x0, ch, cw], row i for fake i AND real i -- as s2e_d_input_aug defines it.
+    color: is the colour part in the policy (decides the launches: 2 with it, 1 without; b and c are not read without it).
+    Differentiable w.r.t. `fake` only; when `fake` needs no gradient (the D step) nothing is saved and no backward runs."""
+
+    @staticmethod
+    def forward(ctx, label, fake, real, params, ncls, cpad, color):
+        n, H, W = label.shape
+        f, r = fake.reshape(n, H, W), real.reshape(n, H, W).to(fake.dtype)
+        f, r = (f if f.is_contiguous() else f.contiguous()), (r if r.is_contiguous() else r.contiguous())
+        _need(label, f, r, params)
+        if params.dtype != torch.float32 or tuple(params.shape) != (n, 8):
+            raise ValueError('d_input_aug: params must be (%d, 8) fp32, got %s %s' % (n, tuple(params.shape), params.dtype))
+        out = torch.empty(2 * n, H, W, cpad, dtype=fake.dtype, device=label.device)
+        L.call.s2e_d_input_aug(_dt(out), _p(label), _p(f), _p(r), _p(params), _p(out), _p(_aug_ws(n, H, W, label.device) if color else None),
+                               n, H, W, ncls, cpad, int(color), _stream())
+        ctx.cfg = (ncls, cpad, int(color), fake.shape)
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(params)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        ncls, cpad, color, shape = ctx.cfg
+        params, = ctx.saved_tensors
+        g = g if g.is_contiguous() else g.contiguous()
+        n2, H, W, _ = g.shape
+        n = n2 // 2
+        dfake = torch.empty(n, H, W, dtype=g.dtype, device=g.device)
+        L.call.s2e_d_input_aug_bwd(_dt(g), _p(g), _p(params), _p(dfake), _p(_aug_ws(n, H, W, g.device) if color else None),
+                                   n, H, W, ncls, cpad, color, _stream())
+        return None, dfake.view(shape), None, None, None, None, None
+
+
+def _aug_ws(n, H, W, device):
+    """s2e_d_input_aug's scratch (no initialisation needed; dead when the call's launches are done)."""
+    nbytes = memo('d_input_aug_ws', (n, H, W), lambda: int(L.call.s2e_d_input_aug_workspace_bytes(n, H, W)))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=device)
+
+
+def d_input_aug(label, fake, real, params, ncls=4, cpad=8, color=True):
+    """label (N,H,W) uint8, fake / real (N,1,H,W) or (N,H,W), params (N,8) fp32 on the device -> (2N,H,W,cpad): see DInputAugFn."""
+    return DInputAugFn.apply(label, fake, real, params, ncls, cpad, bool(color))
 
 
 class SplitHalvesFn(torch.autograd.Function):

@@ -40,6 +40,8 @@ _DEFAULTS = dict(
     grad_clip_norm=0.0,        # > 0: each optimizer's gradient is clipped to this global norm inside the Adam step (optim.FlatAdam); 0 = off
     skip_nonfinite_grads=False,  # a step whose gradient holds an inf / NaN changes nothing: parameters, moments, average, step count
     max_consecutive_skips=100,  # train.py stops after this many skipped steps in a row (0 = never); a policy default, not a measurement
+    diffaug='',                # differentiable augmentation of D's input: parts of 'color,translation,cutout' (seg2eye_amd/diffaug.py); '' = off
+    diffaug_seed=0,            # the sampler's CPU generator is seeded diffaug_seed + rank
 )
 
 
@@ -123,6 +125,8 @@ _CLI_TRAIN_BUILD = [
     ('visuals', 'flag', False, None),
     # the gradient guard: clip by global norm, skip steps with non-finite gradients; off = the Adam step as it was
     ('grad_clip_norm', _F, 0.0, None), ('skip_nonfinite_grads', 'flag', False, None), ('max_consecutive_skips', _I, 100, None),
+    # differentiable augmentation of the discriminator's input: 'color,translation,cutout' or a subset; '' = off
+    ('diffaug', _S, '', None), ('diffaug_seed', _I, 0, None),
 ]
 _CLI_TEST_BUILD = [
     ('use_ema', 'flag', False, None),                                 # score / generate with the averaged weights' checkpoint files
@@ -175,6 +179,9 @@ def parse(argv=None, is_train=True):
         raise ValueError('--ema_decay must lie in [0, 1) (0 = off) and --ema_start must not be negative')
     if not opt.grad_clip_norm >= 0.0 or opt.max_consecutive_skips < 0:
         raise ValueError('--grad_clip_norm (0 = off) and --max_consecutive_skips (0 = never stop) must not be negative')
+    if opt.diffaug:
+        from .diffaug import parse_policy
+        parse_policy(opt.diffaug)                          # (an unknown part raises ValueError)
     # train.py replays each step as hipGraphs BY DEFAULT (round 4: the replayed step is 15 % faster than ~900 individual launches
     # on a slow host, and the overlapped gradient exchange replays graph segments); --no_hip_graphs launches eagerly.  A failed
     # capture falls back to eager launches by itself, a batch of another shape runs eagerly for that step.  (--hip_graphs is

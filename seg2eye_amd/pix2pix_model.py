@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import checkpoint, networks, ops
+from . import checkpoint, diffaug, networks, ops
 from ._lib import LOSS_L1
 from .networks.base_network import compute_dtype_of
 from .networks.normalization import SegMap
@@ -34,6 +34,10 @@ class Pix2PixModel(nn.Module):
         self.cdtype = compute_dtype_of(opt)
         self.netG, self.netD, self.netE = self.initialize_networks(opt)
         self.netE.logvar_used = False        # (`logvar` enters no loss: pix2pix_model.py:271-305; see ConvEncoder.forward)
+        # --diffaug: the enabled parts, and the (N, 8) device rows of the step that is running -- handed over by the
+        # trainer around each G / D step; None (always, outside a trainer's step): D sees its input as it is
+        self.diffaug = diffaug.parse_policy(getattr(opt, 'diffaug', '') or '') if opt.isTrain else frozenset()
+        self.diffaug_rows = None
         if opt.isTrain:
             self.criterionGAN = networks.GANLoss(opt.gan_mode, opt=opt)
             if not opt.no_vgg_loss:
@@ -275,9 +279,15 @@ class Pix2PixModel(nn.Module):
 
     def discriminate(self, seg, fake_image, real_image, feat_lambda=None, divide=True):
         """D on cat over the batch of [cat(seg, fake); cat(seg, real)] (pix2pix_model.py:328-342); the
-        (2N,H,W,8) input is built by two launches from the label map and the two image batches.
+        (2N,H,W,8) input is built by two launches from the label map and the two image batches -- under --diffaug, inside a trainer's
+        step, through the step's augmentation rows (ops.d_input_aug: still at most two launches).
         divide=False (the loss code of this class): -> (undivided predictions, feature-matching term or None)."""
-        x = ops.d_input(seg.label, fake_image.to(self.cdtype), real_image, self.opt.label_nc, networks.discriminator.D_CPAD)
+        rows = self.diffaug_rows
+        if rows is not None and self.diffaug:                # the same row for fake i and real i; the other loss terms see fake_image itself
+            x = ops.d_input_aug(seg.label, fake_image.to(self.cdtype), real_image, rows, self.opt.label_nc, networks.discriminator.D_CPAD,
+                                color='color' in self.diffaug)
+        else:
+            x = ops.d_input(seg.label, fake_image.to(self.cdtype), real_image, self.opt.label_nc, networks.discriminator.D_CPAD)
         out, feat = self.netD(x, feat_lambda=feat_lambda) if feat_lambda is not None else (self.netD(x), None)
         if not divide:
             return out, feat

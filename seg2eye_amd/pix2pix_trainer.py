@@ -4,6 +4,7 @@ flat gradient arenas are sum-all-reduced (RCCL) between backward and the Adam la
 import contextlib
 import os
 
+from . import diffaug
 from .distributed import FlatGradSync, broadcast_buffers, broadcast_flat, exchange_active, world_size
 from .ops import ZeroPool
 from .pix2pix_model import Pix2PixModel
@@ -45,6 +46,14 @@ class Pix2PixTrainer:
         self.g_losses, self.d_losses = {}, {}
         self._static, self.graph_G, self.graph_D = None, None, None
         self.pool = ZeroPool(self.pix2pix_model.device())    # this trainer's zero-filled scratch + deferred gradient re-layouts
+        self.diffaug = self.pix2pix_model.diffaug            # --diffaug: the enabled parts (empty: off -- nothing below exists)
+        if self.diffaug:
+            # the sampler's own CPU generator, seeded per replica (each draws its own rows; nothing is exchanged), and the ONE device
+            # buffer the rows of every full-size step are copied into -- under hipGraphs a further static input of both graphs
+            import torch
+            from .distributed import get_rank
+            self._aug_gen = torch.Generator().manual_seed(int(getattr(opt, 'diffaug_seed', 0) or 0) + get_rank())
+            self._aug_rows = None
         if opt.isTrain:
             self.optimizer_G, self.optimizer_D = self.pix2pix_model_on_one_gpu.create_optimizers(opt)
             self.old_lr = opt.lr
@@ -156,28 +165,53 @@ class Pix2PixTrainer:
             _total(d_losses).backward(self._one())
         self.d_losses = {k: v.detach() for k, v in d_losses.items()}
 
+    def _hand_rows(self, data):
+        """--diffaug: draw this step's rows and hand them to the model (Pix2PixModel.discriminate).  Called BEFORE the inputs are
+        staged, with and without hipGraphs: the capture (inside _stage_inputs) and its warm-up passes then read the buffer as it
+        stands and draw nothing, so a run draws the same sequence either way.  The rows go into the persistent buffer (what a
+        replay reads); a batch of another size -- an epoch's ragged last one, which runs eagerly -- gets rows of its own size."""
+        label = data['label']
+        n, (H, W) = label.shape[0], label.shape[-2:]
+        rows = diffaug.sample(self.diffaug, n, H, W, self._aug_gen)
+        if self._aug_rows is None:
+            self._aug_rows = rows.to(self.pix2pix_model.device())
+        elif self._aug_rows.shape[0] == n:
+            self._aug_rows.copy_(rows, non_blocking=True)
+        else:
+            self.pix2pix_model.diffaug_rows = rows.to(self.pix2pix_model.device())
+            return
+        self.pix2pix_model.diffaug_rows = self._aug_rows
+
     def run_generator_one_step(self, data):
         """trainers/pix2pix_trainer.py:26-35.  With opt.hip_graphs the body is one graph replay."""
         if self.__dict__.get('_in_ema_scope'):
             raise RuntimeError('a generator step inside ema_scope() would train the averaged weights')
         self._train_mode()
         data = self._materialized(data)
+        if self.diffaug:
+            self._hand_rows(data)
         if self.use_graphs and self._stage_inputs(data):     # (captures on first use; turns graphs off if that fails)
             self.graph_G.replay(self.sync_G.launch)          # (segment k, then group k's exchange beside segment k+1)
             for k, v in getattr(self, '_static_log', {}).items():   # the replay refreshed these in place: log this step's values
                 self.pix2pix_model.add_to_loss_log(k, v.clone())
         else:
             self._g_body(data)
+        if self.diffaug:
+            self.pix2pix_model.diffaug_rows = None           # (outside a step nothing augments)
         self.optimizer_G.step(grad_scale=self.sync_G.all_reduce())
 
     def run_discriminator_one_step(self, data):
         """trainers/pix2pix_trainer.py:37-45."""
         self._train_mode()
         data = self._materialized(data)
+        if self.diffaug:
+            self._hand_rows(data)
         if self.use_graphs and self._stage_inputs(data):
             self.graph_D.replay()
         else:
             self._d_body(data)
+        if self.diffaug:
+            self.pix2pix_model.diffaug_rows = None
         self.optimizer_D.step(grad_scale=self.sync_D.all_reduce())
 
     def _materialized(self, data):

@@ -15,6 +15,9 @@ OpenEDS frames are resized, flipped and normalised on the GPU, bit-identical to 
 holds an inf / NaN change nothing, both inside the Adam step and without a host round trip; the progress line then
 carries `grad_norm/{G,D}` and `grad_skipped/{G,D}`, and `--max_consecutive_skips` skipped steps in a row end the run with the
 offending parameter's name -- `latest` is left as it was.
+`--diffaug color,translation,cutout` (or a subset) augments what the discriminator sees -- fake and real alike, in the G step and in the D
+step, fresh parameters before each, drawn from a CPU generator seeded `--diffaug_seed` + rank -- inside the launches that build D's input
+(DESIGN 3.14); validation, the other loss terms and the saved images are untouched.
 
     python train.py --name run1 --batchSize 8 --aspect_ratio 1.0 --niter 1 --niter_decay 0
     python train.py --name run1 --batchSize 8 --aspect_ratio 1.0 --display_freq 1000 --visuals     # + loss_log.txt and PNG panels
