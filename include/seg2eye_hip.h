@@ -255,13 +255,7 @@ int s2e_weight_grads_batched(const s2e_grad_job* jobs, const int* block_map, int
  * adds them in a fixed order in fp64 -- the statistics are bit-reproducible.  On return the first N*C*2 doubles of ws hold
  * {sum x, sum x^2} per (n, c) (BatchNorm SPADE combines them over the batch). */
 size_t s2e_in_stats_workspace_bytes(int dtype, int N, int HW, int C);
-/* counters: NULL (the fold is a second launch: the default), or s2e_in_stats_counters(...) unsigned ints that are ZERO: the last
- * row-walking block of each (sample, channel range) then does the fold -- same order, same bits, one launch -- and leaves them
- * zero.  Measured SLOWER on MI355X (29.7 us against 10.0 + 8.1 us per call in the train step: every block pays a device-scope
- * release, which writes back its XCD's L2); kept as an experiment (S2E_IN_STATS_ONE_LAUNCH=1 on the host side). */
-int s2e_in_stats_counters(int dtype, int N, int HW, int C);
-int s2e_in_stats(int dtype, const void* x, int N, int HW, int C, float eps, double* ws, float* stats, unsigned* counters,
-                 void* stream);
+int s2e_in_stats(int dtype, const void* x, int N, int HW, int C, float eps, double* ws, float* stats, void* stream);
 
 /* {mean, rstd} (and, in ws, the fp64 {sum x, sum x^2}) from P partial-sum slots per sample written by another kernel
  * (s2e_conv2d_stats): part (N, P, C, 2) floats, ws N*C*2 doubles, stats (N, C, 2) floats; HW = pixels per sample.  The slots of a
@@ -285,7 +279,7 @@ int s2e_modulate_fwd(int dtype, int mode, const void* x, const void* gb, const f
  *     out = 0.5*( (x-mean)*rstd*(1+gamma) + beta + x*(1+s0) + s1 )    [LeakyReLU(0.2) if lrelu]
  * gamma and beta go from the fp32 accumulators straight into the result: they are never written to memory (SURVEY 8(d):
  * "need never exist in HBM").  gamma_out: NULL (no-grad forward), or (N,H,W,C): gamma is stored for s2e_modulate_bwd's
- * S2E_NORM_GAMMA_ONLY mode.  actv (N,H,W,nh), x / out (N,H,W,C) NHWC; stats (N,C,2); style / style_ld as s2e_modulate_fwd.
+ * gamma-only form (its `out` argument).  actv (N,H,W,nh), x / out (N,H,W,C) NHWC; stats (N,C,2); style / style_ld as s2e_modulate_fwd.
  * Taken shapes (s2e_spade_conv_modulate_supported != 0): C % 64 == 0, nh a multiple of the 128-byte K row, enough
  * 256-pixel x 64-channel tiles to fill the chip (flags & 1: any tile count -- tests).  Other shapes return
  * S2E_ERR_UNSUPPORTED: run s2e_conv2d + s2e_modulate_fwd. */
@@ -293,14 +287,37 @@ int s2e_spade_conv_modulate_supported(int dtype, int N, int H, int W, int C, int
 int s2e_spade_conv_modulate(int dtype, const void* actv, const void* w_packed, const float* bias, const void* x,
                             const float* stats, const float* style, int style_ld, void* out, void* gamma_out,
                             int N, int H, int W, int C, int nh, int lrelu, int flags, void* stream);
-/* Backward of the above given g = dL/dout.  Writes dx (N,HW,C), dgb (N,HW,2C) and ACCUMULATES
- * dstyle (N,2C) fp32 (SPADE_STYLE mode only; dgb/dstyle may be NULL in PLAIN_IN mode).
- * style_ld (both calls): floats between consecutive samples' rows of style AND dstyle; 0 = dense (2C).  A
+/* Backward of s2e_modulate_fwd / s2e_spade_conv_modulate given g = dL/dout: ONE entry point.  Writes dx (N,HW,C), dgb (N,HW,2C) =
+ * [dgamma | dbeta] (the operand of the conv's weight / data gradients) and ACCUMULATES dstyle (N,2C) fp32 (SPADE_STYLE modes only;
+ * gb, style, dgb, dstyle may be NULL in PLAIN_IN mode).
+ * style_ld (forward and backward): floats between consecutive samples' rows of style AND dstyle; 0 = dense (2C).  A
  * generator keeps the style codes of all its SPADE+Style layers as column slices of ONE (N, sum 2C) matrix
  * (one GEMM for all style FCs, networks/stylebank.py), hence the leading dimension.
  * ws: s2e_modulate_bwd_workspace_bytes(...) bytes of scratch, no initialisation needed (N*C*4 fp64 sums, N*C float4
- * coefficients, then the row-walking blocks' partial sums: plain stores, added up in a fixed order -- no atomics).  mode S2E_NORM_SPADE_STYLE_BATCH: `stats` holds the same {mean, rstd} of the whole batch for every
- * sample (param_free_norm = BatchNorm2d, normalization.py:74-75) and the normalisation's backward sums over N*HW. */
+ * coefficients, then the row-walking blocks' partial sums: plain stores, added up in a fixed order -- no atomics).
+ * mode: S2E_NORM_PLAIN_IN, S2E_NORM_SPADE_STYLE, or S2E_NORM_SPADE_STYLE_BATCH: `stats` holds the same {mean, rstd} of the whole
+ *   batch for every sample (param_free_norm = BatchNorm2d, normalization.py:74-75) and the normalisation's backward sums over N*HW.
+ *   | S2E_NORM_ACCUMULATE_DX: dx = dx_add + this layer's gradient.  dx_add NULL or == dx: in place (dx holds another consumer's
+ *   gradient of the same x).  dx_add apart from dx: dx_add is left alone -- a relayed gradient (architecture.py:53-60: the block
+ *   input feeds both SPADEs and the shortcut) whose tensor a queued weight-gradient job still has to read; refused without the flag.
+ * out: NULL: gb = (N,HW,2C) [gamma | beta], the LeakyReLU mask is recomputed from them.  Else (SPADE_STYLE modes only, the forward
+ *   went through s2e_spade_conv_modulate): gb = gamma alone, (N,HW,C) (what that call stored in gamma_out; beta was never written),
+ *   and the mask is taken from the sign of the forward's output `out` (N,HW,C).
+ * stage: 0 = the whole backward.  1 and 2 split it for BatchNorm SPADE under data parallelism (the per-channel sums of the
+ *   normalisation's backward must be summed over ALL replicas' samples, as torch SyncBatchNorm does -- the 2C-float exchange of
+ *   SURVEY 8 f4):
+ *   stage 1: the row-walking pass only: dgb written, the per-(n,c) fp64 sums left in ws as (N,C,4) {S0, S1, S2, S3};
+ *   (caller: all-reduce sum over samples of S0, S1 across the replicas and fold the difference into ws[0,:,0:2])
+ *   stage 2: coefficients + dx, with the normalisation count batch_count (= world * N * HW; 0 = N * HW) in BATCH mode.
+ * x_up_w != 0 (`out` given, stage 0, per-sample statistics, even H and W): x is (N, H/2, W/2, C) with W = x_up_w -- the generator's
+ *   nearest 2x upsampling in front of the block folded into the read of x, as flags & 8 does in the forward launches; g, gamma, out,
+ *   dx, dgb are at full resolution -- unless dx_quad != 0 (SPADE_STYLE mode): then dx (and dx_add) is (N, H/2, W/2, C), the gradient
+ *   w.r.t. the half-resolution x itself (each element the sum over the 2 x 2 pixels it was replicated to: the upsampling's
+ *   backward folded in). */
+int s2e_modulate_bwd(int dtype, int mode, const void* g, const void* x, const void* gb, const void* out,
+                     const float* stats, const float* style, void* dx, const void* dx_add, void* dgb, float* dstyle, double* ws,
+                     int N, int HW, int C, int lrelu, int style_ld, int stage, double batch_count, int x_up_w,
+                     int dx_quad, void* stream);
 size_t s2e_modulate_bwd_workspace_bytes(int dtype, int N, int HW, int C);
 /* InstanceNorm2d(affine=False) [+ LeakyReLU 0.2] as ONE call each way (reference discriminator.py:91-94, encoder.py:23-39 via
  * normalization.py:38-50): out = [lrelu]((x - mean) * rstd); stats (N,C,2) {mean, rstd} out (forward) / in (backward).
@@ -311,9 +328,6 @@ int s2e_instance_norm_fwd(int dtype, const void* x, void* out, float* stats, dou
                           float eps, int lrelu, void* stream);
 int s2e_instance_norm_bwd(int dtype, const void* g, const void* x, const float* stats, void* dx, double* ws,
                           int N, int HW, int C, int lrelu, void* stream);
-int s2e_modulate_bwd(int dtype, int mode, const void* g, const void* x, const void* gb, const float* stats,
-                     const float* style, void* dx, void* dgb, float* dstyle, double* ws,
-                     int N, int HW, int C, int lrelu, int style_ld, void* stream);
 /* The weight (and bias) gradients of MANY 8-channel-input 3x3 convs in one call -- a generator's 19 mlp_shared convs
  * (normalization.py:97, backward): x = the one-hot label map at the layer's resolution (N,H,W,8), gy = d(hidden activation),
  * masked (N,H,W,128), both bf16.  dw_oihw fp32 (128, ncls, 3, 3) -- the parameter's own layout -- and dbias fp32 (128) are
@@ -425,35 +439,6 @@ int s2e_spade_modulate_uniform(int dtype, const void* x, const float* stats, con
                                const float* table, const uint8_t* cls, const int* uni_list, const int* counts,
                                void* out, void* gamma_out, int N, int H, int W, int C, int tw, int th, int lrelu, int x_up,
                                void* stream);
-/* The same backward for a forward that went through s2e_spade_conv_modulate: `gamma` is (N,HW,C) (what that call stored in
- * gamma_out; beta was never written) and the LeakyReLU mask is taken from the sign of the forward's output `out` (N,HW,C).
- * dgb is still (N,HW,2C) = [dgamma | dbeta], the operand of the conv's weight / data gradients.  SPADE_STYLE modes only. */
-int s2e_modulate_bwd_gamma(int dtype, int mode, const void* g, const void* x, const void* gamma, const void* out,
-                           const float* stats, const float* style, void* dx, void* dgb, float* dstyle, double* ws,
-                           int N, int HW, int C, int lrelu, int style_ld, void* stream);
-/* s2e_modulate_bwd / s2e_modulate_bwd_gamma (out == NULL: gb = [gamma | beta]; else gb = gamma, out = the forward's output) in
- * two stages, for BatchNorm SPADE under data parallelism (the per-channel sums of the normalisation's backward must be summed
- * over ALL replicas' samples, as torch SyncBatchNorm does -- the 2C-float exchange of SURVEY 8 f4):
- *   stage 1: the row-walking pass only: dgb written, the per-(n,c) fp64 sums left in ws as (N,C,4) {S0, S1, S2, S3};
- *   (caller: all-reduce sum over samples of S0, S1 across the replicas and fold the difference into ws[0,:,0:2])
- *   stage 2: coefficients + dx, with the normalisation count batch_count (= world * N * HW; 0 = N * HW) in BATCH mode.
- * stage 0 = both (the plain calls).
- * x_up_w != 0 (gamma-only form, stage 0, per-sample statistics): x is (N, H/2, W/2, C) with W = x_up_w -- the generator's nearest
- * 2x upsampling in front of the block folded into the read of x, as flags & 8 does in the forward launches; g, gamma, out, dx, dgb
- * are at full resolution -- unless dx_quad != 0: then dx is (N, H/2, W/2, C), the gradient w.r.t. the half-resolution x itself
- * (each element the sum over the 2 x 2 pixels it was replicated to: the upsampling's backward folded in), accumulated into
- * with S2E_NORM_ACCUMULATE_DX. */
-int s2e_modulate_bwd_staged(int dtype, int mode, const void* g, const void* x, const void* gb, const void* out,
-                            const float* stats, const float* style, void* dx, void* dgb, float* dstyle, double* ws,
-                            int N, int HW, int C, int lrelu, int style_ld, int stage, double batch_count, int x_up_w,
-                            int dx_quad, void* stream);
-/* The same with the accumulated-into tensor and the result apart: dx = dx_add + this layer's gradient (mode carries
- * S2E_NORM_ACCUMULATE_DX; dx_add NULL or == dx: in place).  For a relayed gradient (architecture.py:53-60: the block input feeds both
- * SPADEs and the shortcut) whose tensor a queued weight-gradient job still has to read (round 6: no copy of it). */
-int s2e_modulate_bwd_relay(int dtype, int mode, const void* g, const void* x, const void* gb, const void* out,
-                           const float* stats, const float* style, void* dx, const void* dx_add, void* dgb, float* dstyle, double* ws,
-                           int N, int HW, int C, int lrelu, int style_ld, int stage, double batch_count, int x_up_w,
-                           int dx_quad, void* stream);
 /* out[c] += sum_m g[m][c]  (conv bias gradient).  g (M, C); out fp32 (C). */
 int s2e_colsum(int dtype, const void* g, long M, int C, float* out, void* stream);
 

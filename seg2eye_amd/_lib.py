@@ -141,13 +141,9 @@ SIGNATURES = {
     's2e_modulate_bwd_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
     's2e_instance_norm_fwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp]),
     's2e_instance_norm_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    's2e_in_stats_counters': (VALUE, [_i, _i, _i, _i]),
-    's2e_in_stats': (STATUS, [_i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
+    's2e_in_stats': (STATUS, [_i, _vp, _i, _i, _i, _f, _vp, _vp, _vp]),
     's2e_modulate_fwd': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    's2e_modulate_bwd': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    's2e_modulate_bwd_gamma': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    's2e_modulate_bwd_staged': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp]),
-    's2e_modulate_bwd_relay': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp]),
+    's2e_modulate_bwd': (STATUS, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i, _vp]),
     's2e_spade_conv_modulate_rect': (VALUE, [_i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     's2e_label_rect_classify': (STATUS, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     's2e_spade_conv_modulate_sparse': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

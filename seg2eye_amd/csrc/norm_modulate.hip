@@ -9,15 +9,6 @@
 #include "common.h"
 #include <stdlib.h>
 
-static constexpr int kSlabIters = 16;     // row passes per block in the row-walking kernels
-// Row passes per block of the row-walking reduction kernels.  A block ends by writing its per-channel partial sums to
-// its own slot of the workspace (plain stores; a later tiny kernel adds the slots of a sample up in fp64, in a fixed order:
-// the statistics are bit-reproducible, run to run and across data-parallel replicas).  Round 1 ended every block with fp64
-// atomics on addresses shared by all blocks of the sample; the grid was then capped by their contention (in_stats of
-// (8,256,256,128): 115 us with 2048 blocks, 30 us with 256).  Without atomics the optimum stays where it was -- few, long
-// sequential row streams suit HBM better than many short ones: S2E_SLAB_BLOCKS blocks in total, same box, whole step:
-// 348.1 / 343.7 / 341.7 / 342.1 img/s at 256 / 1024 / 2048 / 4096 (modulate_bwd 2.41 / 2.61 / 2.73 / 2.71 ms per step; with the
-// atomics, at 256: 2.49) -- default 256, never fewer than 16 passes per block.
 // x handed over at HALF resolution (the generator's nearest 2x upsampling folded into the consumers' reads, xw = W of the full map,
 // 0 = x at full resolution): the pixel row of x that full-resolution pixel `pr` of sample n reads.  (pr + 0.5) * (1 / W) is at
 // least 0.5 / W away from an integer: the fp32 product cannot land on the wrong side.
@@ -28,6 +19,31 @@ __device__ __forceinline__ size_t mod_x_row(int n, int pr, int HW, int xw, float
     return (size_t)n * (HW >> 2) + (size_t)(y >> 1) * (xw >> 1) + (xx >> 1);
 }
 
+// {sum x, sum x^2} of a (sample, channel) over HW pixels -> ws (when there is one), {mean, rstd} -> stats; in fp64:
+// E[x^2] - E[x]^2 cancels.  Returns {mean, rstd}.  i = n * C + c; write = this thread's channel exists.
+__device__ __forceinline__ f32x2_t in_finalize(double s, double q, int HW, float eps, bool write, size_t i, double* __restrict__ ws,
+                                               float* __restrict__ stats) {
+    const double mean = s / HW;
+    double var = q / HW - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const f32x2_t mr = {(float)mean, (float)(1.0 / sqrt(var + (double)eps))};
+    if (write) {
+        if (ws) { ws[2 * i] = s; ws[2 * i + 1] = q; }       // {sum x, sum x^2}: BatchNorm SPADE combines them over the batch
+        stats[2 * i] = mr[0]; stats[2 * i + 1] = mr[1];
+    }
+    return mr;
+}
+
+// ------------------------------------------------------------------------------------ large maps: the row walk
+// Row passes per block of the row-walking reduction kernels.  A block ends by writing its per-channel partial sums to
+// its own slot of the workspace (plain stores; a later tiny kernel adds the slots of a sample up in fp64, in a fixed order:
+// the statistics are bit-reproducible, run to run and across data-parallel replicas).  Round 1 ended every block with fp64
+// atomics on addresses shared by all blocks of the sample; the grid was then capped by their contention (in_stats of
+// (8,256,256,128): 115 us with 2048 blocks, 30 us with 256).  Without atomics the optimum stays where it was -- few, long
+// sequential row streams suit HBM better than many short ones: S2E_SLAB_BLOCKS blocks in total, same box, whole step:
+// 348.1 / 343.7 / 341.7 / 342.1 img/s at 256 / 1024 / 2048 / 4096 (modulate_bwd 2.41 / 2.61 / 2.73 / 2.71 ms per step; with the
+// atomics, at 256: 2.49) -- default 256, never fewer than 16 passes per block.
+static constexpr int kSlabIters = 16;
 static int slab_iters_for(int HW, int rpp, int N, int zblocks) {
     const int target = 256;                          // (one block per CU: 1024 / 2048 / 4096 blocks measured slower)
     const int per_n = target / (N * zblocks) > 1 ? target / (N * zblocks) : 1;
@@ -51,18 +67,88 @@ static RowGeom row_geom(int C, int vec) {
     return g;
 }
 
-// ------------------------------------------------------------------------------------ in_stats
+// The launch plan of a per-sample row-walking reduction with NS sums per channel and its workspace, for the size queries
+// and the launchers alike.  ws, in doubles: N*C*NS sums at 0; behind them (the modulation backward, NS = 4) N*C float4
+// coefficients at `coef`; behind those the blocks' partial sums, [N][P][C][NS] floats, at `part`.  bytes == 0: not a shape
+// these kernels take.
+struct RowPlan {
+    RowGeom g;
+    int iters, P;      // row passes per block; blocks (= partial-sum slots) per sample
+    size_t coef, part, bytes;
+};
+static RowPlan row_plan(int dtype, int N, int HW, int C, int NS) {
+    RowPlan p = {};
+    const int vec = s2e_vec_lanes(dtype);
+    if (N <= 0 || HW <= 0 || C <= 0 || C % vec) return p;
+    p.g = row_geom(C, vec);
+    p.iters = slab_iters_for(HW, p.g.rpp, N, p.g.zblocks);
+    p.P = ceil_div(HW, p.g.rpp * p.iters);
+    p.coef = (size_t)N * C * NS;
+    p.part = p.coef + (NS == 4 ? (size_t)N * C * 2 : 0);
+    p.bytes = p.part * sizeof(double) + (size_t)N * p.P * C * NS * sizeof(float);
+    return p;
+}
+
+// The checks every entry point of this file starts with, in this order.  also: a further refusal (S2E_ERR_ARG) that comes
+// between the argument check and the dtype's, or NULL.
+static int norm_prologue(const char* name, bool ptrs, int dtype, int N, int HW, int C, const char* also = nullptr) {
+    if (!ptrs || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "%s: bad argument", name);
+    if (also) S2E_FAIL(S2E_ERR_ARG, "%s: %s", name, also);
+    S2E_CHECK_DTYPE(dtype, name);
+    const int vec = s2e_vec_lanes(dtype);
+    if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: C=%d not a multiple of %d", name, C, vec);
+    return S2E_OK;
+}
+
+// A thread of a row-walking block: channel group tx of the block's cgb (g of the tensor's cg), row lane ty of rpp.
+struct RowLane { int tx, ty, g; bool active; };
+__device__ __forceinline__ RowLane row_lane(int cg, int cgb, int rpp) {
+    RowLane t;
+    t.tx = threadIdx.x % cgb; t.ty = threadIdx.x / cgb;
+    t.g = blockIdx.z * cgb + t.tx;
+    t.active = t.ty < rpp && t.g < cg;
+    return t;
+}
+// The NS sums per channel that the threads left in red ([thread][VEC][NS] floats), added over the rpp row lanes by the
+// lane-0 threads, which hand each to out(j, k, sum).  (The accumulation itself stays in the kernels: see DESIGN 3.4.)
+template <int VEC, int NS, typename Out>
+__device__ __forceinline__ void fold_row_lanes(const RowLane& t, int cgb, int rpp, const float* red, Out&& out) {
+    __syncthreads();
+    if (t.active && t.ty == 0) {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            float acc[NS];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) acc[k] = 0.f;
+            for (int r = 0; r < rpp; ++r)
+#pragma unroll
+                for (int k = 0; k < NS; ++k) acc[k] += red[((r * cgb + t.tx) * VEC + j) * NS + k];
+#pragma unroll
+            for (int k = 0; k < NS; ++k) out(j, k, acc[k]);
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------ small maps: one launch
 // A dependent kernel inside a replayed graph costs ~4.6 us however little it does, and the statistics of a small map were
 // two of them (partial sums, finalize), a plain InstanceNorm + LeakyReLU three, its backward three more -- 100+ of a step's
 // 918 launches.  For maps of up to S2E_IN_SMALL_HW pixels (default 1280: 34^2) ONE block owns all rows of (sample, 8 channel
 // groups): thread = (channel group, one of 32 row lanes); fp32 sums per thread, the 32 lanes folded in fp64 in a fixed order
-// (bit-reproducible), and -- APPLY -- the same block normalises its slice in a second pass that re-reads x from L2.
+// (bit-reproducible), and the same block does the element-wise work in a second pass that re-reads its slice from L2.
 static int in_small_hw() {
     static const int v = s2e_env_int("S2E_IN_SMALL_HW", 1280);
     return v;
 }
+// channel groups per block of the small-map kernels: 8, or 4 when 8 would leave most of the CUs without a block
+static int small_groups(int N, int C, int vec) { return (long)N * ceil_div(C, 8 * vec) < 192 ? 4 : 8; }
+// f(G as an integral_constant, the grid) for a small-map kernel of element type T
+template <typename T, typename F> static void small_launch(int N, int C, F&& f) {
+    constexpr int vec = Vec<T>::N;
+    if (small_groups(N, C, vec) == 4) f(int_c<4>{}, dim3(ceil_div(C, 4 * vec), N));
+    else f(int_c<8>{}, dim3(ceil_div(C, 8 * vec), N));
+}
 
+// ------------------------------------------------------------------------------------ in_stats, plain InstanceNorm
 template <typename T, int APPLY, int G>          // G channel groups per block (8, or 4 when that is what fills the chip)
 __global__ __launch_bounds__(256) void in_small_kernel(const T* __restrict__ x, T* __restrict__ out, double* __restrict__ ws,
                                                        float* __restrict__ stats, int HW, int C, float eps, int lrelu) {
@@ -104,16 +190,8 @@ __global__ __launch_bounds__(256) void in_small_kernel(const T* __restrict__ x, 
         const int c = blockIdx.x * CH + tid;
         double S = 0.0, Q = 0.0;
         for (int k = 0; k < RL; ++k) { S += (double)red[k][tid][0]; Q += (double)red[k][tid][1]; }
-        const double mean = S / HW;
-        double var = Q / HW - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)mean, rf = (float)(1.0 / sqrt(var + (double)eps));
-        mr[tid][0] = mf; mr[tid][1] = rf;
-        if (c < C) {
-            const size_t i = (size_t)n * C + c;
-            if (ws) { ws[2 * i] = S; ws[2 * i + 1] = Q; }
-            stats[2 * i] = mf; stats[2 * i + 1] = rf;
-        }
+        const f32x2_t m = in_finalize(S, Q, HW, eps, c < C, (size_t)n * C + c, ws, stats);
+        mr[tid][0] = m[0]; mr[tid][1] = m[1];
     }
     if (!APPLY) return;
     __syncthreads();
@@ -217,33 +295,15 @@ __global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__
     }
 }
 
-// channel groups per block of the small-map kernels: 8, or 4 when 8 would leave most of the CUs without a block
-static int small_groups(int N, int C, int vec) { return (long)N * ceil_div(C, 8 * vec) < 192 ? 4 : 8; }
-// f(G as an integral_constant, the grid) for a small-map kernel of element type T
-template <typename T, typename F> static void small_launch(int N, int C, F&& f) {
-    constexpr int vec = Vec<T>::N;
-    if (small_groups(N, C, vec) == 4) f(int_c<4>{}, dim3(ceil_div(C, 4 * vec), N));
-    else f(int_c<8>{}, dim3(ceil_div(C, 8 * vec), N));
-}
-// f(mode as an integral_constant): the element-wise kernels are stamped for SPADE_STYLE and PLAIN_IN
-template <typename F> static void with_norm_mode(int mode, F&& f) {
-    if (mode == S2E_NORM_SPADE_STYLE) f(int_c<S2E_NORM_SPADE_STYLE>{});
-    else f(int_c<S2E_NORM_PLAIN_IN>{});
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void in_stats_partial_kernel(const T* __restrict__ x, float* __restrict__ part,
-                                                               int HW, int C, int cg, int cgb, int rpp, int iters,
-                                                               unsigned* __restrict__ counters, double* __restrict__ ws,
-                                                               float* __restrict__ stats, float eps) {
+                                                               int HW, int C, int cg, int cgb, int rpp, int iters) {
     constexpr int VEC = Vec<T>::N;
     __shared__ float red[256 * VEC * 2];
-    __shared__ int is_last;
     const int tid = threadIdx.x;
-    const int tx = tid % cgb, ty = tid / cgb;
-    const int g = blockIdx.z * cgb + tx;
-    const int n = blockIdx.y;
-    const bool active = ty < rpp && g < cg;
+    const RowLane t = row_lane(cg, cgb, rpp);
+    const int ty = t.ty, g = t.g, n = blockIdx.y;
+    const bool active = t.active;
     float s[VEC], q[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) { s[j] = 0.f; q[j] = 0.f; }
@@ -274,48 +334,9 @@ __global__ __launch_bounds__(256) void in_stats_partial_kernel(const T* __restri
     }
 #pragma unroll
     for (int j = 0; j < VEC; ++j) { red[(tid * VEC + j) * 2] = s[j]; red[(tid * VEC + j) * 2 + 1] = q[j]; }
-    __syncthreads();
-    if (active && ty == 0) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            float a = 0.f, b = 0.f;
-            for (int r = 0; r < rpp; ++r) {
-                a += red[((r * cgb + tx) * VEC + j) * 2];
-                b += red[((r * cgb + tx) * VEC + j) * 2 + 1];
-            }
-            float* w = part + (((size_t)n * gridDim.x + blockIdx.x) * C + g * VEC + j) * 2;     // slot [n][block][c]
-            w[0] = a; w[1] = b;
-        }
-    }
-    if (!counters) return;                                   // two-launch form: in_stats_finalize_kernel follows
-    // One-launch form: the LAST of the gridDim.x blocks of this (sample, channel range) to get here folds the partial sums --
-    // in block order, in fp64, exactly as the finalize kernel does: the same bits whichever block happens to be last.
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-        unsigned* cnt = counters + n * gridDim.z + blockIdx.z;
-        const unsigned done = atomicAdd(cnt, 1u);
-        is_last = done == gridDim.x - 1;
-        if (is_last) *cnt = 0;                               // left zero for the next launch (hipGraph replays never re-zero it)
-    }
-    __syncthreads();
-    if (!is_last) return;
-    __threadfence();
-    const int c0 = blockIdx.z * cgb * VEC, c1 = min(C, c0 + cgb * VEC), P = gridDim.x;
-    for (int c = c0 + tid; c < c1; c += 256) {
-        double sm = 0.0, q = 0.0;
-        for (int b = 0; b < P; ++b) {
-            const float* w = part + (((size_t)n * P + b) * C + c) * 2;
-            sm += (double)__builtin_nontemporal_load(w); q += (double)__builtin_nontemporal_load(w + 1);
-        }
-        const size_t i = (size_t)n * C + c;
-        ws[2 * i] = sm; ws[2 * i + 1] = q;
-        const double mean = sm / HW;
-        double var = q / HW - mean * mean;
-        if (var < 0.0) var = 0.0;
-        stats[2 * i] = (float)mean;
-        stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
+    fold_row_lanes<VEC, 2>(t, cgb, rpp, red, [&](int j, int k, float sum) __attribute__((always_inline)) {
+        part[(((size_t)n * gridDim.x + blockIdx.x) * C + g * VEC + j) * 2 + k] = sum;             // slot [n][block][c]
+    });
 }
 
 __global__ void in_stats_finalize_kernel(const float* __restrict__ part, double* __restrict__ ws, float* __restrict__ stats,
@@ -328,12 +349,7 @@ __global__ void in_stats_finalize_kernel(const float* __restrict__ part, double*
         const float* w = part + (((size_t)n * P + b) * C + c) * 2;
         s += (double)w[0]; q += (double)w[1];
     }
-    ws[2 * i] = s; ws[2 * i + 1] = q;                        // {sum x, sum x^2}: BatchNorm SPADE combines them over the batch
-    const double mean = s / HW;
-    double var = q / HW - mean * mean;
-    if (var < 0.0) var = 0.0;
-    stats[2 * i] = (float)mean;
-    stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    in_finalize(s, q, HW, eps, true, i, ws, stats);
 }
 
 // {mean, rstd} from partial sums another kernel wrote (s2e_conv2d_stats: P slots per sample, hundreds): one block per (sample, 16
@@ -364,13 +380,7 @@ __global__ __launch_bounds__(256) void in_stats_from_partials_kernel(const float
     s = 0.0; q = 0.0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) { s += red[k][cl][0]; q += red[k][cl][1]; }
-    const size_t i = (size_t)n * C + c;
-    ws[2 * i] = s; ws[2 * i + 1] = q;
-    const double mean = s / HW;
-    double var = q / HW - mean * mean;
-    if (var < 0.0) var = 0.0;
-    stats[2 * i] = (float)mean;
-    stats[2 * i + 1] = (float)(1.0 / sqrt(var + (double)eps));
+    in_finalize(s, q, HW, eps, true, (size_t)n * C + c, ws, stats);
 }
 
 extern "C" int s2e_in_stats_from_partials(const float* part, int N, int P, int C, int HW, float eps, double* ws, float* stats,
@@ -381,41 +391,21 @@ extern "C" int s2e_in_stats_from_partials(const float* part, int N, int P, int C
     return S2E_OK;
 }
 
-extern "C" size_t s2e_in_stats_workspace_bytes(int dtype, int N, int HW, int C) {
-    const int vec = s2e_vec_lanes(dtype);
-    if (N <= 0 || HW <= 0 || C <= 0 || C % vec) return 0;
-    const RowGeom g = row_geom(C, vec);
-    const int P = ceil_div(HW, g.rpp * slab_iters_for(HW, g.rpp, N, g.zblocks));
-    return (size_t)N * C * 2 * sizeof(double) + (size_t)N * P * C * 2 * sizeof(float);
-}
+extern "C" size_t s2e_in_stats_workspace_bytes(int dtype, int N, int HW, int C) { return row_plan(dtype, N, HW, C, 2).bytes; }
 
-extern "C" int s2e_in_stats_counters(int dtype, int N, int HW, int C) {
-    const int vec = s2e_vec_lanes(dtype);
-    if (N <= 0 || HW <= 0 || C <= 0 || C % vec || HW <= in_small_hw()) return 0;
-    return N * row_geom(C, vec).zblocks;
-}
-
-extern "C" int s2e_in_stats(int dtype, const void* x, int N, int HW, int C, float eps, double* ws, float* stats, unsigned* counters,
-                            void* stream) {
-    if (!x || !ws || !stats || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_in_stats: bad argument");
-    S2E_CHECK_DTYPE(dtype, "s2e_in_stats");
-    const int vec = s2e_vec_lanes(dtype);
-    if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_in_stats: C=%d not a multiple of %d", C, vec);
+extern "C" int s2e_in_stats(int dtype, const void* x, int N, int HW, int C, float eps, double* ws, float* stats, void* stream) {
+    if (const int rc = norm_prologue("s2e_in_stats", x && ws && stats, dtype, N, HW, C)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (HW <= in_small_hw())                                 // small map: statistics in one launch
         return s2e_with_dtype(dtype, "s2e_in_stats", [&](auto t) { using T = decltype(t);
             small_launch<T>(N, C, [&](auto G, dim3 sg) { in_small_kernel<T, 0, G><<<sg, 256, 0, st>>>((const T*)x, nullptr, ws, stats, HW, C, eps, 0); });
             S2E_CHECK_LAUNCH("in_small_kernel"); return S2E_OK; });
-    const RowGeom g = row_geom(C, vec);
-    const int iters = slab_iters_for(HW, g.rpp, N, g.zblocks);
-    const int P = ceil_div(HW, g.rpp * iters);
-    dim3 grid(P, N, g.zblocks);
-    float* part = (float*)(ws + (size_t)N * C * 2);          // [N][P][C][2] floats behind the N*C*2 doubles
+    const RowPlan p = row_plan(dtype, N, HW, C, 2);
+    float* part = (float*)(ws + p.part);
     if (const int rc = s2e_with_dtype(dtype, "s2e_in_stats", [&](auto t) { using T = decltype(t);
-            in_stats_partial_kernel<T><<<grid, 256, 0, st>>>((const T*)x, part, HW, C, g.cg, g.cgb, g.rpp, iters, counters, ws, stats, eps);
+            in_stats_partial_kernel<T><<<dim3(p.P, N, p.g.zblocks), 256, 0, st>>>((const T*)x, part, HW, C, p.g.cg, p.g.cgb, p.g.rpp, p.iters);
             S2E_CHECK_LAUNCH("in_stats_partial_kernel"); return S2E_OK; })) return rc;
-    if (counters) return S2E_OK;
-    in_stats_finalize_kernel<<<ceil_div((long)N * C, 256), 256, 0, st>>>(part, ws, stats, N * C, C, P, HW, eps);
+    in_stats_finalize_kernel<<<ceil_div((long)N * C, 256), 256, 0, st>>>(part, ws, stats, N * C, C, p.P, HW, eps);
     S2E_CHECK_LAUNCH("in_stats_finalize_kernel");
     return S2E_OK;
 }
@@ -427,9 +417,9 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ gsrc,
     constexpr int VEC = Vec<T>::N;
     __shared__ float red[256 * VEC];
     const int tid = threadIdx.x;
-    const int tx = tid % cgb, ty = tid / cgb;
-    const int g = blockIdx.z * cgb + tx;
-    const bool active = ty < rpp && g < cg;
+    const RowLane t = row_lane(cg, cgb, rpp);
+    const int ty = t.ty, g = t.g;
+    const bool active = t.active;
     float s[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; ++j) s[j] = 0.f;
@@ -457,15 +447,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ gsrc,
     }
 #pragma unroll
     for (int j = 0; j < VEC; ++j) red[tid * VEC + j] = s[j];
-    __syncthreads();
-    if (active && ty == 0) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) {
-            float a = 0.f;
-            for (int r = 0; r < rpp; ++r) a += red[(r * cgb + tx) * VEC + j];
-            atomicAdd(out + g * VEC + j, a);
-        }
-    }
+    fold_row_lanes<VEC, 1>(t, cgb, rpp, red, [&](int j, int, float sum) __attribute__((always_inline)) { atomicAdd(out + g * VEC + j, sum); });
 }
 template <typename T>
 __global__ void colsum_scalar_kernel(const T* __restrict__ gsrc, float* __restrict__ out, long M, int C) {
@@ -498,6 +480,31 @@ extern "C" int s2e_colsum(int dtype, const void* g, long M, int C, float* out, v
         S2E_CHECK_LAUNCH("colsum_kernel"); return S2E_OK; });
 }
 
+// ------------------------------------------------------------------------------------ the per-sample element-wise loop
+// One sample per grid row (32-bit indices, no 64-bit divisions); a grid-stride loop over the sample's vps = rows * cg
+// 16-byte vectors: body(row, c0).  When the grid stride is a multiple of cg (cg a power of two <= 256: every real layer) a
+// thread keeps its channel group over the whole loop, and its per-channel constants -- 8 of the 11 loads of an iteration,
+// 128 B of cache traffic per lane for 48 B of HBM data: the backward's pass ran at 60 % of the HBM rate -- are loaded ONCE,
+// by consts(c0).
+template <int VEC, typename Consts, typename Body>
+__device__ __forceinline__ void sample_vectors(int vps, int cg, int cg_shift, Consts&& consts, Body&& body) {
+    const bool fixed_g = cg_shift >= 0 && cg <= 256;
+    if (fixed_g) consts((threadIdx.x & (cg - 1)) * VEC);
+    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < vps; v += gridDim.x * blockDim.x) {
+        const int prow = cg_shift >= 0 ? v >> cg_shift : v / cg;
+        const int c0 = (v - prow * cg) * VEC;
+        if (!fixed_g) consts(c0);
+        body(prow, c0);
+    }
+}
+// its grid: enough blocks for a vector per thread, at most 8192 over the N samples
+static dim3 sample_grid(int vps, int N) { return dim3(s2e_grid1d(vps, 8192 / N > 1 ? 8192 / N : 1), N); }
+// f(mode as an integral_constant): the element-wise kernels are stamped for SPADE_STYLE and PLAIN_IN
+template <typename F> static void with_norm_mode(int mode, F&& f) {
+    if (mode == S2E_NORM_SPADE_STYLE) f(int_c<S2E_NORM_SPADE_STYLE>{});
+    else f(int_c<S2E_NORM_PLAIN_IN>{});
+}
+
 // ------------------------------------------------------------------------------------ modulation forward
 // pre = sc*(xhat*G + beta) + ssc*(x*a + b);   SPADE_STYLE: sc = ssc = 0.5, G = 1+gamma, a = 1+s0, b = s1
 //                                             PLAIN_IN   : sc = 1, ssc = 0, G = 1, beta = 0
@@ -506,14 +513,9 @@ __global__ __launch_bounds__(256) void modulate_fwd_kernel(const T* __restrict__
                                                            const float* __restrict__ stats, const float* __restrict__ style,
                                                            T* __restrict__ out, int HW, int C, int cg, int cg_shift, int lrelu, int sld) {
     constexpr int VEC = Vec<T>::N;
-    // One sample per grid row (32-bit indices, no 64-bit divisions).  When the grid stride is a multiple of cg (cg a
-    // power of two <= 256: every real layer) a thread keeps its channel group over the whole loop, and its per-channel
-    // constants -- mean, rstd, 1 + s0, s1: 8 of the 11 loads of an iteration -- are loaded once.
     const int n = blockIdx.y;
-    const int vps = HW * cg;                               // 16-byte vectors per sample
-    const bool fixed_g = cg_shift >= 0 && cg <= 256;
-    float mu[VEC], rs[VEC], sa[VEC], sb[VEC];
-    auto load_consts = [&](int c0) __attribute__((always_inline)) {
+    float mu[VEC], rs[VEC], sa[VEC], sb[VEC];              // mean, rstd, 1 + s0, s1
+    sample_vectors<VEC>(HW * cg, cg, cg_shift, [&](int c0) __attribute__((always_inline)) {
         const float* stp = stats + ((size_t)n * C + c0) * 2;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) { mu[j] = stp[2 * j]; rs[j] = stp[2 * j + 1]; }
@@ -522,14 +524,8 @@ __global__ __launch_bounds__(256) void modulate_fwd_kernel(const T* __restrict__
 #pragma unroll
             for (int j = 0; j < VEC; ++j) { sa[j] = 1.f + s0[j]; sb[j] = s0[C + j]; }
         }
-    };
-    if (fixed_g) load_consts((threadIdx.x & (cg - 1)) * VEC);
-    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < vps; v += gridDim.x * blockDim.x) {
-        const int prow = cg_shift >= 0 ? v >> cg_shift : v / cg;
-        const int g = v - prow * cg;
+    }, [&](int prow, int c0) __attribute__((always_inline)) {
         const size_t row = (size_t)n * HW + prow;
-        const int c0 = g * VEC;
-        if (!fixed_g) load_consts(c0);
         float f[VEC], o[VEC];
         unpack16<T>(*(const u32x4_t*)(x + row * C + c0), f);
         if (MODE == S2E_NORM_SPADE_STYLE) {
@@ -550,24 +546,17 @@ __global__ __launch_bounds__(256) void modulate_fwd_kernel(const T* __restrict__
             for (int j = 0; j < VEC; ++j) o[j] = lrelu02(o[j]);
         }
         *(u32x4_t*)(out + row * C + c0) = pack16<T>(o);
-    }
+    });
 }
 
 extern "C" int s2e_modulate_fwd(int dtype, int mode, const void* x, const void* gb, const float* stats, const float* style,
                                 void* out, int N, int HW, int C, int lrelu, int style_ld, void* stream) {
-    if (!x || !stats || !out || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_fwd: bad argument");
-    if (mode == S2E_NORM_SPADE_STYLE && (!gb || !style)) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_fwd: SPADE_STYLE needs gb and style");
-    S2E_CHECK_DTYPE(dtype, "s2e_modulate_fwd");
-    const int vec = s2e_vec_lanes(dtype);
-    if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_modulate_fwd: C=%d not a multiple of %d", C, vec);
-    const int cg = C / vec;
+    if (const int rc = norm_prologue("s2e_modulate_fwd", x && stats && out, dtype, N, HW, C,
+                                     mode == S2E_NORM_SPADE_STYLE && (!gb || !style) ? "SPADE_STYLE needs gb and style" : nullptr)) return rc;
+    const int cg = C / s2e_vec_lanes(dtype);
     const int sld = style_ld > 0 ? style_ld : 2 * C;
     if ((long)HW * cg >= (1L << 31)) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_modulate_fwd: sample too large for 32-bit indices");
-    const int vps = HW * cg;
-    int gx = (vps + 255) / 256;
-    const int gx_cap = 8192 / N > 1 ? 8192 / N : 1;
-    if (gx > gx_cap) gx = gx_cap;
-    const dim3 grid(gx, N);
+    const dim3 grid = sample_grid(HW * cg, N);
     const int cg_shift = s2e_pow2_shift(cg);
     hipStream_t st = (hipStream_t)stream;
     return s2e_with_dtype(dtype, "s2e_modulate_fwd", [&](auto t) { using T = decltype(t);
@@ -586,17 +575,16 @@ __global__ __launch_bounds__(256) void modulate_bwd_reduce_kernel(const T* __res
         const T* __restrict__ gb, const float* __restrict__ stats, const float* __restrict__ style,
         T* __restrict__ dgb, float* __restrict__ part, int HW, int C, int cg, int cgb, int rpp, int lrelu, int sld, int iters,
         const T* __restrict__ fout, int xw, float inv_xw) {
-    // fout != NULL (S2E_NORM_GAMMA_ONLY): gb holds gamma alone, (N,HW,C); the LeakyReLU mask comes from the sign of the
+    // fout != NULL (the gamma-only form): gb holds gamma alone, (N,HW,C); the LeakyReLU mask comes from the sign of the
     // forward's OUTPUT fout (LeakyReLU keeps the sign of its argument) instead of recomputing it from gamma and beta
     constexpr int VEC = Vec<T>::N;
     constexpr int NS = (MODE == S2E_NORM_SPADE_STYLE) ? 4 : 2;
     const int gst = fout ? C : 2 * C;                      // pixels of gb are this many elements apart
     __shared__ float red[256 * VEC * NS];
     const int tid = threadIdx.x;
-    const int tx = tid % cgb, ty = tid / cgb;
-    const int g = blockIdx.z * cgb + tx;
-    const int n = blockIdx.y;
-    const bool active = ty < rpp && g < cg;
+    const RowLane t = row_lane(cg, cgb, rpp);
+    const int ty = t.ty, g = t.g, n = blockIdx.y;
+    const bool active = t.active;
     float S[NS][VEC];
 #pragma unroll
     for (int k = 0; k < NS; ++k)
@@ -702,17 +690,9 @@ __global__ __launch_bounds__(256) void modulate_bwd_reduce_kernel(const T* __res
     for (int k = 0; k < NS; ++k)
 #pragma unroll
         for (int j = 0; j < VEC; ++j) red[(tid * VEC + j) * NS + k] = S[k][j];
-    __syncthreads();
-    if (active && ty == 0) {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j)
-#pragma unroll
-            for (int k = 0; k < NS; ++k) {
-                float acc = 0.f;
-                for (int r = 0; r < rpp; ++r) acc += red[((r * cgb + tx) * VEC + j) * NS + k];
-                part[(((size_t)n * gridDim.x + blockIdx.x) * C + g * VEC + j) * 4 + k] = acc;      // slot [n][block][c][k]
-            }
-    }
+    fold_row_lanes<VEC, NS>(t, cgb, rpp, red, [&](int j, int k, float sum) __attribute__((always_inline)) {
+        part[(((size_t)n * gridDim.x + blockIdx.x) * C + g * VEC + j) * 4 + k] = sum;             // slot [n][block][c][k]
+    });
 }
 
 // Per-(n,c) coefficients of pass 2, computed once by modulate_bwd_coef_kernel and stored as one float4 per channel in
@@ -724,7 +704,7 @@ __global__ __launch_bounds__(256) void modulate_bwd_reduce_kernel(const T* __res
 // fp64 conversions: it was VALU-issue-bound (22 loads and ~350 instructions per 16-byte vector), not HBM-bound.
 // batch != 0 (BatchNorm SPADE: statistics over the whole batch): S0, S1 are summed over the samples and HW -> N*HW.
 // ws: (N,C,4) fp64 sums.  part != NULL: they are first formed here from the blocks' partial slots ([N][P][C][4] floats, added in
-// a fixed order: bit-reproducible); part == NULL: ws already holds them (second stage of s2e_modulate_bwd_staged).
+// a fixed order: bit-reproducible); part == NULL: ws already holds them (stage 2 of s2e_modulate_bwd).
 template <int MODE>
 __global__ void modulate_bwd_sums_kernel(const float* __restrict__ part, double* __restrict__ ws, int N, int C, int P) {
     constexpr int NS = (MODE == S2E_NORM_SPADE_STYLE) ? 4 : 2;
@@ -798,30 +778,16 @@ __global__ __launch_bounds__(256) void modulate_bwd_apply_kernel(const T* __rest
         const T* __restrict__ gb, const T* __restrict__ dgb, const f32x4_t* __restrict__ coef, T* dx, const T* dxa,
         int vps, int HW, int C, int cg, int cg_shift, int lrelu, int acc, int gst, int xw, float inv_xw) {
     constexpr int VEC = Vec<T>::N;
-    const int n = blockIdx.y;                              // one sample per grid row: 32-bit indices, no 64-bit division
-    // The channel group of a thread does not change over the grid-stride loop when the stride is a multiple of cg
-    // (cg a power of two <= 256: every real layer): its 8 x float4 coefficients are then loaded ONCE.  Loaded per vector
-    // they are 8 of the 11 loads of an iteration -- 128 B of cache traffic per lane for 48 B of HBM data -- and the kernel
-    // ran at 60 % of the HBM rate.
-    const bool fixed_g = cg_shift >= 0 && cg <= 256;
+    const int n = blockIdx.y;
     f32x4_t K[VEC];
-    if (fixed_g) {
-        const f32x4_t* kp = coef + (size_t)n * C + (threadIdx.x & (cg - 1)) * VEC;
+    sample_vectors<VEC>(vps, cg, cg_shift, [&](int c0) __attribute__((always_inline)) {
+        const f32x4_t* kp = coef + (size_t)n * C + c0;
 #pragma unroll
         for (int j = 0; j < VEC; ++j) K[j] = kp[j];
-    }
-    for (int v = blockIdx.x * blockDim.x + threadIdx.x; v < vps; v += gridDim.x * blockDim.x) {
-        const int prow = cg_shift >= 0 ? v >> cg_shift : v / cg;
-        const int g = v - prow * cg;
+    }, [&](int prow, int c0) __attribute__((always_inline)) {
         const size_t row = (size_t)n * HW + prow;
-        const int c0 = g * VEC;
         float f[VEC], o[VEC];
         unpack16<T>(*(const u32x4_t*)(x + mod_x_row(n, prow, HW, xw, inv_xw) * C + c0), f);
-        if (!fixed_g) {
-            const f32x4_t* kp = coef + (size_t)n * C + c0;
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) K[j] = kp[j];
-        }
         if (MODE == S2E_NORM_SPADE_STYLE) {
             float ga[VEC], dbe[VEC];
             unpack16<T>(*(const u32x4_t*)(gb + row * gst + c0), ga);
@@ -845,7 +811,7 @@ __global__ __launch_bounds__(256) void modulate_bwd_apply_kernel(const T* __rest
             for (int j = 0; j < VEC; ++j) o[j] += prev[j];
         }
         *(u32x4_t*)(dx + row * C + c0) = pack16<T>(o);
-    }
+    });
 }
 
 // The element-wise pass when x is the half-resolution tensor (xw != 0) AND the caller wants the gradient w.r.t. THAT tensor:
@@ -1036,10 +1002,14 @@ __global__ __launch_bounds__(256) void spade_small_bwd_kernel(const T* __restric
     }
 }
 
-static int modulate_bwd_impl(int dtype, int mode, const void* g, const void* x, const void* gb, const void* fout, const float* stats,
-                             const float* style, void* dx, void* dgb, float* dstyle, double* ws,
-                             int N, int HW, int C, int lrelu, int style_ld, void* stream, int stage = 0, double batch_count = 0.0,
-                             int xw = 0, int quad = 0, const void* dx_add = nullptr) {
+// The one entry point of the backward (include/seg2eye_hip.h describes it): fout = the header's `out`, xw = x_up_w, quad = dx_quad.
+extern "C" int s2e_modulate_bwd(int dtype, int mode, const void* g, const void* x, const void* gb, const void* fout, const float* stats,
+                                const float* style, void* dx, const void* dx_add, void* dgb, float* dstyle, double* ws,
+                                int N, int HW, int C, int lrelu, int style_ld, int stage, double batch_count, int xw, int quad, void* stream) {
+    if (stage < 0 || stage > 2) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: stage %d", stage);
+    if (dx_add && dx_add != dx && !(mode & S2E_NORM_ACCUMULATE_DX)) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: dx_add apart from dx needs S2E_NORM_ACCUMULATE_DX");
+    if (fout && (mode & ~S2E_NORM_ACCUMULATE_DX) != S2E_NORM_SPADE_STYLE && (mode & ~S2E_NORM_ACCUMULATE_DX) != S2E_NORM_SPADE_STYLE_BATCH)
+        S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: out (the gamma-only form) goes with the SPADE_STYLE modes only");
     if (!dx_add) dx_add = dx;                              // S2E_NORM_ACCUMULATE_DX: dx = dx_add + this layer's gradient (in place unless told otherwise)
     const int sld = style_ld > 0 ? style_ld : 2 * C;
     const int gst = fout ? C : 2 * C;
@@ -1047,12 +1017,8 @@ static int modulate_bwd_impl(int dtype, int mode, const void* g, const void* x, 
     mode &= ~S2E_NORM_ACCUMULATE_DX;
     const int batch = mode == S2E_NORM_SPADE_STYLE_BATCH;
     if (batch) mode = S2E_NORM_SPADE_STYLE;                // same passes; only the coefficient kernel sums over the batch
-    if (!g || !x || !stats || !dx || !ws || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: bad argument");
-    if (mode == S2E_NORM_SPADE_STYLE && (!gb || !style || !dgb || !dstyle))
-        S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd: SPADE_STYLE needs gb, style, dgb, dstyle");
-    S2E_CHECK_DTYPE(dtype, "s2e_modulate_bwd");
-    const int vec = s2e_vec_lanes(dtype);
-    if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_modulate_bwd: C=%d not a multiple of %d", C, vec);
+    if (const int rc = norm_prologue("s2e_modulate_bwd", g && x && stats && dx && ws, dtype, N, HW, C,
+                                     mode == S2E_NORM_SPADE_STYLE && (!gb || !style || !dgb || !dstyle) ? "SPADE_STYLE needs gb, style, dgb, dstyle" : nullptr)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const float inv_xw = xw ? 1.f / (float)xw : 0.f;
     if (xw && (!fout || batch || stage != 0 || HW % xw || ((HW / xw) | xw) & 1))
@@ -1064,82 +1030,33 @@ static int modulate_bwd_impl(int dtype, int mode, const void* g, const void* x, 
                 spade_small_bwd_kernel<T, G><<<sg, 256, 0, st>>>((const T*)g, (const T*)x, (const T*)gb, (const T*)fout, stats, style, (T*)dx, (const T*)dx_add,
                                                                   (T*)dgb, dstyle, HW, C, lrelu, sld, acc, xw, inv_xw, quad); });
             S2E_CHECK_LAUNCH("spade_small_bwd_kernel"); return S2E_OK; });
-    const RowGeom rg = row_geom(C, vec);
-    const int iters = slab_iters_for(HW, rg.rpp, N, rg.zblocks);
-    dim3 grid1(ceil_div(HW, rg.rpp * iters), N, rg.zblocks);
+    const RowPlan p = row_plan(dtype, N, HW, C, 4);
+    const RowGeom& rg = p.g;
     if ((long)HW * rg.cg >= (1L << 31)) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_modulate_bwd: sample too large for 32-bit indices");
     const int vps = HW * rg.cg;                            // 16-byte vectors per sample
-    int gx = (vps + 255) / 256;
-    const int gx_cap = 8192 / N > 1 ? 8192 / N : 1;
-    if (gx > gx_cap) gx = gx_cap;
-    dim3 grid2(gx, N);
     const int cg_shift = s2e_pow2_shift(rg.cg);
     const int gridc = ceil_div((long)N * C, 256);
-    f32x4_t* coef = (f32x4_t*)(ws + (size_t)N * C * 4);
-    const int P = (int)grid1.x;                            // partial-sum slots per sample
-    float* part = (float*)(ws + (size_t)N * C * 6);        // [N][P][C][4] floats behind the sums and the coefficients
+    f32x4_t* coef = (f32x4_t*)(ws + p.coef);
+    float* part = (float*)(ws + p.part);
     // the sums of ALL samples must be complete before the batch-statistics coefficients read them, and a staged call hands
     // them to the caller between the stages: a separate (tiny) launch then; otherwise the coefficient kernel adds up its own
     const bool sums_first = batch || stage == 1;
     return s2e_with_dtype(dtype, "s2e_modulate_bwd", [&](auto t) { using T = decltype(t);
         with_norm_mode(mode, [&](auto MM) {
             if (stage != 2) {
-                modulate_bwd_reduce_kernel<T, MM><<<grid1, 256, 0, st>>>((const T*)g, (const T*)x, (const T*)gb, stats, style, (T*)dgb, part, HW, C, rg.cg, rg.cgb, rg.rpp, lrelu, sld, iters, (const T*)fout, xw, inv_xw);
-                if (sums_first) modulate_bwd_sums_kernel<MM><<<gridc, 256, 0, st>>>(part, ws, N, C, P);
+                modulate_bwd_reduce_kernel<T, MM><<<dim3(p.P, N, rg.zblocks), 256, 0, st>>>((const T*)g, (const T*)x, (const T*)gb, stats, style, (T*)dgb, part, HW, C, rg.cg, rg.cgb, rg.rpp, lrelu, sld, p.iters, (const T*)fout, xw, inv_xw);
+                if (sums_first) modulate_bwd_sums_kernel<MM><<<gridc, 256, 0, st>>>(part, ws, N, C, p.P);
             }
             if (stage == 1) return;
-            modulate_bwd_coef_kernel<MM><<<gridc, 256, 0, st>>>(ws, (stage == 2 || sums_first) ? nullptr : part, P, coef, stats, style, dstyle, N, C, HW, sld, batch, batch_count);
-            if (quad) {
-                const int gq = ((HW >> 2) * rg.cg + 255) / 256;
-                modulate_bwd_apply_quad_kernel<T><<<dim3(gq < gx_cap ? gq : gx_cap, N), 256, 0, st>>>((const T*)x, (const T*)gb, (const T*)dgb, coef, (T*)dx, (const T*)dx_add, HW, C, rg.cg, acc, gst, xw, 2.f * inv_xw);
-            } else modulate_bwd_apply_kernel<T, MM><<<grid2, 256, 0, st>>>((const T*)g, (const T*)x, (const T*)gb, (const T*)dgb, coef, (T*)dx, (const T*)dx_add, vps, HW, C, rg.cg, cg_shift, lrelu, acc, gst, xw, inv_xw);
+            modulate_bwd_coef_kernel<MM><<<gridc, 256, 0, st>>>(ws, (stage == 2 || sums_first) ? nullptr : part, p.P, coef, stats, style, dstyle, N, C, HW, sld, batch, batch_count);
+            if (quad)
+                modulate_bwd_apply_quad_kernel<T><<<sample_grid((HW >> 2) * rg.cg, N), 256, 0, st>>>((const T*)x, (const T*)gb, (const T*)dgb, coef, (T*)dx, (const T*)dx_add, HW, C, rg.cg, acc, gst, xw, 2.f * inv_xw);
+            else modulate_bwd_apply_kernel<T, MM><<<sample_grid(vps, N), 256, 0, st>>>((const T*)g, (const T*)x, (const T*)gb, (const T*)dgb, coef, (T*)dx, (const T*)dx_add, vps, HW, C, rg.cg, cg_shift, lrelu, acc, gst, xw, inv_xw);
         });
         S2E_CHECK_LAUNCH("modulate_bwd kernels"); return S2E_OK; });
 }
 
-extern "C" int s2e_modulate_bwd(int dtype, int mode, const void* g, const void* x, const void* gb, const float* stats,
-                                const float* style, void* dx, void* dgb, float* dstyle, double* ws,
-                                int N, int HW, int C, int lrelu, int style_ld, void* stream) {
-    return modulate_bwd_impl(dtype, mode, g, x, gb, nullptr, stats, style, dx, dgb, dstyle, ws, N, HW, C, lrelu, style_ld, stream);
-}
-
-extern "C" int s2e_modulate_bwd_gamma(int dtype, int mode, const void* g, const void* x, const void* gamma, const void* out,
-                                      const float* stats, const float* style, void* dx, void* dgb, float* dstyle, double* ws,
-                                      int N, int HW, int C, int lrelu, int style_ld, void* stream) {
-    const int m = mode & ~S2E_NORM_ACCUMULATE_DX;
-    if (m != S2E_NORM_SPADE_STYLE && m != S2E_NORM_SPADE_STYLE_BATCH) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd_gamma: SPADE_STYLE modes only");
-    if (!gamma || !out) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd_gamma: gamma and out are required");
-    return modulate_bwd_impl(dtype, mode, g, x, gamma, out, stats, style, dx, dgb, dstyle, ws, N, HW, C, lrelu, style_ld, stream);
-}
-
-extern "C" int s2e_modulate_bwd_staged(int dtype, int mode, const void* g, const void* x, const void* gb, const void* out,
-                                       const float* stats, const float* style, void* dx, void* dgb, float* dstyle, double* ws,
-                                       int N, int HW, int C, int lrelu, int style_ld, int stage, double batch_count, int x_up_w,
-                                       int dx_quad, void* stream) {
-    if (stage < 0 || stage > 2) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd_staged: stage %d", stage);
-    return modulate_bwd_impl(dtype, mode, g, x, gb, out, stats, style, dx, dgb, dstyle, ws, N, HW, C, lrelu, style_ld, stream, stage, batch_count,
-                             x_up_w, dx_quad);
-}
-
-// s2e_modulate_bwd_staged with the accumulated-into tensor and the result apart: dx = dx_add + this layer's gradient (mode must carry
-// S2E_NORM_ACCUMULATE_DX; dx_add == dx or NULL is the in-place form)
-extern "C" int s2e_modulate_bwd_relay(int dtype, int mode, const void* g, const void* x, const void* gb, const void* out,
-                                      const float* stats, const float* style, void* dx, const void* dx_add, void* dgb, float* dstyle, double* ws,
-                                      int N, int HW, int C, int lrelu, int style_ld, int stage, double batch_count, int x_up_w,
-                                      int dx_quad, void* stream) {
-    if (stage < 0 || stage > 2) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd_relay: stage %d", stage);
-    if (!(mode & S2E_NORM_ACCUMULATE_DX)) S2E_FAIL(S2E_ERR_ARG, "s2e_modulate_bwd_relay: mode without S2E_NORM_ACCUMULATE_DX");
-    return modulate_bwd_impl(dtype, mode, g, x, gb, out, stats, style, dx, dgb, dstyle, ws, N, HW, C, lrelu, style_ld, stream, stage, batch_count,
-                             x_up_w, dx_quad, dx_add);
-}
-
-extern "C" size_t s2e_modulate_bwd_workspace_bytes(int dtype, int N, int HW, int C) {
-    const int vec = s2e_vec_lanes(dtype);
-    if (N <= 0 || HW <= 0 || C <= 0 || C % vec) return 0;
-    const RowGeom rg = row_geom(C, vec);
-    const int P = ceil_div(HW, rg.rpp * slab_iters_for(HW, rg.rpp, N, rg.zblocks));
-    return (size_t)N * C * 6 * sizeof(double) + (size_t)N * P * C * 4 * sizeof(float);
-}
+extern "C" size_t s2e_modulate_bwd_workspace_bytes(int dtype, int N, int HW, int C) { return row_plan(dtype, N, HW, C, 4).bytes; }
 
 // ------------------------------------------------------------------------------------ plain InstanceNorm (+ LeakyReLU), whole op
 // out = [lrelu 0.2]((x - mean) * rstd) per (sample, channel) over HW (InstanceNorm2d(affine=False), discriminator.py:91-94,
@@ -1147,30 +1064,24 @@ extern "C" size_t s2e_modulate_bwd_workspace_bytes(int dtype, int N, int HW, int
 // statistics kernels, then the element-wise kernel.  ws: s2e_in_stats_workspace_bytes.
 extern "C" int s2e_instance_norm_fwd(int dtype, const void* x, void* out, float* stats, double* ws, int N, int HW, int C,
                                      float eps, int lrelu, void* stream) {
-    if (!x || !out || !stats || !ws || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_instance_norm_fwd: bad argument");
-    S2E_CHECK_DTYPE(dtype, "s2e_instance_norm_fwd");
-    const int vec = s2e_vec_lanes(dtype);
-    if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_instance_norm_fwd: C=%d not a multiple of %d", C, vec);
+    if (const int rc = norm_prologue("s2e_instance_norm_fwd", x && out && stats && ws, dtype, N, HW, C)) return rc;
     if (HW <= in_small_hw())
         return s2e_with_dtype(dtype, "s2e_instance_norm_fwd", [&](auto t) { using T = decltype(t);
             small_launch<T>(N, C, [&](auto G, dim3 sg) {
                 in_small_kernel<T, 1, G><<<sg, 256, 0, (hipStream_t)stream>>>((const T*)x, (T*)out, ws, stats, HW, C, eps, lrelu); });
             S2E_CHECK_LAUNCH("in_small_kernel"); return S2E_OK; });
-    if (const int rc = s2e_in_stats(dtype, x, N, HW, C, eps, ws, stats, nullptr, stream)) return rc;
+    if (const int rc = s2e_in_stats(dtype, x, N, HW, C, eps, ws, stats, stream)) return rc;
     return s2e_modulate_fwd(dtype, S2E_NORM_PLAIN_IN, x, nullptr, stats, nullptr, out, N, HW, C, lrelu, 0, stream);
 }
 
 // its backward: dx from g, x and the forward's stats.  ws: s2e_modulate_bwd_workspace_bytes (unused for small maps).
 extern "C" int s2e_instance_norm_bwd(int dtype, const void* g, const void* x, const float* stats, void* dx, double* ws,
                                      int N, int HW, int C, int lrelu, void* stream) {
-    if (!g || !x || !stats || !dx || N <= 0 || HW <= 0 || C <= 0) S2E_FAIL(S2E_ERR_ARG, "s2e_instance_norm_bwd: bad argument");
-    S2E_CHECK_DTYPE(dtype, "s2e_instance_norm_bwd");
-    const int vec = s2e_vec_lanes(dtype);
-    if (C % vec) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_instance_norm_bwd: C=%d not a multiple of %d", C, vec);
+    if (const int rc = norm_prologue("s2e_instance_norm_bwd", g && x && stats && dx, dtype, N, HW, C)) return rc;
     if (HW <= in_small_hw())
         return s2e_with_dtype(dtype, "s2e_instance_norm_bwd", [&](auto t) { using T = decltype(t);
             small_launch<T>(N, C, [&](auto G, dim3 sg) {
                 in_small_bwd_kernel<T, G><<<sg, 256, 0, (hipStream_t)stream>>>((const T*)g, (const T*)x, stats, (T*)dx, HW, C, lrelu); });
             S2E_CHECK_LAUNCH("in_small_bwd_kernel"); return S2E_OK; });
-    return s2e_modulate_bwd(dtype, S2E_NORM_PLAIN_IN, g, x, nullptr, stats, nullptr, dx, nullptr, nullptr, ws, N, HW, C, lrelu, 0, stream);
+    return s2e_modulate_bwd(dtype, S2E_NORM_PLAIN_IN, g, x, nullptr, nullptr, stats, nullptr, dx, nullptr, nullptr, nullptr, ws, N, HW, C, lrelu, 0, 0, 0.0, 0, 0, stream);
 }

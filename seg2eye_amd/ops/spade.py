@@ -22,8 +22,7 @@ def in_stats(x, return_sums=False):
     n, h, w, c = x.shape
     ws = torch.empty(L.call.s2e_in_stats_workspace_bytes(_dt(x), n, h * w, c) // 8, dtype=torch.float64, device=x.device)
     stats = torch.empty(n, c, 2, dtype=torch.float32, device=x.device)
-    cnt = None          # (the C ABI's one-launch form -- zeroed block counters -- measured slower: include/seg2eye_hip.h)
-    LaunchProfiler.run('in_stats', 0.0, L.call.s2e_in_stats, (_dt(x), _p(x), n, h * w, c, IN_EPS, _p(ws), _p(stats), _p(cnt), _stream()),
+    LaunchProfiler.run('in_stats', 0.0, L.call.s2e_in_stats, (_dt(x), _p(x), n, h * w, c, IN_EPS, _p(ws), _p(stats), _stream()),
                        nbytes=float(x.numel() * x.element_size()))                   # algorithmic: x read once
     return (stats, ws[:n * c * 2].view(n, c, 2)) if return_sums else stats
 
@@ -482,7 +481,7 @@ class ModulateFn(torch.autograd.Function):
 
 def _modulate_grads(ctx, g, g_relay, x, gb, fout, style, stats):
     """Backward of the SPADE+Style modulation -> (dx, dgb (N,h,w,2C), dstyle or None).  fout None: gb = [gamma | beta];
-    else gb = gamma alone and fout = the forward's output (s2e_modulate_bwd_gamma).
+    else gb = gamma alone and fout = the forward's output (s2e_modulate_bwd's gamma-only form).
     relay: the OTHER consumers of x hang off the node's second output, so their gradient arrives here first and the
     element-wise pass adds this layer's dx to it in place -- instead of autograd summing two full tensors."""
     n, h, w, c = (fout if fout is not None else x).shape          # (x may be the half-resolution tensor: ctx.x_up_w; dx then is too)
@@ -512,11 +511,9 @@ def _modulate_grads(ctx, g, g_relay, x, gb, fout, style, stats):
     world = sdist.sync_world_size() if ctx.batch else 1
 
     def launch(stage, count):
-        head = (_dt(x), mode, _p(g), _p(x), _p(gb), _p(fout), _p(stats), sp, _p(dx))
-        tail = (_p(dgb), dsp, _p(ws), n, h * w, c, int(ctx.lrelu), ld, stage, float(count), int(getattr(ctx, 'x_up_w', 0)), quad, _stream())
-        if apart:                                            # (the relay form takes g_relay between dx and dgb, and is otherwise the staged one)
-            return L.call.s2e_modulate_bwd_relay(*head, _p(g_relay), *tail)
-        return L.call.s2e_modulate_bwd_staged(*head, *tail)
+        return L.call.s2e_modulate_bwd(_dt(x), mode, _p(g), _p(x), _p(gb), _p(fout), _p(stats), sp, _p(dx), _p(g_relay) if apart else None,
+                                       _p(dgb), dsp, _p(ws), n, h * w, c, int(ctx.lrelu), ld, stage, float(count), int(getattr(ctx, 'x_up_w', 0)),
+                                       quad, _stream())
     if world == 1:
         LaunchProfiler.run('modulate_bwd', 0.0, launch, (0, 0.0), nbytes=nb)
     else:

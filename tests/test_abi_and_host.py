@@ -460,10 +460,10 @@ HOST_ERROR_TABLE = [
     ('s2e_spade_modulate_uniform', (F32, P, P, P, 0, P, P, P, P, P, None, 1, 16, 16, 6, 8, 8, 1, 0, None), -3, 's2e_spade_modulate_uniform: C=6 not a multiple of 4'),
     ('s2e_spade_uniform_sums', (BF16, None, 1, 64, 64, 128, 4, P, P, P, P, None), -1, 's2e_spade_uniform_sums: null pointer'),
     ('s2e_spade_uniform_sums', (BAD, P, 1, 64, 64, 128, 4, P, P, P, P, None), -1, 's2e_spade_uniform_sums: bad dtype 7'),
-    ('s2e_in_stats', (BF16, None, 1, 64, 8, 1e-05, P, P, None, None), -1, 's2e_in_stats: bad argument'),
-    ('s2e_in_stats', (BAD, P, 1, 64, 8, 1e-05, P, P, None, None), -1, 's2e_in_stats: bad dtype 7'),
-    ('s2e_in_stats', (BF16, P, 1, 64, 12, 1e-05, P, P, None, None), -3, 's2e_in_stats: C=12 not a multiple of 8'),
-    ('s2e_in_stats', (F32, P, 1, 64, 6, 1e-05, P, P, None, None), -3, 's2e_in_stats: C=6 not a multiple of 4'),
+    ('s2e_in_stats', (BF16, None, 1, 64, 8, 1e-05, P, P, None), -1, 's2e_in_stats: bad argument'),
+    ('s2e_in_stats', (BAD, P, 1, 64, 8, 1e-05, P, P, None), -1, 's2e_in_stats: bad dtype 7'),
+    ('s2e_in_stats', (BF16, P, 1, 64, 12, 1e-05, P, P, None), -3, 's2e_in_stats: C=12 not a multiple of 8'),
+    ('s2e_in_stats', (F32, P, 1, 64, 6, 1e-05, P, P, None), -3, 's2e_in_stats: C=6 not a multiple of 4'),
     ('s2e_colsum', (BF16, None, 10, 8, P, None), -1, 's2e_colsum: bad argument'),
     ('s2e_colsum', (BAD, P, 10, 8, P, None), -1, 's2e_colsum: bad dtype 7'),
     ('s2e_colsum', (BAD, P, 10, 3, P, None), -1, 's2e_colsum: bad dtype 7'),
@@ -473,30 +473,30 @@ HOST_ERROR_TABLE = [
     ('s2e_modulate_fwd', (BAD, 0, P, None, P, None, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_fwd: SPADE_STYLE needs gb and style'),
     ('s2e_modulate_fwd', (BF16, 1, P, None, P, None, P, 1, 64, 12, 0, 0, None), -3, 's2e_modulate_fwd: C=12 not a multiple of 8'),
     ('s2e_modulate_fwd', (F32, 1, P, None, P, None, P, 1, 64, 6, 0, 0, None), -3, 's2e_modulate_fwd: C=6 not a multiple of 4'),
-    ('s2e_modulate_bwd', (BF16, 1, P, P, None, P, None, P, None, None, None, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
-    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, P, P, None, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: SPADE_STYLE needs gb, style, dgb, dstyle'),
-    ('s2e_modulate_bwd', (BAD, 1, P, P, None, P, None, P, None, None, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
-    ('s2e_modulate_bwd', (BF16, 1, P, P, None, P, None, P, None, None, P, 1, 64, 12, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
-    ('s2e_modulate_bwd', (F32, 1, P, P, None, P, None, P, None, None, P, 1, 64, 6, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
-    ('s2e_modulate_bwd_gamma', (BF16, 1, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd_gamma: SPADE_STYLE modes only'),
-    ('s2e_modulate_bwd_gamma', (BF16, 0, P, P, None, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd_gamma: gamma and out are required'),
-    ('s2e_modulate_bwd_gamma', (BF16, 0, P, P, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
-    ('s2e_modulate_bwd_gamma', (BAD, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
-    ('s2e_modulate_bwd_gamma', (BF16, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 12, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
-    ('s2e_modulate_bwd_gamma', (F32, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 6, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
-    ('s2e_modulate_bwd_staged', (BF16, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 3, 0.0, 0, 0, None), -1, 's2e_modulate_bwd_staged: stage 3'),
-    ('s2e_modulate_bwd_staged', (BF16, 0, P, P, P, P, None, P, P, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
-    ('s2e_modulate_bwd_staged', (BAD, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
-    ('s2e_modulate_bwd_staged', (BAD, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 8, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
-    ('s2e_modulate_bwd_staged', (BF16, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 12, 0, 0, 1, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
-    ('s2e_modulate_bwd_staged', (F32, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 6, 0, 0, 1, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
-    ('s2e_modulate_bwd_staged', (BF16, 0, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 8, 0, None), -1, 's2e_modulate_bwd: x at half resolution needs the gamma-only form, per-sample statistics and an even H x W map'),
-    ('s2e_modulate_bwd_relay', (BF16, SP | ACC, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 3, 0.0, 0, 0, None), -1, 's2e_modulate_bwd_relay: stage 3'),
-    ('s2e_modulate_bwd_relay', (BF16, 0, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd_relay: mode without S2E_NORM_ACCUMULATE_DX'),
-    ('s2e_modulate_bwd_relay', (BF16, SP | ACC, P, P, P, P, P, P, None, P, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
-    ('s2e_modulate_bwd_relay', (BAD, SP | ACC, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
-    ('s2e_modulate_bwd_relay', (BF16, SP | ACC, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 12, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
-    ('s2e_modulate_bwd_relay', (F32, SP | ACC, P, P, P, P, P, P, P, P, P, P, P, 1, 64, 6, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
+    ('s2e_modulate_bwd', (BF16, 1, P, P, None, None, P, None, P, None, None, None, None, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, None, P, P, P, None, None, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: SPADE_STYLE needs gb, style, dgb, dstyle'),
+    ('s2e_modulate_bwd', (BAD, 1, P, P, None, None, P, None, P, None, None, None, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd', (BF16, 1, P, P, None, None, P, None, P, None, None, None, P, 1, 64, 12, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_bwd', (F32, 1, P, P, None, None, P, None, P, None, None, None, P, 1, 64, 6, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
+    ('s2e_modulate_bwd', (BF16, 1, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: out (the gamma-only form) goes with the SPADE_STYLE modes only'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, None, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: SPADE_STYLE needs gb, style, dgb, dstyle'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, P, P, None, None, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
+    ('s2e_modulate_bwd', (BAD, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 12, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_bwd', (F32, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 6, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, 3, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: stage 3'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, None, P, P, None, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
+    ('s2e_modulate_bwd', (BAD, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd', (BAD, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 8, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 12, 0, 0, 1, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_bwd', (F32, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 6, 0, 0, 1, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, P, P, P, None, P, P, P, 1, 64, 8, 0, 0, 1, 0.0, 8, 0, None), -1, 's2e_modulate_bwd: x at half resolution needs the gamma-only form, per-sample statistics and an even H x W map'),
+    ('s2e_modulate_bwd', (BF16, SP | ACC, P, P, P, P, P, P, P, P + 16, P, P, P, 1, 64, 8, 0, 0, 3, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: stage 3'),
+    ('s2e_modulate_bwd', (BF16, 0, P, P, P, P, P, P, P, P + 16, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: dx_add apart from dx needs S2E_NORM_ACCUMULATE_DX'),
+    ('s2e_modulate_bwd', (BF16, SP | ACC, P, P, P, P, P, P, None, P + 16, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad argument'),
+    ('s2e_modulate_bwd', (BAD, SP | ACC, P, P, P, P, P, P, P, P + 16, P, P, P, 1, 64, 8, 0, 0, 0, 0.0, 0, 0, None), -1, 's2e_modulate_bwd: bad dtype 7'),
+    ('s2e_modulate_bwd', (BF16, SP | ACC, P, P, P, P, P, P, P, P + 16, P, P, P, 1, 64, 12, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=12 not a multiple of 8'),
+    ('s2e_modulate_bwd', (F32, SP | ACC, P, P, P, P, P, P, P, P + 16, P, P, P, 1, 64, 6, 0, 0, 0, 0.0, 0, 0, None), -3, 's2e_modulate_bwd: C=6 not a multiple of 4'),
     ('s2e_instance_norm_fwd', (BF16, P, P, P, None, 1, 64, 8, 1e-05, 1, None), -1, 's2e_instance_norm_fwd: bad argument'),
     ('s2e_instance_norm_fwd', (BAD, P, P, P, P, 1, 64, 8, 1e-05, 1, None), -1, 's2e_instance_norm_fwd: bad dtype 7'),
     ('s2e_instance_norm_fwd', (BF16, P, P, P, P, 1, 64, 12, 1e-05, 1, None), -3, 's2e_instance_norm_fwd: C=12 not a multiple of 8'),
@@ -557,9 +557,6 @@ HOST_QUERY_TABLE = [
     ('s2e_in_stats_workspace_bytes', (BF16, 2, 4096, 64), 10240),
     ('s2e_in_stats_workspace_bytes', (F32, 2, 4096, 64), 18432),
     ('s2e_in_stats_workspace_bytes', (BF16, 2, 4096, 12), 0),
-    ('s2e_in_stats_counters', (BF16, 2, 4096, 64), 2),
-    ('s2e_in_stats_counters', (F32, 2, 4096, 64), 2),
-    ('s2e_in_stats_counters', (F32, 2, 4096, 6), 0),
     ('s2e_modulate_bwd_workspace_bytes', (BF16, 2, 4096, 64), 22528),
     ('s2e_modulate_bwd_workspace_bytes', (F32, 2, 4096, 64), 38912),
     ('s2e_modulate_bwd_workspace_bytes', (BF16, 2, 4096, 12), 0),
@@ -574,7 +571,7 @@ def test_dtype_entry_points_reject_bad_calls_before_any_launch():
     from seg2eye_amd import _lib
     L = _lib.lib()
     assert (_lib.S2E_BF16, _lib.S2E_F32, _lib.NORM_SPADE_STYLE, _lib.NORM_ACCUMULATE_DX) == (BF16, F32, SP, ACC)
-    assert len({name for name, _, _, _ in HOST_ERROR_TABLE}) == 38
+    assert len({name for name, _, _, _ in HOST_ERROR_TABLE}) == 35
     got = []
     for name, args, _, _ in HOST_ERROR_TABLE:
         rc = getattr(L, name)(*[ctypes.byref(_lib.ConvDesc(*a[1:])) if a is BIG else a for a in args])

@@ -175,7 +175,11 @@ def test_in_stats_and_instance_norm(shape, dtype):
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
-@pytest.mark.parametrize('shape', [(2, 16, 16, 32), (2, 9, 7, 8), (1, 32, 32, 128), (2, 64, 64, 8), (2, 64, 64, 16)])
+# The last three maps (> 1280 pixels: the row-walking kernels) end in a partial slab, so that a thread's rows there leave every
+# tail length of the reduce kernel's 4 / 2 / 1-row trips: rows per thread in the last slab (tails) at bf16 | fp32 --
+# (33, 40): 10 or 9 (2, 1) | 3 or 2 (3, 2);  (40, 50): 15 or 14 (3, 2) | 13 (1);  (36, 36): 9 or 8 (1, 0) | 1 (1); full slabs: 16 (0).
+@pytest.mark.parametrize('shape', [(2, 16, 16, 32), (2, 9, 7, 8), (1, 32, 32, 128), (2, 64, 64, 8), (2, 64, 64, 16),
+                                   (2, 33, 40, 64), (2, 40, 50, 64), (2, 36, 36, 64)])
 @pytest.mark.parametrize('lrelu', [False, True])
 def test_spade_style_modulate(shape, dtype, lrelu):
     from seg2eye_amd import ops
@@ -274,11 +278,13 @@ def test_spade_params_and_label_conv(cfg, dtype):
 @pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('sparse', [False, True])
 @pytest.mark.parametrize('cfg', [(2, 64, 64, 32, 32, 64, True, True), (1, 48, 80, 24, 40, 128, False, True), (2, 32, 32, 16, 16, 192, True, False),
-                                 (3, 64, 64, 64, 64, 64, True, True), (2, 128, 128, 128, 128, 64, True, False)])
+                                 (3, 64, 64, 64, 64, 64, True, True), (2, 128, 128, 128, 128, 64, True, False),
+                                 # the partial-slab maps of test_spade_style_modulate: every row tail of the gamma-only form too
+                                 (2, 33, 40, 33, 40, 64, True, False), (2, 40, 50, 40, 50, 64, True, True), (2, 36, 36, 36, 36, 64, False, True)])
 def test_spade_conv_modulate_fused(cfg, sparse, dtype):
     """s2e_spade_conv_modulate (the [gamma | beta] conv with the modulation in its epilogue; flags=1 forces the fused kernel at
     any tile count) against the fp64 reference of SPADE_STYLE_Block.forward (normalization.py:184-192) and against the two-launch
-    path, forward (no-grad: gamma never stored; with grad) and every gradient (s2e_modulate_bwd_gamma).
+    path, forward (no-grad: gamma never stored; with grad) and every gradient (s2e_modulate_bwd's gamma-only form).
     sparse: the label-sparse form (flags 4 forces it at these small sizes) on clean nested-ellipse maps -- label-uniform
     rectangles take gamma / beta from the per-class table, incl. the rectangles on the image border; dense: flags 2."""
     from seg2eye_amd import ops
@@ -321,32 +327,33 @@ def test_spade_conv_modulate_fused(cfg, sparse, dtype):
     with torch.no_grad():
         y0 = ops.spade_style_fused(xg, lab.to(dev), *prm, sg, st, lrelu, flags=FL)
     _close(nchw(y0), yr, dtype, what='fused out (no grad)')
-    # flags 8: x handed over at HALF resolution, the generator's nearest 2x upsampling folded into the launch's read of x
-    # (no-grad forward) -- the same bits as upsampling first
-    xl = nhwc(_rnd((N, C, h // 2, w // 2), 48, dtype) * 1.1 - 0.1).to(dev)
-    stl = ops.in_stats(xl)
-    with torch.no_grad():
-        y_fold = ops.spade_style_fused(xl, lab.to(dev), *prm, sg, stl, lrelu, flags=FL | 8)
-        y_mat = ops.spade_style_fused(ops.upsample2x(xl), lab.to(dev), *prm, sg, stl, lrelu, flags=FL)
-    assert y_fold.shape == y_mat.shape == (N, h, w, C) and torch.equal(y_fold, y_mat)
-    # ... and WITH gradients (the training forward): the same output bit for bit, and the gradient w.r.t. the half-resolution
-    # tensor -- the launch's backward sums the 2 x 2 pixels in fp32 and rounds once (s2e_modulate_bwd_staged: x_up_w, dx_quad),
-    # upsampling first rounds four times and once more in the upsampling's backward: equal to the compute dtype's resolution
-    gyl = nhwc(gy).to(dev)
-    res = []
-    for fold in (False, True):
-        xs = xl.clone().requires_grad_(True)
-        prm2 = [t.detach().clone().requires_grad_(True) for t in prm]
-        if fold:
-            yy = ops.spade_style_fused(xs, lab.to(dev), *prm2, sg.detach(), stl, lrelu, flags=FL | 8)
-        else:
-            yy = ops.spade_style_fused(ops.upsample2x(xs), lab.to(dev), *prm2, sg.detach(), stl, lrelu, flags=FL)
-        yy.backward(gyl)
-        res.append((yy.detach(), xs.grad, [t.grad for t in prm2]))
-    assert torch.equal(res[0][0], res[1][0])
-    _close(res[1][1], res[0][1], dtype, what='dx of the folded upsampling')
-    for a, b in zip(res[0][2], res[1][2]):
-        assert float((a - b).abs().max()) <= 2e-3 * float(a.abs().max()) + 1e-6      # (weight-gradient atomics: summation order)
+    if h % 2 == 0 and w % 2 == 0:                         # (an odd map is not the output of a 2x upsampling)
+        # flags 8: x handed over at HALF resolution, the generator's nearest 2x upsampling folded into the launch's read of x
+        # (no-grad forward) -- the same bits as upsampling first
+        xl = nhwc(_rnd((N, C, h // 2, w // 2), 48, dtype) * 1.1 - 0.1).to(dev)
+        stl = ops.in_stats(xl)
+        with torch.no_grad():
+            y_fold = ops.spade_style_fused(xl, lab.to(dev), *prm, sg, stl, lrelu, flags=FL | 8)
+            y_mat = ops.spade_style_fused(ops.upsample2x(xl), lab.to(dev), *prm, sg, stl, lrelu, flags=FL)
+        assert y_fold.shape == y_mat.shape == (N, h, w, C) and torch.equal(y_fold, y_mat)
+        # ... and WITH gradients (the training forward): the same output bit for bit, and the gradient w.r.t. the half-resolution
+        # tensor -- the launch's backward sums the 2 x 2 pixels in fp32 and rounds once (s2e_modulate_bwd: x_up_w, dx_quad),
+        # upsampling first rounds four times and once more in the upsampling's backward: equal to the compute dtype's resolution
+        gyl = nhwc(gy).to(dev)
+        res = []
+        for fold in (False, True):
+            xs = xl.clone().requires_grad_(True)
+            prm2 = [t.detach().clone().requires_grad_(True) for t in prm]
+            if fold:
+                yy = ops.spade_style_fused(xs, lab.to(dev), *prm2, sg.detach(), stl, lrelu, flags=FL | 8)
+            else:
+                yy = ops.spade_style_fused(ops.upsample2x(xs), lab.to(dev), *prm2, sg.detach(), stl, lrelu, flags=FL)
+            yy.backward(gyl)
+            res.append((yy.detach(), xs.grad, [t.grad for t in prm2]))
+        assert torch.equal(res[0][0], res[1][0])
+        _close(res[1][1], res[0][1], dtype, what='dx of the folded upsampling')
+        for a, b in zip(res[0][2], res[1][2]):
+            assert float((a - b).abs().max()) <= 2e-3 * float(a.abs().max()) + 1e-6      # (weight-gradient atomics: summation order)
     y = ops.spade_style_fused(xg, lab.to(dev), *prm, sg, st, lrelu, relay=relay, flags=FL)
     if relay:
         y, xalias = y
@@ -1295,9 +1302,12 @@ def test_style_fc_kernels_match_torch(cfg):
 
 @pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('shape', [(2, 64, 64, 64), (8, 128, 128, 128), (3, 40, 50, 2064), (1, 256, 256, 8)])
-def test_in_stats_one_launch_equals_two_launches_bitwise(shape, dtype):
-    """The fold of the per-block partial sums done by the last row-walking block (counters given) gives the bits of the separate
-    finalize launch, launch after launch, and leaves the counters zero."""
+def test_in_stats_large_maps_repeat_bitwise_and_match_fp64(shape, dtype):
+    """The large-map statistics (partial sums per row-walking block, folded in a fixed order) at two channel-group blocks with a
+    channel-group count that is no power of two (C = 2064), at C = 8 and at N = 8: a second call into a NaN-filled workspace gives
+    the same bits; mean and rstd match fp64 to test_in_stats_and_instance_norm's tolerances; the first N*C*2 doubles of the
+    workspace are the fp64 {sum x, sum x^2} of the input as stored, to 1e-6 relative (fp32 partial sums over at most 512 rows,
+    folded in fp64)."""
     from seg2eye_amd import _lib as L
     dev = _dev()
     n, h, w, c = shape
@@ -1305,21 +1315,20 @@ def test_in_stats_one_launch_equals_two_launches_bitwise(shape, dtype):
     dt = L.S2E_BF16 if dtype == torch.bfloat16 else L.S2E_F32
     st = torch.cuda.current_stream().cuda_stream
     wsb = L.lib().s2e_in_stats_workspace_bytes(dt, n, h * w, c)
-    ncnt = L.lib().s2e_in_stats_counters(dt, n, h * w, c)
-    assert ncnt > 0
     res = []
-    cnt = torch.zeros(ncnt, dtype=torch.int32, device=dev)
-    for counters in (None, cnt, cnt, cnt):
+    for _ in range(2):
         ws = torch.full((wsb // 8,), float('nan'), dtype=torch.float64, device=dev)
         stats = torch.empty(n, c, 2, device=dev)
-        L.check(L.lib().s2e_in_stats(dt, x.data_ptr(), n, h * w, c, 1e-5, ws.data_ptr(), stats.data_ptr(),
-                                     None if counters is None else counters.data_ptr(), st), 'in_stats')
+        L.check(L.lib().s2e_in_stats(dt, x.data_ptr(), n, h * w, c, 1e-5, ws.data_ptr(), stats.data_ptr(), st), 'in_stats')
         res.append((stats, ws[:n * c * 2].clone()))
-        assert int(cnt.abs().sum()) == 0
-    for stats, sums in res[1:]:
-        assert torch.equal(stats, res[0][0]) and torch.equal(sums, res[0][1])
+    assert torch.equal(res[1][0], res[0][0]) and torch.equal(res[1][1], res[0][1])
+    stats, sums = res[0][0].cpu(), res[0][1].cpu().view(n, c, 2)
     ref = x.double().cpu().view(n, h * w, c)
-    assert torch.allclose(res[0][0][..., 0].double().cpu(), ref.mean(1), rtol=1e-4, atol=1e-4)
+    _close(stats[..., 0], ref.mean(1), torch.float32, what='mean')
+    _close(stats[..., 1], 1.0 / torch.sqrt(ref.var(1, unbiased=False) + 1e-5), torch.float32, what='rstd')
+    rel = [float(((sums[..., k] - want).abs() / want.abs()).max()) for k, want in enumerate((ref.sum(1), (ref * ref).sum(1)))]
+    print('in_stats sums %s %s: max relative error sum x %.3e, sum x^2 %.3e' % (shape, dtype, rel[0], rel[1]))
+    assert rel[0] <= 1e-6 and rel[1] <= 1e-6, rel
 
 
 def test_discriminator_input_and_split_halves():

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Micro-benchmark of the SPADE+Style modulation backward (s2e_modulate_bwd_staged) and the plain InstanceNorm backward at the
+"""Micro-benchmark of the SPADE+Style modulation backward (s2e_modulate_bwd) and the plain InstanceNorm backward at the
 step's large shapes: HIP-event time per call and algorithmic GB/s (DESIGN 3.5's access counts).  Run it under
 `rocprofv3 --kernel-trace --stats` to split the passes (reduce / coef / apply).
 
@@ -41,8 +41,8 @@ def main():
         ws = torch.empty(lib.s2e_modulate_bwd_workspace_bytes(L.S2E_BF16, n, h * w, c) // 8, dtype=torch.float64, device=dev)
 
         def call():
-            L.check(lib.s2e_modulate_bwd_staged(L.S2E_BF16, L.NORM_SPADE_STYLE, p(g), p(x), p(gamma), p(fout), p(stats), p(style), p(dx), p(dgb),
-                                                p(dstyle), p(ws), n, h * w, c, 1, 2 * c, 0, 0.0, w if half else 0, 1 if half else 0, st), 'bwd')
+            L.check(lib.s2e_modulate_bwd(L.S2E_BF16, L.NORM_SPADE_STYLE, p(g), p(x), p(gamma), p(fout), p(stats), p(style), p(dx), None, p(dgb),
+                                         p(dstyle), p(ws), n, h * w, c, 1, 2 * c, 0, 0.0, w if half else 0, 1 if half else 0, st), 'bwd')
         for _ in range(3):
             call()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
