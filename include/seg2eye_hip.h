@@ -626,6 +626,27 @@ int s2e_openeds_error(int dtype, const void* fake, const void* target, int N, in
 int s2e_openeds_error_u8(const uint8_t* produced, const uint8_t* target, int N, int H, int W, float* err, void* stream);
 int s2e_resize_to255(int dtype, const void* x, int N, int H, int W, uint8_t* out, int Ho, int Wo, void* stream);
 
+/* ------------------------------------------------------------------ structural similarity (an extension: the reference has none)
+ * SSIM (Wang et al. 2004) of two single-channel batches x, y (N,H,W) and its gradient with respect to x.  u = (x + 1) / 2 and
+ * v = (y + 1) / 2 for images of T in [-1, 1] (no clamp), u = a / 255 for the uint8 entry.  Window: 11 taps exp(-(i-5)^2 / (2 1.5^2))
+ * normalised to sum 1 in fp64, as the outer product; "valid" placement only, (H-10)(W-10) positions.  With the window-weighted
+ * means mu_u, mu_v, E[u^2], E[v^2], E[uv] of a position, su2 = E[u^2] - mu_u^2, sv2 likewise, suv = E[uv] - mu_u mu_v and
+ *   S = (2 mu_u mu_v + C1)(2 suv + C2) / ((mu_u^2 + mu_v^2 + C1)(su2 + sv2 + C2)),   C1 = 0.01^2, C2 = 0.03^2 (data range 1),
+ * ssim[n] (fp32) = the mean of S over image n's positions.  fp32 arithmetic from the loaded values, the moments taken about each
+ * tile's first pixel; the sum toward ssim[n] in fp64: per-tile partials in `workspace` (plain stores), folded in index order by a
+ * second launch.  maps (may be NULL: nothing is saved): 3 N (H-10)(W-10) fp32 -- the planes A = dS/dmu_u, B = dS/dE[u^2],
+ * C = dS/dE[uv], each (N,H-10,W-10) -- for s2e_ssim_bwd:
+ *   dx[n,p] (of T) = gssim[n] / positions * 1/2 * sum_q g(x)g(p - q) (A(q) + 2 u(p) B(q) + v(p) C(q)),    q over the positions covering p.
+ * Two launches forward, one backward; no atomics, no synchronisation, launch shapes from (N, H, W) alone, bit-reproducible.
+ * workspace: s2e_ssim_workspace_bytes(N, H, W) bytes (0 for N <= 0 or an image below 11 x 11), uninitialised.
+ * Before any launch: S2E_ERR_ARG on a null pointer (maps of s2e_ssim_fwd excepted), N <= 0, a bad dtype or a short workspace;
+ * S2E_ERR_UNSUPPORTED on H < 11, W < 11, N > 65535 or N H W >= 2^31. */
+size_t s2e_ssim_workspace_bytes(int N, int H, int W);
+int s2e_ssim_fwd(int dtype, const void* x, const void* y, int N, int H, int W, float* ssim, float* maps, void* workspace,
+                 size_t workspace_bytes, void* stream);
+int s2e_ssim_u8(const uint8_t* a, const uint8_t* b, int N, int H, int W, float* ssim, void* workspace, size_t workspace_bytes, void* stream);
+int s2e_ssim_bwd(int dtype, const void* x, const void* y, const float* maps, const float* gssim, int N, int H, int W, void* dx, void* stream);
+
 /* ------------------------------------------------------------------ side-by-side validation panels
  * The reference's visualize_sidebyside (util/visualizer.py:131-166) for a batch of n samples, as three launches on the caller's
  * stream with no host synchronisation between them: out[i] = [ style | label | target_original | fake | heat ], five h x w cells of

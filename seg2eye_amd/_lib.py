@@ -170,6 +170,10 @@ SIGNATURES = {
     's2e_openeds_error': (STATUS, [_i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     's2e_openeds_error_u8': (STATUS, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     's2e_resize_to255': (STATUS, [_i, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
+    's2e_ssim_workspace_bytes': (SIZE, [_i, _i, _i]),
+    's2e_ssim_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
+    's2e_ssim_u8': (STATUS, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
+    's2e_ssim_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     's2e_bilinear_resize_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_bilinear_resize_bwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_upsample2x_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),

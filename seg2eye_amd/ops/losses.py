@@ -1,5 +1,5 @@
 """Loss reductions (hinge / L1 / feature matching with in-place gradient injection), the flat Adam step, and the OpenEDS validation
-metric kernels."""
+metric and SSIM kernels."""
 import torch
 
 from .. import _lib as L
@@ -250,6 +250,73 @@ def openeds_error_u8(produced, target):
     err = torch.empty(n, dtype=torch.float32, device=a.device)
     L.call.s2e_openeds_error_u8(_p(a), _p(b), n, h, w, _p(err), _stream())
     return err
+
+
+def _ssim_workspace(n, h, w, device):
+    return torch.empty(int(L.call.s2e_ssim_workspace_bytes(n, h, w)) // 8, dtype=torch.float64, device=device)
+
+
+def _ssim_cost(n, h, w, planes):
+    """(algorithmic FLOPs, bytes) of one SSIM launch pair: `planes` separable 11-tap passes per position; the images once, the maps once."""
+    pos = n * (h - 10) * (w - 10)
+    return float(2 * 2 * 11 * planes * pos), pos
+
+
+class SsimFn(torch.autograd.Function):
+    """ssim[n] of two (N,H,W) batches in [-1, 1] (s2e_ssim_fwd: two launches); the backward is s2e_ssim_bwd on the saved A, B, C maps
+    (one launch), for x only.  When x needs no gradient nothing is saved and no maps are allocated."""
+
+    @staticmethod
+    def forward(ctx, x, y):
+        a, b = _single_channel(x.detach()), _single_channel(y.detach().to(x.dtype))
+        _need(a, b)
+        n, h, w = a.shape
+        out = torch.empty(n, dtype=torch.float32, device=a.device)
+        ws = _ssim_workspace(n, h, w, a.device)
+        maps = torch.empty(3, n, h - 10, w - 10, dtype=torch.float32, device=a.device) if ctx.needs_input_grad[0] and h > 10 and w > 10 else None
+        flops, pos = _ssim_cost(n, h, w, 5)
+        LaunchProfiler.run('ssim_fwd', flops, L.call.s2e_ssim_fwd,
+                           (_dt(a), _p(a), _p(b), n, h, w, _p(out), _p(maps), _p(ws), ws.numel() * 8, _stream()),
+                           nbytes=float(2 * a.numel() * a.element_size() + (12 * pos if maps is not None else 0)))
+        if maps is not None:
+            ctx.save_for_backward(a, b, maps)
+        ctx.x_shape = x.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if not ctx.saved_tensors:
+            return None, None
+        a, b, maps = ctx.saved_tensors
+        n, h, w = a.shape
+        gs = gout.detach().float().contiguous()
+        dx = torch.empty_like(a)
+        flops, pos = _ssim_cost(n, h, w, 3)
+        LaunchProfiler.run('ssim_bwd', flops, L.call.s2e_ssim_bwd, (_dt(a), _p(a), _p(b), _p(maps), _p(gs), n, h, w, _p(dx), _stream()),
+                           nbytes=float(3 * a.numel() * a.element_size() + 12 * pos))
+        return dx.view(ctx.x_shape), None
+
+
+def ssim(x, y):
+    """Per-image structural similarity of two single-channel batches in [-1, 1] (11-tap Gaussian window, sigma 1.5, valid
+    placement, data range 1, no clamp).  -> fp32 (N,), higher is better, 1 for identical images; differentiable in x only (y is cast
+    to x's dtype, as openeds_error does)."""
+    return SsimFn.apply(x, y)
+
+
+def ssim_u8(a, b):
+    """The same on uint8 images that already are 0..255 (u = a / 255).  -> fp32 (N,), no gradient."""
+    a, b = _single_channel(a), _single_channel(b)
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise ValueError('uint8 images expected')
+    _need(a, b)
+    n, h, w = a.shape
+    out = torch.empty(n, dtype=torch.float32, device=a.device)
+    ws = _ssim_workspace(n, h, w, a.device)
+    flops, _ = _ssim_cost(n, h, w, 5)
+    LaunchProfiler.run('ssim_fwd', flops, L.call.s2e_ssim_u8, (_p(a), _p(b), n, h, w, _p(out), _p(ws), ws.numel() * 8, _stream()),
+                       nbytes=float(2 * a.numel()))
+    return out
 
 
 def resize_to255(x, w=400, h=640):

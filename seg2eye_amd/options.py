@@ -42,6 +42,7 @@ _DEFAULTS = dict(
     max_consecutive_skips=100,  # train.py stops after this many skipped steps in a row (0 = never); a policy default, not a measurement
     diffaug='',                # differentiable augmentation of D's input: parts of 'color,translation,cutout' (seg2eye_amd/diffaug.py); '' = off
     diffaug_seed=0,            # the sampler's CPU generator is seeded diffaug_seed + rank
+    lambda_ssim=0.0,           # > 0: lambda_ssim * (1 - mean SSIM(fake, target)) joins the generator's loss (ops.ssim); 0 = off
 )
 
 
@@ -118,6 +119,9 @@ _CLI = [  # (name, type or 'flag', default, choices)
     ('synthetic_size', _I, 64, None),        # samples per epoch of the synthetic dataset
     # the dataset's resize / flip / normalise as HIP launches on raw frames, bit-identical to the host path; off = host
     ('device_preprocess', 'flag', False, None),
+    # validation also scores SSIM on the 640 x 400 uint8 pair the OpenEDS error sees (ops.ssim_u8): 'ssim/<key>/<mode>' in
+    # the statistics (higher is better), `ssim` in the error log; off = validation as it was
+    ('val_ssim', 'flag', False, None),
 ]
 _CLI_TRAIN_BUILD = [
     ('ema_decay', _F, 0.0, None), ('ema_start', _I, 0, None),        # averaged generator weights; 0 = off
@@ -127,6 +131,9 @@ _CLI_TRAIN_BUILD = [
     ('grad_clip_norm', _F, 0.0, None), ('skip_nonfinite_grads', 'flag', False, None), ('max_consecutive_skips', _I, 100, None),
     # differentiable augmentation of the discriminator's input: 'color,translation,cutout' or a subset; '' = off
     ('diffaug', _S, '', None), ('diffaug_seed', _I, 0, None),
+    # structural-similarity term of the generator's loss: lambda_ssim * (1 - mean SSIM(fake, target)); 'SSIM/raw' in the
+    # loss log is the mean SSIM itself, so HIGHER is better (1 = identical); 0 = off, nothing is launched
+    ('lambda_ssim', _F, 0.0, None),
 ]
 _CLI_TEST_BUILD = [
     ('use_ema', 'flag', False, None),                                 # score / generate with the averaged weights' checkpoint files

@@ -206,6 +206,11 @@ class Pix2PixModel(nn.Module):
             l1 = ops.loss_sum(a, b, LOSS_L1, 1.0 / a.numel()).view(1)
             G_losses['L1/weighted'] = l1 * self.opt.lambda_l1
             self.add_to_loss_log('L1/raw', l1.detach())
+        if getattr(opt, 'lambda_ssim', 0):
+            # structural similarity of the un-augmented fake and the target (an extension): two launches, one in the backward
+            s = ops.ssim(fake_image, target_image).mean()
+            G_losses['SSIM/weighted'] = (opt.lambda_ssim * (1.0 - s)).view(1)
+            self.add_to_loss_log('SSIM/raw', s.detach())          # (the mean SSIM itself: higher is better)
         if getattr(self.opt, 'lambda_openeds', 0):
             # pix2pix_model.py:206-210: the OpenEDS metric of the batch (per image; no gradient -- the reference's
             # `.int()` cuts the graph too), weighted into the logged loss

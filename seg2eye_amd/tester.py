@@ -9,7 +9,9 @@ What differs from the reference: the generated batch never leaves the GPU before
 filename (h5 with h5py, else npz) and, with `--visuals`, the reference's fourth dataset `visualisation`: the side-by-side panels,
 built on the device too (seg2eye_amd/visualizer.py).  A `visualizer` handed to the constructor receives the
 statistics lines (`run(log=True)`) and the panels of `run_visual_validation`; without one neither happens (the reference builds
-its own Visualizer there; TensorBoard events are not built).  The dataset is whatever `data.create_dataloader`
+its own Visualizer there; TensorBoard events are not built).  With `--val_ssim` every scored pair also gets its structural similarity
+(`s2e_ssim_u8` on the same 640 x 400 uint8 pair): `ssim/<dataset_key>/<mode>` in the statistics of `run` (the mean; higher is
+better) and one more dataset, `ssim` (float64, one per sample), in the error log.  The dataset is whatever `data.create_dataloader`
 yields (synthetic, or the OpenEDS H5 dataset) -- batches must carry `target_original` (N, 1, 640, 400) for validation."""
 import os
 import re
@@ -37,6 +39,8 @@ class Tester:
         self.dataloader = data_mod.create_dataloader(self.opt)
         self.visualizer = visualizer
         self.is_validation = self.opt.dataset_key in ['validation', 'train']
+        self.val_ssim = bool(getattr(self.opt, 'val_ssim', False))
+        self.all_ssim = []                                   # --val_ssim: per-sample SSIM of the last run_validation, beside its errors
         self.N = getattr(self.dataloader, 'N', len(self.dataloader) * self.opt.batchSize)
         self.results_dir = os.path.join(opt.checkpoints_dir, self.opt.name, self.opt.results_dir, self.opt.dataset_key)
         os.makedirs(self.results_dir, exist_ok=True)
@@ -86,15 +90,19 @@ class Tester:
                'filename': np.zeros((self.N,), dtype='S13')}
         if getattr(self.opt, 'visuals', False):
             log['visualisation'] = np.zeros((self.N, 1, 320 + CAPTION_ROWS, 5 * 200), dtype=np.uint8)
+        if self.val_ssim:
+            log['ssim'] = np.zeros((self.N,), dtype=np.float64)
         return log
 
-    def _write_error_log_batch(self, error_log, data_i, i, errors, fake=None):
+    def _write_error_log_batch(self, error_log, data_i, i, errors, fake=None, ssim=None):
         """tester.py:76-91; the panels of a batch are normalised over that batch, as there."""
         a = i * self.opt.batchSize
         b = min(a + len(errors), self.N)
         error_log['user'][a:b] = np.array(list(data_i['user']), dtype='S4')[:b - a]
         error_log['filename'][a:b] = np.array(list(data_i['filename']), dtype='S13')[:b - a]
         error_log['error'][a:b] = np.asarray(errors, dtype=np.float64)[:b - a]
+        if 'ssim' in error_log:
+            error_log['ssim'][a:b] = np.asarray(ssim, dtype=np.float64)[:b - a]
         if 'visualisation' in error_log:
             visuals = visualize_sidebyside({**data_i, 'fake': fake}, error_list=errors)
             error_log['visualisation'][a:b] = np.stack(list(visuals.values()))[:b - a]
@@ -118,6 +126,7 @@ class Tester:
         print('write error log: %s' % write_error_log)
         error_log = self._prepare_error_log() if write_error_log else None
         all_errors, counter = [], 0
+        self.all_ssim = []
         for i, data_i in enumerate(generator):
             data_i = materialize(data_i, self.opt, model.device())          # (--device_preprocess: raw frames -> the batch contract)
             counter += data_i['label'].shape[0]
@@ -126,10 +135,15 @@ class Tester:
             if i % 10 == 9:
                 print('Processing batch %d' % i)
                 print('Error so far: %s' % (np.sum(all_errors) / len(all_errors) * 1471))
-            errors, fake, _, _ = self.run_batch(data_i, model)
+            errors, fake, fake_resized, target = self.run_batch(data_i, model)
             all_errors += list(errors)
+            ssim = None
+            if self.val_ssim:                                # the same uint8 pair the error saw
+                from . import ops
+                ssim = ops.ssim_u8(fake_resized, target).cpu().numpy()
+                self.all_ssim += list(ssim)
             if error_log is not None:
-                self._write_error_log_batch(error_log, data_i, i, errors, fake)
+                self._write_error_log_batch(error_log, data_i, i, errors, fake, ssim)
         if error_log is not None:
             print('error log: %s' % self._close_error_log(error_log))
         return all_errors
@@ -139,7 +153,7 @@ class Tester:
         print('------------------')
         print('Error calculated on %d / %d samples' % (len(all_errors), self.N))
         for k in sorted(errors_dict):
-            print('  %s, %.2f' % (k, errors_dict[k]))
+            print(('  %s, %.4f' if k.startswith('ssim/') else '  %s, %.2f') % (k, errors_dict[k]))
         print('  dataset_key: %s, model: %s, epoch: %s, n_steps: %s' % (self.opt.dataset_key, self.opt.name, epoch, n_steps))
 
     def run_visual_validation(self, model, mode, epoch, n_steps, limit):
@@ -181,6 +195,8 @@ class Tester:
         generator = self.get_iterator(self.dataloader, indices=self._get_validation_indices(mode, limit))
         all_errors = self.run_validation(model, generator, limit=limit, write_error_log=write_error_log)
         errors_dict = MSECalculator.calculate_error_statistics(all_errors, mode=mode, dataset_key=self.opt.dataset_key)
+        if self.val_ssim:
+            errors_dict['ssim/%s/%s' % (self.opt.dataset_key, mode)] = float(np.mean(np.asarray(self.all_ssim, dtype=np.float64)))
         self.print_results(all_errors, errors_dict, epoch, n_steps)
         if log and self.visualizer is not None:
             self.log_visualizer(errors_dict, epoch, n_steps)
