@@ -185,28 +185,32 @@ int s2e_conv2d_wgrad_multi_kind(int dtype, const s2e_conv_desc* d);
  * network at once.  Per layer, W = weight_orig viewed (rows=Cout) x (cols=Cin*kh*kw), row-major:
  *   train != 0 (per iteration): v = normalize(W^T u); u = normalize(W v); sigma = u . (W v)   (u, v updated in place)
  *   train == 0:                 sigma = u . (W v)                                              (u, v untouched)
- * layers: DEVICE array of n_layers descriptors.  block_map: DEVICE int32 [n_blocks][3] = {layer, row0, col0}
- * covering every layer with the blocks s2e_sn_block_shape reports (rows x columns of one workgroup).  t (cols) and s (rows) of all layers are 64-bit fixed-point
- * accumulators (the blocks' partial sums are combined with INTEGER atomics, so u, v, sigma are bit-reproducible: identical
- * run to run and on every data-parallel replica); they live in `scratch`, which must be ZERO on the first call (the
- * kernels leave it zero again: no fill per iteration).
- * sigma: fp32 [n_layers] out. */
+ * layers: DEVICE array of n_layers descriptors.  sigma: fp32 [n_layers] out.
+ * train: `iterations` launches of one kernel, each reading every W ONCE (a workgroup owns a column strip of W and forms its share of
+ * both products from it), plus one finalising launch.  strip_map: DEVICE int32 [n_strips][2] = {layer, first column}, covering
+ * every layer's columns in strips of the width s2e_sn_block_shape(1, ..) reports (its rows: how many rows of a strip are held in
+ * registers; taller layers are walked in chunks).  Any order; neighbours in the map run together, so strips of ONE layer, which
+ * all add into that layer's y, are best kept apart.
+ * eval: two launches.  block_map: DEVICE int32 [n_blocks][3] = {layer, row0, col0} covering every layer with the tiles
+ * s2e_sn_block_shape(0, ..) reports.
+ * The workgroups' partial sums are combined with INTEGER atomics on fixed-point values, every other sum runs in a fixed order, so u, v
+ * and sigma are a function of (W, u, v, iterations) alone: identical run to run and on every data-parallel replica.  The
+ * accumulators live in `scratch`, which must be ZERO on the first call (the kernels leave it zero again: no fill per call). */
 typedef struct {
-    const float* w; float* u; float* v; long long* t; long long* s;
+    const float* w; float* u; float* v;
+    float* t;                         /* train: t = W^T u of the latest iteration, [cols] */
+    long long* s;                     /* eval: W v in units of 2^-40, [rows]; may alias y */
     int rows, cols;
-    long long* t2; long long* s2;     /* second accumulator pair (zero like t, s) for chain != 0; may be NULL otherwise */
+    float* tq;                        /* train: |t_J|^2 of every strip, [2][ceil(cols / strip width)] (by iteration parity) */
+    long long* y;                     /* train: W t as [3][2][rows] (buffers in rotation x {units of 2^-20, residual in units of 2^-60}) */
     int cin, taps;                    /* taps > 1: w is stored channels-last, [co][tap][ci] (cols = taps * cin, cin % 4 == 0), while v
                                        * keeps torch's (ci, tap) order: the kernels translate.  0, 0: w's columns are v's order. */
 } s2e_sn_layer;
-/* chain != 0 (train only; every layer's cols <= s2e_sn_chain_max_cols(), t2 / s2 set): the per-layer normalising launches are
- * folded into the GEMV passes -- 2 * iterations + 1 launches instead of 4 * iterations; same u, v, sigma up to the fp32
- * rounding of the norms. */
-int s2e_sn_chain_max_cols(void);
-int s2e_sn_block_shape(int which, int* rows, int* cols);   /* which = 0: tiles of block_map (W v); 1: of block_map_t (W^T u) */
-int s2e_sn_power_iteration(const s2e_sn_layer* layers, int n_layers, const int* block_map_t, int n_blocks_t,
+int s2e_sn_block_shape(int which, int* rows, int* cols);   /* which = 0: tiles of block_map (eval, W v); 1: the strip of strip_map (train) */
+int s2e_sn_power_iteration(const s2e_sn_layer* layers, int n_layers, const int* strip_map, int n_strips,
                            const int* block_map, int n_blocks,
                            void* scratch, size_t scratch_bytes, float* sigma, int train, int iterations,
-                           float eps, int chain, void* stream);
+                           float eps, void* stream);
 /* Gradient through W = W_orig / sigma (sigma = u^T W_orig v; u, v constants):
  *   gw_orig (=|+=) gW / sigma - (<gW, W_orig> / sigma^2) * u v^T     in OIHW order,
  * with gW given in the packed order of s2e_conv2d_wgrad ([co][(tap)*cin_pad + ci]).  dot_ws: 1 float of scratch, ZERO-FILLED by the caller.

@@ -59,7 +59,7 @@ class ClassTableJob(C.Structure):
 class SnLayer(C.Structure):
     """s2e_sn_layer"""
     _fields_ = [('w', C.c_void_p), ('u', C.c_void_p), ('v', C.c_void_p), ('t', C.c_void_p), ('s', C.c_void_p),
-                ('rows', C.c_int), ('cols', C.c_int), ('t2', C.c_void_p), ('s2', C.c_void_p), ('cin', C.c_int), ('taps', C.c_int)]
+                ('rows', C.c_int), ('cols', C.c_int), ('tq', C.c_void_p), ('y', C.c_void_p), ('cin', C.c_int), ('taps', C.c_int)]
 
 
 class PackJob(C.Structure):
@@ -103,8 +103,7 @@ SIGNATURES = {
     's2e_conv_k_pad': (VALUE, [_i, _i]),
     's2e_pack_conv_weight': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     's2e_sn_block_shape': (STATUS, [_i, _vp, _vp]),
-    's2e_sn_chain_max_cols': (VALUE, []),
-    's2e_sn_power_iteration': (STATUS, [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, _i, _i, _f, _i, _vp]),
+    's2e_sn_power_iteration': (STATUS, [_vp, _i, _vp, _i, _vp, _i, _vp, C.c_size_t, _vp, _i, _i, _f, _vp]),
     's2e_sn_weight_grad': (STATUS, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     's2e_grad_block_map': (COUNT, [_vp, _i, _vp]),
     's2e_sngrad_block_map': (COUNT, [_vp, _i, _vp]),

@@ -3,7 +3,7 @@
 torch.nn.utils.spectral_norm stays registered on the conv modules -- it defines the state_dict layout
 (`weight_orig`, `weight_u`, `weight_v`) -- but its pre-forward hook is never run on the HIP path.
 Instead the owning network calls `bank.step(training)` once at the top of its forward: one batched
-power iteration (4 launches for all layers), after which each conv's sigma is a device scalar that
+power iteration (one launch per iteration plus one for all layers), after which each conv's sigma is a device scalar that
 the weight-pack kernel divides by on the fly.  Semantics are those of the hook (reference
 architecture.py:30-34, normalization.py:25-26): one iteration per forward in train
 mode updating u, v in place, none in eval mode.
@@ -18,11 +18,6 @@ import torch
 from . import _lib as L
 
 SN_EPS = 1e-12
-_CHAIN_OFF = False      # (S2E_SN_CHAIN, retired in round 5: the two-launch power iteration of the small banks measured 0.88 -> 0.75 ms per step in round 2)
-
-
-def lib_chain_max_cols():
-    return L.call.s2e_sn_chain_max_cols()
 
 
 def sn_convs(root):
@@ -74,26 +69,27 @@ class SpectralBank:
                 c._buffers['weight_v'] = vview
                 self.uv_off.append((ou, ov))
         self.uv_arena = arena
-        # t | s (64-bit fixed point), same offsets; twice: small banks alternate between two accumulator pairs (chain mode)
-        tot = int(offs[-1])
-        self.scratch = torch.zeros(2 * tot, dtype=torch.int64, device=dev)
-        self.chain = int(max(cols) <= lib_chain_max_cols() and not _CHAIN_OFF)
         shapes = []
-        for which in (0, 1):                                  # the W tile one workgroup takes: W v pass, W^T u pass
+        for which in (0, 1):                                  # eval: the W tile one workgroup takes; train: the column strip
             br, bc = C.c_int(), C.c_int()
             L.call.s2e_sn_block_shape(which, C.byref(br), C.byref(bc))
             shapes.append((br.value, bc.value))
+        (_BR, _BC), (_, _SC) = shapes
+        # the kernels' accumulators (s2e_sn_layer), in 8-byte words: y [3][2][rows] | t [cols] fp32 | tq [2][strips] fp32 per layer
+        nstrips = [(c_ + _SC - 1) // _SC for c_ in cols]
+        soff = np.concatenate([[0], np.cumsum([6 * r + (c_ + 1) // 2 + ns for r, c_, ns in zip(rows, cols, nstrips)])])
+        self.scratch = torch.zeros(int(soff[-1]), dtype=torch.int64, device=dev)
         table = (L.SnLayer * self.n)()
-        maps = ([], [])
+        block_map, strips = [], []
         for i, c in enumerate(self.convs):
             ou, ov = self.uv_off[i]
+            sp = self.scratch.data_ptr() + 8 * int(soff[i])
             table[i].w = c.weight_orig.data_ptr()
             table[i].u = arena.data_ptr() + 4 * ou
             table[i].v = arena.data_ptr() + 4 * ov
-            table[i].s = self.scratch.data_ptr() + 8 * ou
-            table[i].t = self.scratch.data_ptr() + 8 * ov
-            table[i].s2 = self.scratch.data_ptr() + 8 * (tot + ou)
-            table[i].t2 = self.scratch.data_ptr() + 8 * (tot + ov)
+            table[i].y = table[i].s = sp                      # (eval's accumulator is the first of y's: zero between calls)
+            table[i].t = sp + 8 * 6 * rows[i]
+            table[i].tq = sp + 8 * (6 * rows[i] + (cols[i] + 1) // 2)
             table[i].rows, table[i].cols = rows[i], cols[i]
             w = c.weight_orig
             if w.dim() == 4 and not w.is_contiguous():
@@ -102,14 +98,17 @@ class SpectralBank:
                 if not w.permute(0, 2, 3, 1).is_contiguous() or w.shape[1] % 8:
                     raise L.Seg2EyeHipError('spectral norm: weight_orig of %s is neither contiguous nor channels-last' % (tuple(w.shape),))
                 table[i].cin, table[i].taps = w.shape[1], w.shape[2] * w.shape[3]
-            for bm, (_BR, _BC) in zip(maps, shapes):
-                for r0 in range(0, rows[i], _BR):
-                    for c0 in range(0, cols[i], _BC):
-                        bm.append((i, r0, c0))
+            for r0 in range(0, rows[i], _BR):
+                for c0 in range(0, cols[i], _BC):
+                    block_map.append((i, r0, c0))
+            strips += [(i, c0) for c0 in range(0, cols[i], _SC)]
         from .ops import upload_structs
         self.table_dev = upload_structs(table, dev)
-        self.block_map = torch.tensor(maps[0], dtype=torch.int32, device=dev)
-        self.block_map_t = torch.tensor(maps[1], dtype=torch.int32, device=dev)
+        self.block_map = torch.tensor(block_map, dtype=torch.int32, device=dev)
+        # Workgroups that run together belong to DIFFERENT layers: every strip of a layer adds into that layer's <= 16 KB of row
+        # accumulators, and atomics crowding onto one such patch are slow (the generator's bank, a call: 86 us layer by layer, 66 so)
+        strips.sort(key=lambda e: (e[1], e[0]))
+        self.strip_map = torch.tensor(strips, dtype=torch.int32, device=dev)
         self.rows, self.cols = rows, cols
         self._ptrs = self._current_ptrs()
 
@@ -157,11 +156,11 @@ class SpectralBank:
         from .ops import LaunchProfiler
         wbytes = 4.0 * sum(r * c for r, c in zip(self.rows, self.cols))
         LaunchProfiler.run('spectral_norm', 0.0, L.call.s2e_sn_power_iteration, (
-            self.table_dev.data_ptr(), self.n, self.block_map_t.data_ptr(), self.block_map_t.shape[0],
+            self.table_dev.data_ptr(), self.n, self.strip_map.data_ptr(), self.strip_map.shape[0],
             self.block_map.data_ptr(), self.block_map.shape[0],
             self.scratch.data_ptr(), self.scratch.numel() * 8, self.sigma.data_ptr(), int(bool(training)),
-            int(iterations), SN_EPS, self.chain, torch.cuda.current_stream().cuda_stream),
-            nbytes=wbytes * (2 * int(iterations) if training else 1))     # algorithmic: W^T u and W v each read W once per iteration
+            int(iterations), SN_EPS, torch.cuda.current_stream().cuda_stream),
+            nbytes=wbytes * (int(iterations) if training else 1))         # algorithmic: one read of W per iteration
         # the backward of this forward needs u, v as they are NOW (later forwards update them in place)
         if not torch.is_grad_enabled():
             self.uv_snap = self.uv_arena

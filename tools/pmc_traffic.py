@@ -70,7 +70,6 @@ FAMILIES = {  # kernel-name substring -> (family, counts as a launch of the fami
     # channels-last masters (round 3): the in-place spectral-norm chain rule is the same profiler family
     'sn_grad_inplace_apply_kernel': ('weight_grad_relayout', True), 'sn_grad_inplace_dot_kernel': ('weight_grad_relayout', False),
     'style_fc_fwd_kernel': ('style_fc', True), 'style_fc_bwd_kernel': ('style_fc', True), 'style_fc_dw_fold_kernel': ('style_fc', False),
-    'sn_gemvT_chain_kernel': ('spectral_norm', True), 'sn_gemv_chain_kernel': ('spectral_norm', False), 'sn_finalize_chain_kernel': ('spectral_norm', False),
     'conv_wgrad_reduce_kernel': ('conv_wgrad', False),
     # (round 6: every generic weight gradient of a backward as one multi-job launch + one reduction launch)
     'conv_wgrad_multi_kernel': ('conv_wgrad', True), 'conv_wgrad_reduce_multi_kernel': ('conv_wgrad', False),
@@ -78,8 +77,8 @@ FAMILIES = {  # kernel-name substring -> (family, counts as a launch of the fami
     #  and its 8-channel first layer in conv_c8.hip)
     'conv_wgrad_flat_kernel': ('conv_wgrad', True), 'conv_c8s2_wgrad_kernel': ('conv_wgrad', False), 'conv_c8s2_wgrad_reduce_kernel': ('conv_wgrad', False),
     'conv_c8s2_fwd_kernel': ('conv_small', True), 'conv_c8s2_dgrad_kernel': ('conv_small', True),
-    'sn_gemvT_kernel': ('spectral_norm', True), 'sn_gemv_kernel': ('spectral_norm', False),     # launches = power ITERATIONS
-    'sn_norm_v_kernel': ('spectral_norm', False), 'sn_finalize_kernel': ('spectral_norm', False),
+    'sn_onepass_kernel': ('spectral_norm', True), 'sn_onepass_finalize_kernel': ('spectral_norm', False),     # launches = power ITERATIONS
+    'sn_gemv_kernel': ('spectral_norm', True), 'sn_finalize_kernel': ('spectral_norm', False),                # (eval mode)
     'upsample2x_fwd_kernel': ('resample', True), 'upsample2x_bwd_kernel': ('resample', True),
     'avgpool_fwd_kernel': ('resample', True), 'avgpool_bwd_kernel': ('resample', True),
     'loss_reduce_kernel': ('loss', True), 'loss_grad_kernel': ('loss', True),
