@@ -102,10 +102,10 @@ long s2e_pack_block_map(int dtype, const s2e_pack_job* jobs_host, int n_jobs, in
 int s2e_pack_conv_weights(int dtype, const s2e_pack_job* jobs, const int* block_map, int n_blocks, int max_taps,
                           const float* sigma_base, void* stream);
 
-/* Layers that cannot fill the chip from their output tiling alone (small N*Ho*Wo, large K) are
- * split over K: each split writes an fp32 partial slab into `workspace` and a finishing kernel sums
- * the slabs and applies the epilogue (deterministic; no atomics).  workspace_bytes(d) is 0 for
- * shapes that do not split; the caller allocates (no initialisation needed). */
+/* The bytes of `workspace` the kernel this shape routes to needs (0: none): the fp32 partial slabs of a layer split over K
+ * because its output tiling alone cannot fill the chip (implicit GEMM, and the patch kernel's channel-chunk splits; a finishing
+ * kernel sums the slabs and applies the epilogue), or the stream-K kernel's two partial tiles per CU.  Deterministic, no atomics;
+ * the caller allocates (no initialisation needed) and s2e_conv2d refuses a smaller workspace with S2E_ERR_ARG. */
 size_t s2e_conv2d_workspace_bytes(int dtype, const s2e_conv_desc* d);
 /* Which kernel s2e_conv2d / s2e_conv2d_wgrad run for this shape (for profilers and tests; the choice is made inside the
  * library from the shape alone): S2E_KERNEL_GENERIC = implicit GEMM (conv_igemm.hip / conv_wgrad.hip),

@@ -589,56 +589,76 @@ static void plan_splits(int dtype, const s2e_conv_desc* d, int* tiles, int* tile
     *splits = ceil_div(nk, *per);                    // no empty split
 }
 
+// The one routing decision of a forward / data-gradient shape: every query below and s2e_conv2d read it.  Order:
+// small, duo (unless the launch has a residual AND a mask: the duo epilogue takes one of them), patch, stream, igemm.
+enum { ROUTE_SMALL, ROUTE_DUO, ROUTE_PATCH, ROUTE_STREAM, ROUTE_IGEMM };
+struct ConvRoute {
+    int kernel;                                      // ROUTE_*
+    int small_kind;                                  // ROUTE_SMALL
+    s2e_patch_plan patch;                            // ROUTE_DUO, ROUTE_PATCH
+    int tiles, tiles_n, splits, kt_per_split;        // ROUTE_IGEMM
+    bool s2_class;
+    size_t workspace_bytes;                          // what the routed kernel needs: fp32 split slabs (patch, igemm), stream-K partials
+};
+static ConvRoute conv_route(int dtype, const s2e_conv_desc* d, bool res_and_mask) {
+    ConvRoute r{};
+    const size_t out_elems = (size_t)d->N * d->Ho * d->Wo * d->Cout;
+    if ((r.small_kind = s2e_small_conv_kind(dtype, d)) != SMALL_NONE) r.kernel = ROUTE_SMALL;
+    else if (!res_and_mask && s2e_conv_duo_plan(dtype, d, &r.patch)) r.kernel = ROUTE_DUO;
+    else if (s2e_conv_patch_plan(dtype, d, &r.patch)) {
+        r.kernel = ROUTE_PATCH;
+        if (r.patch.splits > 1) r.workspace_bytes = r.patch.splits * out_elems * sizeof(float);
+    } else if (s2e_conv_stream_plan(dtype, d, &r.workspace_bytes)) r.kernel = ROUTE_STREAM;
+    else {
+        r.kernel = ROUTE_IGEMM;
+        plan_splits(dtype, d, &r.tiles, &r.tiles_n, &r.splits, &r.kt_per_split);
+        r.s2_class = s2_class_mode(dtype, d);
+        if (r.splits > 1) r.workspace_bytes = r.splits * out_elems * sizeof(float);
+    }
+    return r;
+}
+
 extern "C" size_t s2e_conv2d_workspace_bytes(int dtype, const s2e_conv_desc* d) {
-    if (!d) return 0;
-    if (s2e_small_conv_kind(dtype, d) != SMALL_NONE) return 0;
-    if (s2e_conv_duo_plan(dtype, d, nullptr)) return 0;
-    if (s2e_conv_patch_plan(dtype, d, nullptr)) return s2e_conv_patch_workspace_bytes(dtype, d);
-    if (s2e_conv_stream_plan(dtype, d)) return s2e_conv_stream_workspace_bytes(dtype, d);
-    int tiles, tiles_n, splits, per;
-    plan_splits(dtype, d, &tiles, &tiles_n, &splits, &per);
-    return splits > 1 ? (size_t)splits * d->N * d->Ho * d->Wo * d->Cout * sizeof(float) : 0;
+    return d ? conv_route(dtype, d, false).workspace_bytes : 0;
 }
 
 extern "C" int s2e_conv2d_kernel_kind(int dtype, const s2e_conv_desc* d) {
     if (!d) return S2E_KERNEL_GENERIC;
-    if (s2e_small_conv_kind(dtype, d) != SMALL_NONE) return S2E_KERNEL_SMALL;
-    return (s2e_conv_duo_plan(dtype, d, nullptr) || s2e_conv_patch_plan(dtype, d, nullptr)) ? S2E_KERNEL_PATCH : S2E_KERNEL_GENERIC;
+    const int k = conv_route(dtype, d, false).kernel;
+    return k == ROUTE_SMALL ? S2E_KERNEL_SMALL : (k == ROUTE_DUO || k == ROUTE_PATCH) ? S2E_KERNEL_PATCH : S2E_KERNEL_GENERIC;
 }
 
 // The convolution WITH the InstanceNorm partial sums of its output (the statistics pass over a large map is
 // the producer's epilogue): s2e_conv2d_stats_slots = the slots per sample the launch writes (0: this shape's kernel has no such
 // epilogue -- run s2e_conv2d + s2e_in_stats), part = (N, slots, Cout, 2) floats {sum y, sum y^2}, to s2e_in_stats_from_partials.
 extern "C" int s2e_conv2d_stats_slots(int dtype, const s2e_conv_desc* d) {
-    s2e_patch_plan pplan;
-    if (!d || d->transposed || d->aux_mode != S2E_AUX_NONE || s2e_small_conv_kind(dtype, d) != SMALL_NONE) return 0;
-    if (!s2e_conv_duo_plan(dtype, d, &pplan)) return 0;
-    return s2e_conv_duo_stats_slots(d, &pplan);
+    if (!d || d->transposed || d->aux_mode != S2E_AUX_NONE) return 0;
+    const ConvRoute r = conv_route(dtype, d, false);
+    return r.kernel == ROUTE_DUO ? s2e_conv_duo_stats_slots(d, &r.patch) : 0;
 }
 
 extern "C" int s2e_conv2d_stats(int dtype, const void* x, const void* w, const float* bias, const void* res, void* y,
                                 const s2e_conv_desc* d, float* part, void* stream) {
     if (!x || !w || !y || !d || !part) S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d_stats: null pointer");
-    s2e_patch_plan pplan;
-    if (!s2e_conv2d_stats_slots(dtype, d) || !s2e_conv_duo_plan(dtype, d, &pplan))
+    if (!s2e_conv2d_stats_slots(dtype, d))
         S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d_stats: this shape's kernel writes no statistics (s2e_conv2d_stats_slots == 0)");
-    return s2e_conv_duo_launch(&pplan, x, w, bias, res, nullptr, y, d, s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), part, nullptr, nullptr, (hipStream_t)stream);
+    const ConvRoute r = conv_route(dtype, d, false);
+    return s2e_conv_duo_launch(&r.patch, x, w, bias, res, nullptr, y, d, s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), part, nullptr, nullptr, (hipStream_t)stream);
 }
 
 // s2e_conv2d over a device-side list of 16 x 16 rectangles (label-sparse backward of the SPADE branch): the duo kernel's shapes only.
 extern "C" int s2e_conv2d_rects_supported(int dtype, const s2e_conv_desc* d) {
-    s2e_patch_plan pplan;
-    return d && s2e_small_conv_kind(dtype, d) == SMALL_NONE && s2e_conv_duo_plan(dtype, d, &pplan) ? 1 : 0;
+    return d && conv_route(dtype, d, false).kernel == ROUTE_DUO ? 1 : 0;
 }
 
 extern "C" int s2e_conv2d_rects(int dtype, const void* x, const void* w, const float* bias, const void* res, const void* aux, void* y,
                                 const s2e_conv_desc* d, const int* rect_list, const int* rect_count, void* stream) {
     if (!x || !w || !y || !d || !rect_list || !rect_count) S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d_rects: null pointer");
     if (d->aux_mode != S2E_AUX_NONE && !aux) S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d_rects: aux_mode without aux");
-    s2e_patch_plan pplan;
-    if ((res && d->aux_mode != S2E_AUX_NONE) || !s2e_conv2d_rects_supported(dtype, d) || !s2e_conv_duo_plan(dtype, d, &pplan))
+    const ConvRoute r = conv_route(dtype, d, res && d->aux_mode != S2E_AUX_NONE);
+    if (r.kernel != ROUTE_DUO)
         S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d_rects: this shape's kernel takes no rectangle list (s2e_conv2d_rects_supported)");
-    return s2e_conv_duo_launch(&pplan, x, w, bias, res, aux, y, d, s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), nullptr, rect_list, rect_count,
+    return s2e_conv_duo_launch(&r.patch, x, w, bias, res, aux, y, d, s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), nullptr, rect_list, rect_count,
                                (hipStream_t)stream);
 }
 
@@ -653,47 +673,46 @@ extern "C" int s2e_conv2d(int dtype, const void* x, const void* w, const float* 
     if (d->KH * d->KW > 32) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d: kernel %dx%d has more than 32 taps", d->KH, d->KW);
     if ((long)d->N * d->Hi * d->Wi >= (1L << 31) || (long)d->N * d->Ho * d->Wo >= (1L << 31))
         S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d: tensor too large for 32-bit pixel indices");
-    if (const int kind = s2e_small_conv_kind(dtype, d)) {           // 1-channel heads: dedicated streaming kernels
+    const ConvRoute r = conv_route(dtype, d, res && d->aux_mode != S2E_AUX_NONE);
+    if (r.workspace_bytes && (!workspace || workspace_bytes < r.workspace_bytes))
+        S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d: this shape needs %zu bytes of workspace (s2e_conv2d_workspace_bytes)", r.workspace_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    const int kpad = s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin);
+    switch (r.kernel) {
+    case ROUTE_SMALL: {                              // 1-channel heads: dedicated streaming kernels
         SmallConvParams sp{};
         sp.x = x; sp.w = w; sp.bias = bias; sp.res = res; sp.aux = aux; sp.y = y;
         sp.N = d->N; sp.Hi = d->Hi; sp.Wi = d->Wi; sp.Cin = d->Cin; sp.Ho = d->Ho; sp.Wo = d->Wo; sp.Cout = d->Cout;
         sp.KH = d->KH; sp.KW = d->KW; sp.stride = d->stride; sp.pad = d->pad;
         sp.in_act = d->in_act; sp.out_act = d->out_act; sp.aux_mode = d->aux_mode;
-        sp.Kpad = s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin);
-        return s2e_small_conv_launch(dtype, kind, sp, (hipStream_t)stream);
+        sp.Kpad = kpad;
+        return s2e_small_conv_launch(dtype, r.small_kind, sp, st);
     }
-    s2e_patch_plan pplan;
-    if (!(res && d->aux_mode != S2E_AUX_NONE) && s2e_conv_duo_plan(dtype, d, &pplan))       // the big bf16 3x3 layers with >= 128 output channels: two staggered workgroups per CU (conv_duo.hip)
-        return s2e_conv_duo_launch(&pplan, x, w, bias, res, aux, y, d, s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), nullptr, nullptr, nullptr, (hipStream_t)stream);
-    if (s2e_conv_patch_plan(dtype, d, &pplan)) {      // big 3x3 / 4x4 stride-1 layers: patch-resident kernel
-        const int patch_splits = pplan.splits;
-        const size_t need = s2e_conv_patch_workspace_bytes(dtype, d);
-        if (need && (!workspace || workspace_bytes < need))
-            S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d: this shape needs %zu bytes of workspace (s2e_conv2d_workspace_bytes)", need);
-        const int rc = s2e_conv_patch_launch(dtype, &pplan, x, w, bias, res, aux, y, d,
-                                             s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), (float*)workspace, (hipStream_t)stream);
-        if (rc != S2E_OK || patch_splits == 1) return rc;
+    case ROUTE_DUO:                                  // the big bf16 3x3 layers with >= 128 output channels: two staggered workgroups per CU (conv_duo.hip)
+        return s2e_conv_duo_launch(&r.patch, x, w, bias, res, aux, y, d, kpad, nullptr, nullptr, nullptr, st);
+    case ROUTE_PATCH: {                              // big 3x3 / 4x4 stride-1 layers: patch-resident kernel
+        const int rc = s2e_conv_patch_launch(dtype, &r.patch, x, w, bias, res, aux, y, d, kpad, (float*)workspace, st);
+        if (rc != S2E_OK || r.patch.splits == 1) return rc;
         ConvKParams f{};                             // split over channel chunks: combine the slabs, then the fused epilogue
         f.bias = bias; f.res = res; f.aux = aux; f.y = y;
         f.out_act = d->out_act; f.aux_mode = d->aux_mode;
-        f.M = d->N * d->Ho * d->Wo; f.Cout = d->Cout; f.splits = patch_splits; f.partial = (float*)workspace;
-        return launch_finish(dtype, f, (hipStream_t)stream);
+        f.M = d->N * d->Ho * d->Wo; f.Cout = d->Cout; f.splits = r.patch.splits; f.partial = (float*)workspace;
+        return launch_finish(dtype, f, st);
     }
-    if (s2e_conv_stream_plan(dtype, d))               // every other bf16 vector-channel shape: persistent stream-K kernel
-        return s2e_conv_stream_launch(x, w, bias, res, aux, y, d, s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), workspace,
-                                      workspace_bytes, (hipStream_t)stream);
+    case ROUTE_STREAM:                               // every other bf16 vector-channel shape: persistent stream-K kernel
+        return s2e_conv_stream_launch(x, w, bias, res, aux, y, d, kpad, workspace, st);
+    }
     ConvKParams p;
     p.x = x; p.w = w; p.bias = bias; p.res = res; p.aux = aux; p.y = y;
     p.N = d->N; p.Hi = d->Hi; p.Wi = d->Wi; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
     p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.transposed = d->transposed;
     p.in_act = d->in_act; p.out_act = d->out_act; p.aux_mode = d->aux_mode;
     p.Ktot = d->KH * d->KW * d->Cin;
-    p.Kpad = s2e_conv_k_pad(dtype, p.Ktot);
+    p.Kpad = kpad;
     p.M = d->N * d->Ho * d->Wo;
     const int bn = bn_for(d->Cout);
-    plan_splits(dtype, d, &p.tiles, &p.tiles_n, &p.splits, &p.kt_per_split);
-    const bool s2 = s2_class_mode(dtype, d);
-    if (s2) s2_class_tiles(d, p.cls_tile0);
+    p.tiles = r.tiles; p.tiles_n = r.tiles_n; p.splits = r.splits; p.kt_per_split = r.kt_per_split;
+    if (r.s2_class) s2_class_tiles(d, p.cls_tile0);
     // Tile order.  xcd_remap hands each XCD a contiguous range of tile ids, and whatever operand panel those tiles do
     // NOT share is fetched into that XCD's L2 once per XCD.  Default: Cout tiles fastest (neighbours share the
     // im2col panel).  The PMC pass shows the price on the small-M, 1024-channel layers: 80-190 MB fetched per launch
@@ -703,18 +722,6 @@ extern "C" int s2e_conv2d(int dtype, const void* x, const void* w, const float* 
     // Infinity Cache and are not what bounds these launches.  Not used (the kernel keeps the code path; p.tm_fast = 0).
     p.tm_fast = 0;                                   // (the pixel-tiles-fastest order: measured, no gain -- see above)
     p.partial = (float*)workspace;
-    if (p.splits > 1 && (!workspace || workspace_bytes < s2e_conv2d_workspace_bytes(dtype, d)))
-        S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d: this shape needs %zu bytes of workspace (s2e_conv2d_workspace_bytes)",
-                 s2e_conv2d_workspace_bytes(dtype, d));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == S2E_BF16) {
-        if (bn == 128) return launch_conv<bf16_t, 128>(p, st, s2);
-        if (bn == 64) return launch_conv<bf16_t, 64>(p, st, s2);
-        return launch_conv<bf16_t, 32>(p, st, s2);
-    } else if (dtype == S2E_F32) {
-        if (bn == 128) return launch_conv<float, 128>(p, st, s2);
-        if (bn == 64) return launch_conv<float, 64>(p, st, s2);
-        return launch_conv<float, 32>(p, st, s2);
-    }
-    S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d: bad dtype %d", dtype);
+    return s2e_with_dtype(dtype, "s2e_conv2d", [&](auto t) { using T = decltype(t);
+        return bn == 128 ? launch_conv<T, 128>(p, st, r.s2_class) : bn == 64 ? launch_conv<T, 64>(p, st, r.s2_class) : launch_conv<T, 32>(p, st, r.s2_class); });
 }

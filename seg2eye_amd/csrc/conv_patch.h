@@ -10,7 +10,6 @@ struct s2e_patch_plan {
 };
 // 0 = the generic implicit-GEMM kernel runs this shape; 1 = this kernel does, with *plan (may be NULL) filled in.
 int s2e_conv_patch_plan(int dtype, const s2e_conv_desc* d, s2e_patch_plan* plan);
-size_t s2e_conv_patch_workspace_bytes(int dtype, const s2e_conv_desc* d);
 int s2e_conv_patch_launch(int dtype, const s2e_patch_plan* plan, const void* x, const void* w, const float* bias, const void* res,
                           const void* aux, void* y, const s2e_conv_desc* d, int kpad, float* partial, hipStream_t st);
 

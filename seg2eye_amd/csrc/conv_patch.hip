@@ -640,12 +640,6 @@ int s2e_conv_patch_plan(int dtype, const s2e_conv_desc* d, s2e_patch_plan* plan)
     return 0;
 }
 
-size_t s2e_conv_patch_workspace_bytes(int dtype, const s2e_conv_desc* d) {
-    s2e_patch_plan plan;
-    if (!s2e_conv_patch_plan(dtype, d, &plan) || plan.splits == 1) return 0;
-    return (size_t)plan.splits * d->N * d->Ho * d->Wo * d->Cout * sizeof(float);
-}
-
 template <typename T, int BN>
 static int launch_patch(const PatchParams& p, int ks, hipStream_t st, int s2d = 0) {
     const int grid = p.tiles < s2e_cu_count() ? p.tiles : s2e_cu_count();      // persistent: one 127-154 KB workgroup per CU

@@ -517,7 +517,7 @@ bool sk_fill_units(const s2e_conv_desc* d, int kpad, StreamParams* p) {
 
 // S2E_CONV_STREAM: 0 = never; 1 (default) = the shapes it measured faster on (long-K tiles: >= 16 K-steps per tile and >= 64
 // tiles, no parity classes -- DESIGN 3.1e has the per-shape table); 2 = every shape the kernel can run (tests, A/B runs).
-int s2e_conv_stream_plan(int dtype, const s2e_conv_desc* d) {
+int s2e_conv_stream_plan(int dtype, const s2e_conv_desc* d, size_t* workspace_bytes) {
     static const int mode = s2e_env_int("S2E_CONV_STREAM", 1);
     if (mode <= 0 || dtype != S2E_BF16) return 0;
     if (d->Cin % 8 != 0 || d->Cout % 8 != 0 || d->Cout <= 32 || d->in_act != S2E_ACT_NONE) return 0;
@@ -525,21 +525,14 @@ int s2e_conv_stream_plan(int dtype, const s2e_conv_desc* d) {
     if (d->transposed && d->stride == 2 && (d->KH < 2 || d->KW < 2)) return 0;
     StreamParams p{};
     if (!sk_fill_units(d, s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), &p)) return 0;
-    if (mode >= 2) return 1;
-    if (p.ncls > 1) return 0;
-    const long tiles = p.units / p.cls_nk[0];
-    return p.cls_nk[0] >= 16 && tiles >= 64;
+    if (mode < 2 && (p.ncls > 1 || p.cls_nk[0] < 16 || p.units / p.cls_nk[0] < 64)) return 0;
+    *workspace_bytes = p.whole_tiles ? 0 : (size_t)2 * p.G * 128 * sk_bn(d) * sizeof(float);
+    return 1;
 }
 
-size_t s2e_conv_stream_workspace_bytes(int dtype, const s2e_conv_desc* d) {
-    if (!s2e_conv_stream_plan(dtype, d)) return 0;
-    StreamParams p{};
-    sk_fill_units(d, s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin), &p);
-    return p.whole_tiles ? 0 : (size_t)2 * p.G * 128 * sk_bn(d) * sizeof(float);
-}
-
+// workspace: the bytes s2e_conv_stream_plan reported for this shape
 int s2e_conv_stream_launch(const void* x, const void* w, const float* bias, const void* res, const void* aux, void* y,
-                           const s2e_conv_desc* d, int kpad, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                           const s2e_conv_desc* d, int kpad, void* workspace, hipStream_t st) {
     StreamParams p{};
     p.x = x; p.w = w; p.bias = bias; p.res = res; p.aux = aux; p.y = y;
     p.N = d->N; p.Hi = d->Hi; p.Wi = d->Wi; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
@@ -548,9 +541,6 @@ int s2e_conv_stream_launch(const void* x, const void* w, const float* bias, cons
     p.Kpad = kpad;
     if (!sk_fill_units(d, kpad, &p)) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d: too many work units for the stream kernel");
     if (p.units <= 0) return S2E_OK;
-    const size_t need = p.whole_tiles ? 0 : (size_t)2 * p.G * 128 * sk_bn(d) * sizeof(float);
-    if (need && (!workspace || workspace_bytes < need))
-        S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d: this shape needs %zu bytes of workspace (s2e_conv2d_workspace_bytes)", need);
     p.partial = (float*)workspace;
     if (sk_bn(d) == 128) conv_stream_kernel<128><<<p.G, 256 + 64 * SK_LOADERS, 0, st>>>(p);
     else conv_stream_kernel<64><<<p.G, 256 + 64 * SK_LOADERS, 0, st>>>(p);

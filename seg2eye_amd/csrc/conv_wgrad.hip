@@ -416,30 +416,53 @@ static bool wgrad_use_partial(int splits) {
     return n > 0 && splits >= 2 && splits >= n;
 }
 
-extern "C" size_t s2e_conv2d_wgrad_workspace_bytes(int dtype, const s2e_conv_desc* d) {
-    if (!d || d->transposed) return 0;
-    if ((long)d->N * d->Hi * d->Wi >= (1L << 31) || (long)d->N * d->Ho * d->Wo >= (1L << 31)) return 0;
-    const int kind = s2e_small_wgrad_kind(dtype, d);
-    if (kind) return s2e_small_wgrad_workspace_bytes(dtype, kind, d);
-    if (const int slab_w = s2e_wgrad_patch_plan(dtype, d)) return s2e_wgrad_patch_workspace_bytes(slab_w, d);
-    if (const int slab_w = s2e_wgrad_c8_plan(dtype, d)) return s2e_wgrad_c8_workspace_bytes(slab_w, d);
-    WgradParams p{};                                       // generic kernel: one partial tile (+ 128 bias sums) per workgroup
-    int splits;
-    generic_wgrad_plan(d, &p, &splits);
-    if (!wgrad_use_partial(splits)) return 0;
+// the generic kernel's workspace: one partial tile (+ 128 bias sums) per workgroup
+static size_t generic_partial_bytes(const WgradParams& p, int splits) {
     return (size_t)p.tiles_k * p.tiles_co * splits * (128 * 128 + 128) * sizeof(float);
+}
+// the kernels index pixels with 32-bit integers
+static bool wgrad_index_range_ok(const s2e_conv_desc* d) {
+    return (long)d->N * d->Hi * d->Wi < (1L << 31) && (long)d->N * d->Ho * d->Wo < (1L << 31);
+}
+
+// The one routing decision of a weight-gradient shape: every query below, s2e_conv2d_wgrad and the multi-job call read it.
+// Order: small, patch, c8, generic.  d describes the forward conv (transposed = 0: the callers check).
+enum { WG_SMALL, WG_PATCH, WG_C8, WG_GENERIC };
+struct WgradRoute {
+    int kernel;                                      // WG_*
+    int kind;                                        // WG_SMALL: s2e_small_wgrad_kind; WG_PATCH, WG_C8: the slab width
+    WgradParams tiling; int splits; bool partial;    // WG_GENERIC, and WG_C8 (which runs the generic kernel when given too little workspace)
+    size_t workspace_bytes;                          // of `kernel`
+};
+static WgradRoute wgrad_route(int dtype, const s2e_conv_desc* d) {
+    WgradRoute r{};
+    if ((r.kind = s2e_small_wgrad_kind(dtype, d))) {
+        r.kernel = WG_SMALL; r.workspace_bytes = s2e_small_wgrad_workspace_bytes(dtype, r.kind, d);
+    } else if ((r.kind = s2e_wgrad_patch_plan(dtype, d))) {
+        r.kernel = WG_PATCH; r.workspace_bytes = s2e_wgrad_patch_workspace_bytes(r.kind, d);
+    } else {
+        generic_wgrad_plan(d, &r.tiling, &r.splits);
+        r.partial = wgrad_use_partial(r.splits);
+        if ((r.kind = s2e_wgrad_c8_plan(dtype, d))) { r.kernel = WG_C8; r.workspace_bytes = s2e_wgrad_c8_workspace_bytes(r.kind, d); }
+        else { r.kernel = WG_GENERIC; r.workspace_bytes = r.partial ? generic_partial_bytes(r.tiling, r.splits) : 0; }
+    }
+    return r;
+}
+
+extern "C" size_t s2e_conv2d_wgrad_workspace_bytes(int dtype, const s2e_conv_desc* d) {
+    return d && !d->transposed && wgrad_index_range_ok(d) ? wgrad_route(dtype, d).workspace_bytes : 0;
 }
 
 extern "C" int s2e_conv2d_wgrad_kernel_kind(int dtype, const s2e_conv_desc* d) {
     if (!d || d->transposed) return S2E_KERNEL_GENERIC;
-    if (s2e_small_wgrad_kind(dtype, d)) return S2E_KERNEL_SMALL;
-    return (s2e_wgrad_patch_plan(dtype, d) || s2e_wgrad_c8_plan(dtype, d)) ? S2E_KERNEL_PATCH : S2E_KERNEL_GENERIC;
+    const int k = wgrad_route(dtype, d).kernel;
+    return k == WG_SMALL ? S2E_KERNEL_SMALL : k == WG_GENERIC ? S2E_KERNEL_GENERIC : S2E_KERNEL_PATCH;
 }
 
 // s2e_conv2d_wgrad over the pixels of a device-side list of 16 x 16 rectangles only (label-sparse backward of the SPADE branch): the
 // patch-resident kernel with 8 x 16 slabs.  workspace: s2e_conv2d_wgrad_rects_workspace_bytes (0 = not this shape).
 extern "C" size_t s2e_conv2d_wgrad_rects_workspace_bytes(int dtype, const s2e_conv_desc* d) {
-    if (!d || d->transposed || s2e_small_wgrad_kind(dtype, d) || !s2e_wgrad_patch_plan(dtype, d) || (d->Hi & 15) || (d->Wi & 15)) return 0;
+    if (!d || d->transposed || (d->Hi & 15) || (d->Wi & 15) || wgrad_route(dtype, d).kernel != WG_PATCH) return 0;
     const size_t b = s2e_wgrad_patch_workspace_bytes(16, d);
     return b ? b : 16;                                    // (non-zero = supported; few-split shapes need no tiles)
 }
@@ -457,36 +480,32 @@ extern "C" int s2e_conv2d_wgrad(int dtype, const void* x, const void* gy, float*
     if (!x || !gy || !dw || !d) S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d_wgrad: null pointer");
     if (d->transposed) S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d_wgrad: describe the forward conv (transposed=0)");
     if (d->stride != 1 && d->stride != 2) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d_wgrad: stride %d", d->stride);
-    if ((long)d->N * d->Hi * d->Wi >= (1L << 31) || (long)d->N * d->Ho * d->Wo >= (1L << 31))
-        S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d_wgrad: tensor too large for 32-bit pixel indices");
-    if (const int kind = s2e_small_wgrad_kind(dtype, d)) {          // 1-channel heads: dedicated streaming kernels
+    if (!wgrad_index_range_ok(d)) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d_wgrad: tensor too large for 32-bit pixel indices");
+    const WgradRoute r = wgrad_route(dtype, d);
+    hipStream_t st = (hipStream_t)stream;
+    if (r.kernel == WG_SMALL) {                                     // 1-channel heads: dedicated streaming kernels
         SmallConvParams sp{};
         sp.x = x; sp.gy = gy; sp.dw = dw;
         sp.N = d->N; sp.Hi = d->Hi; sp.Wi = d->Wi; sp.Cin = d->Cin; sp.Ho = d->Ho; sp.Wo = d->Wo; sp.Cout = d->Cout;
         sp.KH = d->KH; sp.KW = d->KW; sp.stride = d->stride; sp.pad = d->pad; sp.in_act = d->in_act;
-        if (int rc = s2e_small_wgrad_launch(dtype, kind, d, sp, workspace, workspace_bytes, (hipStream_t)stream)) return rc;
+        if (int rc = s2e_small_wgrad_launch(dtype, r.kind, d, sp, workspace, workspace_bytes, st)) return rc;
         if (dbias) return s2e_colsum(dtype, gy, (long)d->N * d->Ho * d->Wo, d->Cout, dbias, stream);
         return S2E_OK;
     }
-    if (const int slab_w = s2e_wgrad_patch_plan(dtype, d))          // big 3x3 stride-1 layers: patch-resident kernel
-        return s2e_wgrad_patch_launch(slab_w, x, gy, dw, dbias, d, workspace, workspace_bytes, nullptr, nullptr, (hipStream_t)stream);
-    if (const int slab_w = s2e_wgrad_c8_plan(dtype, d))             // 8-channel (label-map) input: B operand built from a 16-B/pixel patch
-        if (workspace && workspace_bytes >= s2e_wgrad_c8_workspace_bytes(slab_w, d))
-            return s2e_wgrad_c8_launch(slab_w, x, gy, dw, dbias, d, workspace, (hipStream_t)stream);
-    WgradParams p{};
+    if (r.kernel == WG_PATCH)                                       // big 3x3 stride-1 layers: patch-resident kernel (no workspace: atomics)
+        return s2e_wgrad_patch_launch(r.kind, x, gy, dw, dbias, d, workspace, workspace_bytes, nullptr, nullptr, st);
+    // 8-channel (label-map) input: B operand built from a 16-B/pixel patch; given too little workspace the generic kernel runs
+    if (r.kernel == WG_C8 && workspace && workspace_bytes >= r.workspace_bytes)
+        return s2e_wgrad_c8_launch(r.kind, x, gy, dw, dbias, d, workspace, st);
+    WgradParams p = r.tiling;
     p.x = x; p.gy = gy; p.dw = dw; p.dbias = dbias;
     p.N = d->N; p.Hi = d->Hi; p.Wi = d->Wi; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
     p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.in_act = d->in_act;
-    int splits;
-    generic_wgrad_plan(d, &p, &splits);
-    const int tiles = p.tiles_k * p.tiles_co;
-    hipStream_t st = (hipStream_t)stream;
-    const int g = tiles * splits;
+    const int splits = r.splits, tiles = p.tiles_k * p.tiles_co, g = tiles * splits;
     // With a workspace the workgroups store their partial tiles and a second kernel adds them up in a fixed order:
     // deterministic, and cheaper than the atomics once a launch has more than a few splits (64 KB written + read per
-    // workgroup at HBM rate against 64 KB of float atomics at ~1.3 TB/s chip-wide).
-    const size_t need = (size_t)g * (128 * 128 + 128) * sizeof(float);
-    if (wgrad_use_partial(splits) && workspace && workspace_bytes >= need) {
+    // workgroup at HBM rate against 64 KB of float atomics at ~1.3 TB/s chip-wide).  Without one they add with atomics.
+    if (r.partial && workspace && workspace_bytes >= generic_partial_bytes(p, splits)) {
         p.partial = (float*)workspace;
         p.bpartial = p.partial + (size_t)g * (128 * 128);
     }
@@ -517,9 +536,7 @@ static bool ranges_overlap(const float* a, size_t na, const float* b, size_t nb)
 static bool wgrad_multi_ok(int dtype, const s2e_conv_desc* d) {
     if (!d || dtype != S2E_BF16 || d->transposed || (d->stride != 1 && d->stride != 2)) return false;
     if (d->Cin % 8 != 0 || d->Cout % 8 != 0) return false;
-    if ((long)d->N * d->Hi * d->Wi >= (1L << 31) || (long)d->N * d->Ho * d->Wo >= (1L << 31)) return false;
-    if (s2e_small_wgrad_kind(dtype, d) || s2e_wgrad_patch_plan(dtype, d) || s2e_wgrad_c8_plan(dtype, d)) return false;
-    return true;
+    return wgrad_index_range_ok(d) && wgrad_route(dtype, d).kernel == WG_GENERIC;
 }
 extern "C" int s2e_conv2d_wgrad_multi_supported(int dtype, const s2e_conv_desc* d) { return wgrad_multi_ok(dtype, d) ? 1 : 0; }
 
@@ -571,7 +588,7 @@ extern "C" size_t s2e_conv2d_wgrad_multi_workspace_bytes(int dtype, const s2e_wg
         wgrad_multi_plan(jobs, idx_all + base, n, ps, splits);
         for (int i = 0; i < n; ++i)
             if (wgrad_use_partial(splits[i]))
-                total += ((size_t)ps[i].tiles_k * ps[i].tiles_co * splits[i] * (128 * 128 + 128) * sizeof(float) + 255) & ~(size_t)255;
+                total += (generic_partial_bytes(ps[i], splits[i]) + 255) & ~(size_t)255;
     }
     return total;
 }
@@ -612,7 +629,7 @@ extern "C" int s2e_conv2d_wgrad_multi(int dtype, const s2e_wgrad_multi_job* jobs
             p.x = J.x; p.gy = J.gy; p.dw = J.dw; p.dbias = J.dbias;
             const int splits = splits_of[i];
             const int g = p.tiles_k * p.tiles_co * splits;
-            const size_t need = (size_t)g * (128 * 128 + 128) * sizeof(float);
+            const size_t need = generic_partial_bytes(p, splits);
             if (wgrad_use_partial(splits) && ws && ws_left >= need) {
                 p.partial = (float*)ws;
                 p.bpartial = p.partial + (size_t)g * (128 * 128);

@@ -1,5 +1,7 @@
 """Convolutions: weight packs, the raw launchers (s2e_conv2d / s2e_conv2d_wgrad), Conv2dFn with its data / weight / bias gradients
 (spectral norm's chain rule included), the live-prefix gate of the G step's discriminator pass, the encoder's FC head."""
+import collections
+
 import torch
 
 from .. import _lib as L
@@ -60,9 +62,24 @@ def packed_weight(w, dtype, cin_pad, transposed, sigma, plan, generation=None, s
     return pack_weight(w, dtype, cin_pad, transposed, sigma, plane)
 
 
-def _plane_query(shape):
+ConvShape = collections.namedtuple('ConvShape', 'd workspace_bytes plane stats_slots rects')      # a forward / data-gradient shape
+WgradShape = collections.namedtuple('WgradShape', 'd workspace_bytes rects_workspace_bytes')
+
+
+def _conv_shape(wgrad, dt, *shape):
+    """What the library says about ONE conv shape -- its s2e_conv_desc, the workspace of the kernel it routes to, and for a forward
+    shape the plane mode, the statistics slots and whether it takes a rectangle list (for a weight gradient: the workspace of the
+    rectangle form) -- asked once, on first sight of the shape: a step repeats the same ~150 shapes, and building the ctypes
+    structure + the queries cost microseconds of host time per launch."""
+    return memo('conv', (wgrad, dt) + shape, _conv_shape_query, wgrad, dt, shape)
+
+
+def _conv_shape_query(wgrad, dt, shape):
     d = ConvDesc(*shape)
-    return int(L.call.s2e_conv2d_plane_supported(L.S2E_BF16, d))
+    if wgrad:
+        return WgradShape(d, L.call.s2e_conv2d_wgrad_workspace_bytes(dt, d), int(L.call.s2e_conv2d_wgrad_rects_workspace_bytes(dt, d)))
+    return ConvShape(d, L.call.s2e_conv2d_workspace_bytes(dt, d), int(L.call.s2e_conv2d_plane_supported(dt, d)) if dt == L.S2E_BF16 else 0,
+                     int(L.call.s2e_conv2d_stats_slots(dt, d)), bool(L.call.s2e_conv2d_rects_supported(dt, d)))
 
 
 def plane_mode(x_dtype, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, transposed, in_act=ACT_NONE, out_act=ACT_NONE, aux_mode=AUX_NONE,
@@ -71,39 +88,12 @@ def plane_mode(x_dtype, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, trans
     in the PLANE layout (pack_weight(..., plane=True)) and conv2d_raw is called with plane=True.  Memoised per shape."""
     if x_dtype != torch.bfloat16 or (has_res and aux_mode != AUX_NONE):
         return 0
-    key = (n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, int(transposed), in_act, out_act, aux_mode)
-    return memo('plane', key, _plane_query, key)
+    return _conv_shape(False, L.S2E_BF16, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, int(transposed), in_act, out_act, aux_mode).plane
 
 
 # profiler families = the kernel s2e_conv2d / s2e_conv2d_wgrad choose for the shape (S2E_KERNEL_GENERIC / SMALL / PATCH)
 _CONV_FAMILY = ('conv_igemm', 'conv_small', 'conv_patch')
 _WGRAD_FAMILY = ('conv_wgrad', 'conv_wgrad_small', 'conv_wgrad_patch')
-
-
-_CONV_PLANS = {}
-
-
-def _conv_plan(wgrad, dt, *shape):
-    """(s2e_conv_desc, workspace bytes) of a launch, memoised per shape: a step repeats the same ~150 shapes, and building the
-    ctypes structure + asking the library for the workspace size cost ~3 us of host time per launch."""
-    key = (wgrad, dt) + shape
-    ent = _CONV_PLANS.get(key)
-    if ent is None:
-        d = ConvDesc(*shape)
-        wsb = (L.call.s2e_conv2d_wgrad_workspace_bytes if wgrad else L.call.s2e_conv2d_workspace_bytes)(dt, d)
-        if len(_CONV_PLANS) > 8192:
-            _CONV_PLANS.clear()
-        ent = _CONV_PLANS[key] = (d, wsb)
-    return ent
-
-
-def _conv_stats_slots(dt, d, *shape):
-    """s2e_conv2d_stats_slots, memoised per shape."""
-    return memo('stats_slots', (dt,) + shape, _stats_slots_query, dt, d)
-
-
-def _stats_slots_query(dt, d):
-    return int(L.call.s2e_conv2d_stats_slots(dt, d))
 
 
 def conv2d_raw(x, wp, bias, residual, aux, out_hw_c, kh, kw, stride, pad, transposed=False,
@@ -119,7 +109,7 @@ def conv2d_raw(x, wp, bias, residual, aux, out_hw_c, kh, kw, stride, pad, transp
     if out is not None and (tuple(out.shape) != (n, ho, wo, cout) or out.dtype != x.dtype or not out.is_contiguous()):
         raise ValueError('conv2d_raw: out must be a contiguous %s tensor with the shape of the result' % (x.dtype,))
     dt = _dt(x)
-    d, wsb = _conv_plan(False, dt, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, int(transposed), in_act, out_act, aux_mode)
+    d, wsb, _, slots, _ = _conv_shape(False, dt, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, int(transposed), in_act, out_act, aux_mode)
     # algorithmic FLOPs = those of the forward conv this launch computes or differentiates (a stride-2
     # data-gradient executes 4x that on structural zeros; not counted)
     pix = hi * wi if transposed else ho * wo
@@ -132,7 +122,6 @@ def conv2d_raw(x, wp, bias, residual, aux, out_hw_c, kh, kw, stride, pad, transp
                                   + (aux.numel() if aux is not None else 0)) * x.element_size()))
         return y
     if stats_out is not None and aux is None and not transposed:
-        slots = _conv_stats_slots(dt, d, n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, in_act, out_act)
         if slots:
             part = torch.empty(n * slots * cout * 2, dtype=torch.float32, device=x.device)
             LaunchProfiler.run(
@@ -186,7 +175,7 @@ def conv2d_wgrad_raw(x, gy, kh, kw, stride, pad, in_act=ACT_NONE, want_bias=Fals
         return dw, db                                        # accumulated at the step's next flush, with every other queued layer
     if defer_ok and not own_b and GradSink.push_gwg(x, gy, dw, dbp, (n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, 0, in_act, ACT_NONE, AUX_NONE)):
         return dw, db
-    d, wsb = _conv_plan(True, _dt(x), n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, 0, in_act, ACT_NONE, AUX_NONE)
+    d, wsb, _ = _conv_shape(True, _dt(x), n, hi, wi, cin, ho, wo, cout, kh, kw, stride, pad, 0, in_act, ACT_NONE, AUX_NONE)
     ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device) if wsb else None
     LaunchProfiler.run(
         lambda: _WGRAD_FAMILY[L.call.s2e_conv2d_wgrad_kernel_kind(_dt(x), d)], 2.0 * n * ho * wo * cin * cout * kh * kw,

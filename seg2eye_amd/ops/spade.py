@@ -9,9 +9,9 @@ from .. import packing
 from .._lib import NORM_SPADE_STYLE_BATCH, NORM_ACCUMULATE_DX, ACT_NONE, AUX_NONE, AUX_RELU_MASK, NORM_SPADE_STYLE
 from . import switches
 from .core import (IN_EPS, LaunchProfiler, ZeroPool, _adjacent, _cl_dense, _cl_rows, _dt, _grad_dst, _need, _p, _span2, _stream,
-                   device_job_table, memo)
+                   device_job_table)
 from .sink import GradSink
-from .conv import _conv_plan, _unpack_dw, conv2d_raw, conv2d_wgrad_raw, packed_weight, unpack_weight_grad_into
+from .conv import _conv_shape, _unpack_dw, conv2d_raw, conv2d_wgrad_raw, packed_weight, unpack_weight_grad_into
 
 
 def in_stats(x, return_sums=False):
@@ -318,8 +318,7 @@ def _sparse_bwd_lists(ctx, g, h, w, cch, nh, ncls):
     if tw != 16 or th != 16 or h < _SPARSE_BWD_MIN or w < _SPARSE_BWD_MIN or 2 * cch not in (128, 256, 512, 1024) or wdst is None or bdst is None or not wdst.is_contiguous():
         return None
     n = g.shape[0]
-    d, _ = _conv_plan(False, _dt(g), n, h, w, 2 * cch, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK)
-    if not memo('rects_supported', (n, h, w, cch, nh), lambda: bool(L.call.s2e_conv2d_rects_supported(_dt(g), d))):
+    if not _conv_shape(False, _dt(g), n, h, w, 2 * cch, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK).rects:
         return None
     ck = ('rects_bwd', cls.data_ptr(), h, w)
     ent = pool.step_cache.get(ck)
@@ -337,8 +336,7 @@ def _sparse_wgrad(g, actv, gb_dst, sp):
     added by s2e_spade_uniform_grads at the flush.  False: this shape's kernel takes no list (the caller runs the dense one)."""
     n, h, w, nh = actv.shape
     c2 = g.shape[-1]
-    d, _ = _conv_plan(True, _dt(g), n, h, w, nh, h, w, c2, 3, 3, 1, 1, 0, ACT_NONE, ACT_NONE, AUX_NONE)
-    wsb = memo('wgrad_rects_ws', (n, h, w, nh, c2), lambda: int(L.call.s2e_conv2d_wgrad_rects_workspace_bytes(_dt(g), d)))
+    d, _, wsb = _conv_shape(True, _dt(g), n, h, w, nh, h, w, c2, 3, 3, 1, 1, 0, ACT_NONE, ACT_NONE, AUX_NONE)
     dw, db = gb_dst
     if not wsb or db is None or w_strides_differ(dw):
         return False
@@ -399,7 +397,7 @@ def _spade_param_grads(ctx, g, label, w_sh, w_gb, actv):
         dactv = torch.empty(n, h, w, nh, dtype=g.dtype, device=g.device) if lazy else \
             ZeroPool.take(n * h * w * nh, g.dtype, g.device).view(n, h, w, nh)               # (zero where no conv runs)
         c8_rects = (work_list, counts) if lazy else None
-        d, _ = _conv_plan(False, _dt(g), n, h, w, c2, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK)
+        d = _conv_shape(False, _dt(g), n, h, w, c2, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK).d
         flops = 2.0 * n * h * w * c2 * nh * 9
         frac = 1.0
         if LaunchProfiler.active():

@@ -1439,3 +1439,151 @@ def test_an_installed_profiler_records_one_conv_launch():
     assert nbytes == (x.numel() + y.numel() + wp.numel()) * 2
     assert list(summary) == [family] and summary[family]['launches'] == 1 and summary[family]['ms'] > 0
     assert torch.equal(y, y0)
+
+
+# ---- every route of the conv dispatch, launched once with exactly the workspace its query reports
+def _conv_ref64(x, w, stride, pad):
+    """fp64 convolution on the CPU: x (N, H, W, Ci), w (Co, Ci, k, k) -> (N, Ho, Wo, Co); one im2col matmul per sample"""
+    co, ci, k, _ = w.shape
+    n, h, wd, _ = x.shape
+    ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
+    wm = w.reshape(co, ci * k * k).t()
+    return torch.stack([(F.unfold(x[b:b + 1].permute(0, 3, 1, 2), k, padding=pad, stride=stride)[0].t() @ wm).view(ho, wo, co) for b in range(n)])
+
+
+def _wgrad_ref64(x, gy, k, stride, pad):
+    """fp64 weight gradient in the library's layout (Co, (ky, kx, ci)): x (N, H, W, Ci), gy (N, Ho, Wo, Co)"""
+    ci, co = x.shape[-1], gy.shape[-1]
+    dw = sum(gy[b].reshape(-1, co).t() @ F.unfold(x[b:b + 1].permute(0, 3, 1, 2), k, padding=pad, stride=stride)[0].t() for b in range(x.shape[0]))
+    return dw.view(co, ci, k * k).permute(0, 2, 1).reshape(co, k * k * ci)
+
+
+# The smallest shape the dispatch sends to each route (found by sweeping the queries of the commit before conv_route / wgrad_route
+# existed), bf16, and the query answers that identify the route: (family, workspace bytes, statistics slots, takes a rectangle list).
+# The workspace formulas hold for the 256 CUs of an MI355X.  (name, (N, Hi, Wi, Cin, Ho, Wo, Cout, k, stride, pad, transposed), answers)
+_FWD_ROUTES = [
+    # conv_small.hip: one input channel
+    ('small', (1, 4, 4, 1, 2, 2, 8, 3, 2, 1, 0), ('conv_small', 0, 0, 0)),
+    # conv_duo.hip: 4 x 8 x 8 rectangles of 16 x 16 = 256 work items, the threshold; 64 rectangles a sample x 4 wave rows = 256 slots
+    ('duo', (4, 128, 128, 64, 128, 128, 64, 3, 1, 1, 0), ('conv_patch', 0, 256, 1)),
+    # conv_patch.hip, one pass over the channels: 7 samples x 32 rectangles = 224 tiles, the threshold (no duo: 40 output channels)
+    ('patch unsplit', (7, 64, 128, 64, 64, 128, 40, 3, 1, 1, 0), ('conv_patch', 0, 0, 0)),
+    # conv_patch.hip split over channel chunks: too few tiles for one pass, so 4 splits of 2 of the 8 chunks; workspace = splits x M x Cout fp32
+    ('patch split', (5, 64, 34, 512, 64, 34, 40, 3, 1, 1, 0), ('conv_patch', 4 * (5 * 64 * 34) * 40 * 4, 0, 0)),
+    # conv_stream.hip: 67 pixel tiles (>= 64) of 16 K-steps (>= 16), fewer than 8 a CU: two 128 x 64 fp32 partial tiles per CU
+    ('stream', (2, 64, 64, 64, 65, 65, 64, 4, 1, 2, 0), ('conv_igemm', 2 * 256 * 128 * 64 * 4, 0, 0)),
+    # conv_igemm.hip split-K: 8 output channels (no other kernel takes <= 32), 32 K-tiles over 1 tile: 2 splits x M x Cout fp32
+    ('igemm split', (1, 4, 4, 128, 3, 3, 8, 4, 2, 2, 0), ('conv_igemm', 2 * 9 * 8 * 4, 0, 0)),
+    # conv_igemm.hip, a stride-2 data gradient by output-parity class: odd map, so the four classes differ in size; never split
+    ('igemm stride-2 classes', (2, 5, 5, 16, 9, 9, 8, 3, 2, 1, 1), ('conv_igemm', 0, 0, 0)),
+]
+# (name, (N, Hi, Wi, Cin, Ho, Wo, Cout, k, stride, pad), (family, workspace bytes, rectangle-form workspace bytes))
+_WGRAD_ROUTES = [
+    # conv_small.hip: one partial row of 9 x 8 floats for each of the 2 work items
+    ('small', (1, 4, 4, 1, 2, 2, 8, 3, 2, 1), ('conv_wgrad_small', 2 * 9 * 8 * 4, 0)),
+    # conv_wgrad_patch.hip: 7 x 5 slabs of 16 x 8 pixels x 8 channel tiles = 280 items (>= 256); 8 tiles x 18 splits of 9 x 128 x 64 fp32;
+    # no rectangle form (34 is no multiple of 16)
+    ('patch', (7, 34, 16, 512, 34, 16, 64, 3, 1, 1), ('conv_wgrad_patch', 8 * 18 * 9 * 128 * 64 * 4, 0)),
+    # conv_wgrad_patch.hip's 8-channel kernel: 2 x 128 slabs = 256, the threshold; 128 splits of 128 x 80 fp32
+    ('c8', (2, 128, 128, 8, 128, 128, 128, 3, 1, 1), ('conv_wgrad_patch', 128 * 128 * 80 * 4, 0)),
+    # conv_wgrad.hip with partial tiles: one tile, 16 pixel splits (the threshold) of 128 x 128 + 128 fp32
+    ('generic, partial tiles', (1, 64, 64, 1, 64, 64, 1, 1, 1, 0), ('conv_wgrad', 16 * (128 * 128 + 128) * 4, 0)),
+    # conv_wgrad.hip with atomics: one tile, 4225 pixels in 14 splits of 320 (< 16: no partial tiles, no workspace)
+    ('generic, atomics', (1, 64, 64, 8, 65, 65, 8, 4, 1, 2), ('conv_wgrad', 0, 0)),
+]
+S2E_ERR_ARG = -1
+
+
+def test_every_conv_route_runs_with_the_workspace_its_query_reports():
+    """Each route of s2e_conv2d and s2e_conv2d_wgrad once, on the smallest shape that takes it: the queries name the route, the call gets
+    exactly s2e_conv2d[_wgrad]_workspace_bytes of NaN-filled workspace between guard bytes, and every element is compared with fp64 under
+    the bound of tests/_conv3x3_child.py: 2^-8 |ref| + 2^-16 A for a bf16 output, 2^-16 (A_w + |start|) for an fp32 gradient.  With one
+    byte less, the routes that cannot run without their workspace refuse (S2E_ERR_ARG) before anything is launched.  The duo shape is
+    launched once more with a residual AND a mask, the one launch s2e_conv2d keeps out of the duo kernel."""
+    import ctypes as C
+    import _conv3x3_child as c3
+    from seg2eye_amd import ops
+    from seg2eye_amd.ops import conv as oc
+    L, lb = c3.lib()
+    dev, BF = _dev(), L.S2E_BF16
+    assert torch.cuda.get_device_properties(0).multi_processor_count == 256
+    for i, (name, (n, hi, wi, ci, ho, wo, co, k, st, pd, tr), (family, wsb, slots, rects)) in enumerate(_FWD_ROUTES):
+        d = L.ConvDesc(n, hi, wi, ci, ho, wo, co, k, k, st, pd, tr, 0, 0, 0)
+        got = (oc._CONV_FAMILY[lb.s2e_conv2d_kernel_kind(BF, C.byref(d))], int(lb.s2e_conv2d_workspace_bytes(BF, C.byref(d))),
+               lb.s2e_conv2d_stats_slots(BF, C.byref(d)), lb.s2e_conv2d_rects_supported(BF, C.byref(d)))
+        assert got == (family, wsb, slots, rects), (name, got)
+        g = torch.Generator().manual_seed(1700 + i)
+        x = c3.rnd((n, hi, wi, ci), g).to(torch.bfloat16)
+        w = c3.rnd((ci, co, k, k) if tr else (co, ci, k, k), g, (ci * k * k) ** -0.5)          # OIHW of the FORWARD conv
+        b = c3.rnd((co,), g, 0.5)
+        x64, w64, b64 = x.double(), w.to(torch.bfloat16).double(), b.double()
+        if tr:                                                                               # the data gradient of that conv
+            def conv(xx, ww):
+                opad = (ho - ((hi - 1) * st - 2 * pd + k), wo - ((wi - 1) * st - 2 * pd + k))
+                return F.conv_transpose2d(xx.permute(0, 3, 1, 2), ww, stride=st, padding=pd, output_padding=opad).permute(0, 2, 3, 1)
+        else:
+            def conv(xx, ww):
+                return _conv_ref64(xx, ww, st, pd)
+        ref, A = conv(x64, w64) + b64, conv(x64.abs(), w64.abs()) + b64.abs()
+        xd, bd = x.to(dev), b.to(dev)
+        wp = ops.pack_weight(w.to(dev), torch.bfloat16, co if tr else ci, bool(tr))
+
+        def launch(desc, wsbytes, res=None, aux=None):
+            y = c3.Guarded((n, ho, wo, co), torch.bfloat16, dev, float('nan'))
+            ws = c3.workspace(wsbytes, dev)
+            rc = lb.s2e_conv2d(BF, xd.data_ptr(), wp.data_ptr(), bd.data_ptr(), res, aux, y.ptr(), C.byref(desc), ws.ptr(), wsbytes, c3.stream())
+            y.check('%s y' % name)
+            ws.check('%s workspace' % name)
+            return rc, y
+        rc, y = launch(d, wsb)
+        L.check(rc, 's2e_conv2d (%s)' % name)
+        print('forward route %-24s worst err/bound %.3f' % (name, c3.check_close(y.t, ref, A, 'forward route ' + name)))
+        if wsb:
+            rc, y = launch(d, wsb - 1)
+            assert rc == S2E_ERR_ARG and bool(torch.isnan(y.t).all()), (name, rc)
+        if name == 'duo':
+            r = c3.rnd((n, ho, wo, co), g, 0.7, 0.2).to(torch.bfloat16)
+            m = c3.rnd((n, ho, wo, co), g).to(torch.bfloat16)
+            dm = L.ConvDesc(n, hi, wi, ci, ho, wo, co, k, k, st, pd, tr, 0, 0, L.AUX_RELU_MASK)
+            wsm = int(lb.s2e_conv2d_workspace_bytes(BF, C.byref(dm)))
+            rd, md = r.to(dev), m.to(dev)
+            rc, y = launch(dm, wsm, rd.data_ptr(), md.data_ptr())
+            L.check(rc, 's2e_conv2d (duo shape, residual and mask)')
+            keep = (m.double() > 0).double()
+            print('forward route %-24s worst err/bound %.3f' % ('duo shape, res + mask', c3.check_close(
+                y.t, (ref + r.double()) * keep, A + r.double().abs(), 'duo shape with a residual and a mask')))
+    for i, (name, (n, hi, wi, ci, ho, wo, co, k, st, pd), (family, wsb, rects_wsb)) in enumerate(_WGRAD_ROUTES):
+        d = L.ConvDesc(n, hi, wi, ci, ho, wo, co, k, k, st, pd, 0, 0, 0, 0)
+        got = (oc._WGRAD_FAMILY[lb.s2e_conv2d_wgrad_kernel_kind(BF, C.byref(d))], int(lb.s2e_conv2d_wgrad_workspace_bytes(BF, C.byref(d))),
+               int(lb.s2e_conv2d_wgrad_rects_workspace_bytes(BF, C.byref(d))))
+        assert got == (family, wsb, rects_wsb), (name, got)
+        g = torch.Generator().manual_seed(1800 + i)
+        x, gy = c3.rnd((n, hi, wi, ci), g).to(torch.bfloat16), c3.rnd((n, ho, wo, co), g).to(torch.bfloat16)
+        dw0, db0 = c3.rnd((co, k * k * ci), g), c3.rnd((co,), g)
+        x64, g64 = x.double(), gy.double()
+        ref, A = _wgrad_ref64(x64, g64, k, st, pd), _wgrad_ref64(x64.abs(), g64.abs(), k, st, pd)
+        xd, gyd = x.to(dev), gy.to(dev)
+
+        def launch(wsbytes):
+            dw = c3.Guarded((co, k * k * ci), torch.float32, dev, dw0)
+            db = c3.Guarded((co,), torch.float32, dev, db0)
+            ws = c3.workspace(wsbytes, dev)
+            rc = lb.s2e_conv2d_wgrad(BF, xd.data_ptr(), gyd.data_ptr(), dw.ptr(), db.ptr(), C.byref(d), ws.ptr(), wsbytes, c3.stream())
+            for buf, what in ((dw, 'dW'), (db, 'dbias'), (ws, 'workspace')):
+                buf.check('wgrad route %s %s' % (name, what))
+            return rc, dw, db
+
+        def check(dw, db, what):
+            worst = c3.check_close(dw.t, ref, A + dw0.double().abs(), what + ' dW', rel=0.0, start=dw0.double())
+            return max(worst, c3.check_close(db.t, g64.sum((0, 1, 2)), g64.abs().sum((0, 1, 2)) + db0.double().abs(), what + ' dbias',
+                                             rel=0.0, start=db0.double()))
+        rc, dw, db = launch(wsb)
+        L.check(rc, 's2e_conv2d_wgrad (%s)' % name)
+        print('wgrad route   %-24s worst err/bound %.3f' % (name, check(dw, db, 'wgrad route ' + name)))
+        if name == 'small':                                      # cannot run without its partial rows
+            rc, dw, db = launch(wsb - 1)
+            assert rc == S2E_ERR_ARG and torch.equal(dw.t.cpu(), dw0) and torch.equal(db.t.cpu(), db0), (name, rc)
+        elif name == 'c8':                                       # documented: with too little workspace the generic kernel runs
+            rc, dw, db = launch(wsb - 1)
+            L.check(rc, 's2e_conv2d_wgrad (c8, one byte short)')
+            print('wgrad route   %-24s worst err/bound %.3f' % ('c8, one byte short', check(dw, db, 'wgrad route c8, one byte short')))
