@@ -651,6 +651,33 @@ int s2e_ssim_fwd(int dtype, const void* x, const void* y, int N, int H, int W, f
 int s2e_ssim_u8(const uint8_t* a, const uint8_t* b, int N, int H, int W, float* ssim, void* workspace, size_t workspace_bytes, void* stream);
 int s2e_ssim_bwd(int dtype, const void* x, const void* y, const float* maps, const float* gssim, int N, int H, int W, void* dx, void* stream);
 
+/* ------------------------------------------------------------------ region-aware reconstruction error (an extension: the reference has none)
+ * Statistics of d = x - y per image and label class, the class-balanced loss built from them, and its gradient with respect to x.
+ * x, y: single-channel batches (N,H,W) of T in [-1, 1] (or uint8 0..255 for s2e_region_stats_u8); label: uint8 (N,Hl,Wl); ncls in 1..8.
+ * Pixel (n, r, c) has class l = label[n, (r Hl) / H, (c Wl) / W] (integer division); a pixel with l >= ncls belongs to no region: it
+ * enters no count and no sum and gets a zero gradient (a label is compared, never used as an index).
+ *   stats[n][c][3] (fp64) = {count, sum |d|, sum d^2} over image n's pixels of class c.  d, |d|, d^2 are fp32 from the loaded values,
+ *   every sum over pixels is fp64; for uint8 images all three numbers are exact.
+ *   With f = |d| (norm S2E_REGION_L1) or d^2 (S2E_REGION_L2), n_c = sum_n count[n][c], and the classes with n_c > 0 called present:
+ *   loss[0] (fp32) = sum_present w_c (sum_n sum f [n][c] / n_c) / sum_present w_c,   coef[c] (fp32) = w_c / (n_c sum_present w) for a
+ *   present class, else 0;  loss = 0 and coef = 0 when no class of positive weight is present.  weights: ncls fp32, >= 0, on the device.
+ *   s2e_region_loss_bwd:  dx[p] (of T) = gloss[0] coef[l(p)] f'(d(p)),  f' = sign(d) (0 at d == 0, NaN for a NaN d) or 2 d.
+ * A NaN or inf difference puts NaN or inf into its class's sums, the loss and that pixel's gradient; nothing is special-cased.
+ * Forward: two launches (per-block, per-class partial records in `workspace`, plain stores; one fold in index order); backward: one.
+ * No atomics, no synchronisation, launch shapes from (N, H, W, Hl, Wl, ncls) alone, bit-reproducible.
+ * workspace: s2e_region_workspace_bytes(N, H, W, ncls) bytes (0 for N <= 0, H < 1, W < 1 or ncls outside 1..8), uninitialised.
+ * Before any launch, in this order: S2E_ERR_ARG on a null pointer or N <= 0, then a bad dtype, then a bad norm; S2E_ERR_UNSUPPORTED
+ * on ncls outside 1..8, then H, W, Hl or Wl < 1, then N > 65535, H W > 2^24 or N H W >= 2^31; S2E_ERR_ARG on a short workspace. */
+enum { S2E_REGION_L1 = 0, S2E_REGION_L2 = 1 };
+size_t s2e_region_workspace_bytes(int N, int H, int W, int ncls);
+int s2e_region_loss_fwd(int dtype, const void* x, const void* y, const uint8_t* label, int N, int H, int W, int Hl, int Wl, int ncls,
+                        int norm, const float* weights, double* stats, float* loss, float* coef, void* workspace,
+                        size_t workspace_bytes, void* stream);
+int s2e_region_stats_u8(const uint8_t* a, const uint8_t* b, const uint8_t* label, int N, int H, int W, int Hl, int Wl, int ncls,
+                        double* stats, void* workspace, size_t workspace_bytes, void* stream);
+int s2e_region_loss_bwd(int dtype, const void* x, const void* y, const uint8_t* label, const float* coef, const float* gloss,
+                        int N, int H, int W, int Hl, int Wl, int ncls, int norm, void* dx, void* stream);
+
 /* ------------------------------------------------------------------ side-by-side validation panels
  * The reference's visualize_sidebyside (util/visualizer.py:131-166) for a batch of n samples, as three launches on the caller's
  * stream with no host synchronisation between them: out[i] = [ style | label | target_original | fake | heat ], five h x w cells of

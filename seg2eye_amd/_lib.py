@@ -20,6 +20,7 @@ AUX_NONE, AUX_RELU_MASK, AUX_LRELU_GRAD = 0, 1, 2
 NORM_SPADE_STYLE, NORM_PLAIN_IN, NORM_SPADE_STYLE_BATCH = 0, 1, 2
 NORM_ACCUMULATE_DX = 0x100
 LOSS_NEG_MEAN, LOSS_HINGE_REAL, LOSS_HINGE_FAKE, LOSS_L1, LOSS_L1_NANGRAD = 0, 1, 2, 3, 4
+REGION_L1, REGION_L2 = 0, 1
 
 
 class ConvDesc(C.Structure):
@@ -173,6 +174,10 @@ SIGNATURES = {
     's2e_ssim_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
     's2e_ssim_u8': (STATUS, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
     's2e_ssim_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    's2e_region_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_region_loss_fwd': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    's2e_region_stats_u8': (STATUS, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
+    's2e_region_loss_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     's2e_bilinear_resize_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_bilinear_resize_bwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_upsample2x_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -1,5 +1,5 @@
 """Loss reductions (hinge / L1 / feature matching with in-place gradient injection), the flat Adam step, and the OpenEDS validation
-metric and SSIM kernels."""
+metric, SSIM and region-error kernels."""
 import torch
 
 from .. import _lib as L
@@ -317,6 +317,106 @@ def ssim_u8(a, b):
     LaunchProfiler.run('ssim_fwd', flops, L.call.s2e_ssim_u8, (_p(a), _p(b), n, h, w, _p(out), _p(ws), ws.numel() * 8, _stream()),
                        nbytes=float(2 * a.numel()))
     return out
+
+
+_REGION_NORMS = {'l1': L.REGION_L1, 'l2': L.REGION_L2}
+
+
+def _region_workspace(n, h, w, ncls, device):
+    return torch.empty(int(L.call.s2e_region_workspace_bytes(n, h, w, ncls)) // 8, dtype=torch.float64, device=device)
+
+
+def _region_label(label, n):
+    """uint8 (N,Hl,Wl), contiguous ((N,1,Hl,Wl) accepted)."""
+    if label.dim() == 4 and label.shape[1] == 1:
+        label = label[:, 0]
+    if label.dim() != 3 or label.shape[0] != n or label.dtype != torch.uint8:
+        raise ValueError('label: a uint8 map (N,Hl,Wl) with the images\' N expected, got %s %s' % (label.dtype, tuple(label.shape)))
+    return label.contiguous()
+
+
+def _region_ncls(ncls):
+    if not 1 <= int(ncls) <= 8:
+        raise ValueError('1 to 8 classes expected, got %d' % ncls)
+    return int(ncls)
+
+
+class RegionLossFn(torch.autograd.Function):
+    """(loss, stats) of s2e_region_loss_fwd (two launches); the backward is s2e_region_loss_bwd on the saved images, label and the
+    per-class coefficients the fold wrote (one launch), for x only.  When x needs no gradient nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, x, y, label, weights, norm):
+        a, b = _single_channel(x.detach()), _single_channel(y.detach().to(x.dtype))
+        lb = _region_label(label, a.shape[0])
+        if a.shape != b.shape:
+            raise ValueError('x and y of one shape expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+        _need(a, b, lb, weights)
+        n, h, w = a.shape
+        ncls = weights.numel()
+        stats = torch.empty(n, ncls, 3, dtype=torch.float64, device=a.device)
+        loss = torch.empty((), dtype=torch.float32, device=a.device)
+        coef = torch.empty(ncls, dtype=torch.float32, device=a.device)
+        ws = _region_workspace(n, h, w, ncls, a.device)
+        LaunchProfiler.run('region_fwd', float(4 * a.numel()), L.call.s2e_region_loss_fwd,
+                           (_dt(a), _p(a), _p(b), _p(lb), n, h, w, lb.shape[1], lb.shape[2], ncls, norm, _p(weights), _p(stats), _p(loss),
+                            _p(coef), _p(ws), ws.numel() * 8, _stream()),
+                           nbytes=float(2 * a.numel() * a.element_size() + (lb.numel() if lb.shape[1:] == a.shape[1:] else a.numel())))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(a, b, lb, coef)
+        ctx.cfg = (x.shape, ncls, norm)
+        ctx.mark_non_differentiable(stats)
+        return loss, stats
+
+    @staticmethod
+    def backward(ctx, gloss, _gstats):
+        if not ctx.saved_tensors:
+            return None, None, None, None, None
+        a, b, lb, coef = ctx.saved_tensors
+        x_shape, ncls, norm = ctx.cfg
+        n, h, w = a.shape
+        gs = gloss.detach().float().contiguous()
+        dx = torch.empty_like(a)
+        LaunchProfiler.run('region_bwd', float(3 * a.numel()), L.call.s2e_region_loss_bwd,
+                           (_dt(a), _p(a), _p(b), _p(lb), _p(coef), _p(gs), n, h, w, lb.shape[1], lb.shape[2], ncls, norm, _p(dx), _stream()),
+                           nbytes=float(3 * a.numel() * a.element_size() + (lb.numel() if lb.shape[1:] == a.shape[1:] else a.numel())))
+        return dx.view(x_shape), None, None, None, None
+
+
+def region_loss(x, y, label, weights, norm='l1'):
+    """The class-balanced reconstruction error of two single-channel batches in [-1, 1]: per class c the mean of |x - y|
+    ('l1') or (x - y)^2 ('l2') over the batch's pixels of that class, the classes present in the batch averaged by `weights` (fp32,
+    one per class, on the device; or a sequence of numbers).  label: uint8 (N,Hl,Wl), looked up at [(r Hl) // H, (c Wl) // W]; a class
+    >= len(weights) belongs to no region.  -> (loss: 0-dim fp32, differentiable in x only (y is cast to x's dtype);
+    stats: (N, ncls, 3) float64 {count, sum |d|, sum d^2} per image and class, detached)."""
+    if norm not in _REGION_NORMS:
+        raise ValueError("norm: 'l1' or 'l2' expected, got %r" % (norm,))
+    if not torch.is_tensor(weights):
+        weights = torch.tensor([float(v) for v in weights], dtype=torch.float32, device=x.device)
+    if weights.dtype != torch.float32 or weights.dim() != 1:
+        raise ValueError('weights: one fp32 number per class expected')
+    _region_ncls(weights.numel())
+    return RegionLossFn.apply(x, y, label, weights, _REGION_NORMS[norm])
+
+
+def region_stats_u8(a, b, label, ncls):
+    """{count, sum |a - b|, sum (a - b)^2} per image and class of uint8 images that already are 0..255, by the label lookup of
+    region_loss.  -> (N, ncls, 3) float64, every number exact; no gradient."""
+    a, b = _single_channel(a), _single_channel(b)
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise ValueError('uint8 images expected')
+    ncls = _region_ncls(ncls)
+    lb = _region_label(label, a.shape[0])
+    if a.shape != b.shape:
+        raise ValueError('a and b of one shape expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    _need(a, b, lb)
+    n, h, w = a.shape
+    stats = torch.empty(n, ncls, 3, dtype=torch.float64, device=a.device)
+    ws = _region_workspace(n, h, w, ncls, a.device)
+    LaunchProfiler.run('region_fwd', float(4 * a.numel()), L.call.s2e_region_stats_u8,
+                       (_p(a), _p(b), _p(lb), n, h, w, lb.shape[1], lb.shape[2], ncls, _p(stats), _p(ws), ws.numel() * 8, _stream()),
+                       nbytes=float(3 * a.numel()))
+    return stats
 
 
 def resize_to255(x, w=400, h=640):

@@ -43,6 +43,9 @@ _DEFAULTS = dict(
     diffaug='',                # differentiable augmentation of D's input: parts of 'color,translation,cutout' (seg2eye_amd/diffaug.py); '' = off
     diffaug_seed=0,            # the sampler's CPU generator is seeded diffaug_seed + rank
     lambda_ssim=0.0,           # > 0: lambda_ssim * (1 - mean SSIM(fake, target)) joins the generator's loss (ops.ssim); 0 = off
+    lambda_region=0.0,         # > 0: lambda_region * the class-balanced reconstruction error joins the generator's loss (ops.region_loss); 0 = off
+    region_norm='l1',          # 'l1' | 'l2': the per-pixel error of that term
+    region_weights='',         # 'w0,w1,...': one non-negative weight per label class (parse_region_weights); '' = all ones
 )
 
 
@@ -58,6 +61,24 @@ def default_opt(**overrides):
     if isinstance(d['gpu_ids'], str):         # options/base_options.py:153-158
         d['gpu_ids'] = [int(s) for s in d['gpu_ids'].split(',') if int(s) >= 0]
     return argparse.Namespace(**d)
+
+
+def parse_region_weights(text, label_nc):
+    """--region_weights: exactly label_nc non-negative finite numbers separated by commas, at least one positive; '' = all ones.
+    -> list of floats; anything else is a ValueError."""
+    if text is None or str(text).strip() == '':
+        return [1.0] * int(label_nc)
+    try:
+        ws = [float(t) for t in str(text).split(',')]
+    except ValueError:
+        raise ValueError("--region_weights '%s': numbers separated by commas expected" % text) from None
+    if len(ws) != int(label_nc):
+        raise ValueError("--region_weights '%s': %d weights for %d label classes" % (text, len(ws), label_nc))
+    if not all(w >= 0.0 and w != float('inf') for w in ws):          # (a NaN fails w >= 0)
+        raise ValueError("--region_weights '%s': every weight must be finite and not negative" % text)
+    if not any(w > 0.0 for w in ws):
+        raise ValueError("--region_weights '%s': at least one weight must be positive" % text)
+    return ws
 
 
 def latent_size(opt):
@@ -122,6 +143,9 @@ _CLI = [  # (name, type or 'flag', default, choices)
     # validation also scores SSIM on the 640 x 400 uint8 pair the OpenEDS error sees (ops.ssim_u8): 'ssim/<key>/<mode>' in
     # the statistics (higher is better), `ssim` in the error log; off = validation as it was
     ('val_ssim', 'flag', False, None),
+    # validation also takes the error apart by label class (ops.region_stats_u8 on the same uint8 pair):
+    # 'region_mae/<key>/<mode>/<c>' and 'region_rmse/<key>/<mode>/<c>' in the statistics (grey levels), `region` in the error log
+    ('val_regions', 'flag', False, None),
 ]
 _CLI_TRAIN_BUILD = [
     ('ema_decay', _F, 0.0, None), ('ema_start', _I, 0, None),        # averaged generator weights; 0 = off
@@ -134,6 +158,9 @@ _CLI_TRAIN_BUILD = [
     # structural-similarity term of the generator's loss: lambda_ssim * (1 - mean SSIM(fake, target)); 'SSIM/raw' in the
     # loss log is the mean SSIM itself, so HIGHER is better (1 = identical); 0 = off, nothing is launched
     ('lambda_ssim', _F, 0.0, None),
+    # class-balanced reconstruction term of the generator's loss: every label class counts by its weight, not by its area;
+    # 'region/raw' in the loss log is the term before lambda_region; 0 = off, nothing is launched
+    ('lambda_region', _F, 0.0, None), ('region_norm', _S, 'l1', ['l1', 'l2']), ('region_weights', _S, '', None),
 ]
 _CLI_TEST_BUILD = [
     ('use_ema', 'flag', False, None),                                 # score / generate with the averaged weights' checkpoint files
@@ -186,6 +213,7 @@ def parse(argv=None, is_train=True):
         raise ValueError('--ema_decay must lie in [0, 1) (0 = off) and --ema_start must not be negative')
     if not opt.grad_clip_norm >= 0.0 or opt.max_consecutive_skips < 0:
         raise ValueError('--grad_clip_norm (0 = off) and --max_consecutive_skips (0 = never stop) must not be negative')
+    parse_region_weights(opt.region_weights, opt.label_nc)   # (a malformed list raises ValueError here, not at the first step)
     if opt.diffaug:
         from .diffaug import parse_policy
         parse_policy(opt.diffaug)                          # (an unknown part raises ValueError)

@@ -38,6 +38,13 @@ class Pix2PixModel(nn.Module):
         # trainer around each G / D step; None (always, outside a trainer's step): D sees its input as it is
         self.diffaug = diffaug.parse_policy(getattr(opt, 'diffaug', '') or '') if opt.isTrain else frozenset()
         self.diffaug_rows = None
+        # --lambda_region: the class weights as the fp32 device tensor s2e_region_loss_fwd reads, made once -- a captured
+        # step reads the same address at every replay; None (the flag absent): nothing is allocated
+        self.region_w = None
+        if opt.isTrain and getattr(opt, 'lambda_region', 0):
+            from .options import parse_region_weights
+            self.region_w = torch.tensor(parse_region_weights(getattr(opt, 'region_weights', ''), opt.label_nc), dtype=torch.float32,
+                                         device=self.device())
         if opt.isTrain:
             self.criterionGAN = networks.GANLoss(opt.gan_mode, opt=opt)
             if not opt.no_vgg_loss:
@@ -211,6 +218,12 @@ class Pix2PixModel(nn.Module):
             s = ops.ssim(fake_image, target_image).mean()
             G_losses['SSIM/weighted'] = (opt.lambda_ssim * (1.0 - s)).view(1)
             self.add_to_loss_log('SSIM/raw', s.detach())          # (the mean SSIM itself: higher is better)
+        if getattr(opt, 'lambda_region', 0):
+            # class-balanced error of the un-augmented fake against the target, keyed by the step's own label map (an
+            # extension): two launches, one in the backward
+            r, _ = ops.region_loss(fake_image, target_image, seg.label, self.region_w, getattr(opt, 'region_norm', 'l1'))
+            G_losses['region/weighted'] = (opt.lambda_region * r).view(1)
+            self.add_to_loss_log('region/raw', r.detach().view(1))
         if getattr(self.opt, 'lambda_openeds', 0):
             # pix2pix_model.py:206-210: the OpenEDS metric of the batch (per image; no gradient -- the reference's
             # `.int()` cuts the graph too), weighted into the logged loss
