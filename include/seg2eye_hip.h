@@ -273,7 +273,8 @@ int s2e_in_stats_from_partials(const float* part, int N, int P, int C, int HW, f
  *     style (N, 2C) fp32 = {s0 | s1} (already through FC + LeakyReLU, normalization.py:135-141)
  * mode S2E_NORM_PLAIN_IN (InstanceNorm2d + LeakyReLU of discriminator.py:91-94, encoder.py IN):
  *     out = (x-mean)*rstd            (gb, style unused; may be NULL)
- * lrelu != 0 applies LeakyReLU(0.2) to out. */
+ * lrelu != 0 applies LeakyReLU(0.2) to out: slope 0.2 unless the argument is > 0 (torch's convention), so every backward
+ * below takes 0.2 AT zero too -- an exactly constant channel gets the same gradient whichever kernel its map size selects. */
 int s2e_modulate_fwd(int dtype, int mode, const void* x, const void* gb, const float* stats, const float* style,
                      void* out, int N, int HW, int C, int lrelu, int style_ld, void* stream);
 /* The [gamma | beta] conv of a SPADE and the SPADE+Style modulation in ONE kernel (SPADE.forward normalization.py:97-105 +

@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__
 #pragma unroll
                 for (int j = 0; j < VEC; ++j) {
                     const float xh = (fx[j] - mu[j]) * rs[j];
-                    const float go = (lrelu && xh < 0.f) ? 0.2f * fg[j] : fg[j];
+                    const float go = (lrelu && !(xh > 0.f)) ? 0.2f * fg[j] : fg[j];      // slope 0.2 AT zero too, as every other kernel and torch
                     s0[j] += go; s1[j] += go * xh;
                 }
             }
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void in_small_bwd_kernel(const T* __restrict__
 #pragma unroll
             for (int j = 0; j < VEC; ++j) {
                 const float xh = (fx[j] - mu[j]) * rs[j];
-                const float go = (lrelu && xh < 0.f) ? 0.2f * fg[j] : fg[j];
+                const float go = (lrelu && !(xh > 0.f)) ? 0.2f * fg[j] : fg[j];      // slope 0.2 AT zero too, as every other kernel and torch
                 o[j] = rs[j] * (go - m0[j] - xh * m1[j]);
             }
             *(u32x4_t*)(dx + off + (size_t)(r + RL * k) * C) = pack16<T>(o);
