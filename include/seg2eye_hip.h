@@ -652,6 +652,37 @@ int s2e_ssim_fwd(int dtype, const void* x, const void* y, int N, int H, int W, f
 int s2e_ssim_u8(const uint8_t* a, const uint8_t* b, int N, int H, int W, float* ssim, void* workspace, size_t workspace_bytes, void* stream);
 int s2e_ssim_bwd(int dtype, const void* x, const void* y, const float* maps, const float* gssim, int N, int H, int W, void* dx, void* stream);
 
+/* ------------------------------------------------------------------ multi-scale structural similarity (an extension: the reference has none)
+ * MS-SSIM (Wang, Simoncelli, Bovik 2003) of two single-channel batches x, y (N,H,W) and its gradient with respect to x, on the window,
+ * the placement, the units and the constants of s2e_ssim_*.  levels L in 1..5.  Level 0 is the image; level j + 1 is the 2 x 2 mean,
+ * stride 2, of level j, a trailing odd row or column dropped: H_j = H >> j, W_j = W >> j, P_j = (H_j - 10)(W_j - 10) positions.  Legal
+ * sizes have H >> (L-1) >= 11 and W >> (L-1) >= 11.  For image n:
+ *   m_j[n] = the mean over level j's positions of cs = (2 suv + C2) / (su2 + sv2 + C2) for j < L-1, of the full S for j = L-1,
+ *   msssim[n] (fp32) = prod_j max(m_j[n], F)^weights[j],   F = 1e-3 (a level at or below the floor counts as F and passes no gradient).
+ * weights: a HOST array of L positive finite floats (they travel by value); the published five are 0.0448, 0.2856, 0.3001, 0.2363, 0.1333.
+ * terms (N,L) fp32 = m_j[n] before the clamp; coef (N,L) fp32 = d msssim[n] / d m_j[n] = weights[j] msssim[n] / m_j[n], 0 where m_j[n] < F.
+ * Forward, three launches (two when L = 1): the pyramid (levels 1..L-1 of both images, fp32 in the input's own units, into `pyramid`);
+ * the moment passes of the tiles of all levels (one fp64 partial per tile into `workspace`; when maps is not NULL the planes A, B, C of
+ * every level, level j's three (N,H_j-10,W_j-10) planes after those of the levels before it); the fold, per image, each level's partials
+ * in index order.  s2e_msssim_bwd, two launches (one when L = 1): g_j = gout[n] coef[n][j] / P_j * (s2e_ssim_bwd's three correlations on
+ * level j's maps) for the levels 1..L-1 into gbuf (fp32, (N,H_j,W_j) per level), then
+ *   dx[n,p] (of T) = 1/2 sum_j 4^-j g_j(p >> j),    over the levels whose field holds p >> j.
+ * No atomics, no synchronisation, launch shapes from (N, H, W, levels) alone, bit-reproducible.
+ * Sizes: s2e_msssim_workspace_bytes, s2e_msssim_pyramid_bytes (0 when L = 1: pyramid and gbuf may then be NULL) and s2e_msssim_maps_bytes;
+ * each is 0 for N <= 0, levels outside 1..5 or an illegal size.  gbuf needs half of s2e_msssim_pyramid_bytes.  All uninitialised.
+ * Before any launch: S2E_ERR_ARG on a null pointer (maps of s2e_msssim_fwd excepted), N <= 0, a bad dtype, levels outside 1..5, a weight
+ * that is not positive and finite, a short buffer; S2E_ERR_UNSUPPORTED on a last level below 11 x 11, N > 65535 or N H W >= 2^31. */
+size_t s2e_msssim_workspace_bytes(int N, int H, int W, int levels);
+size_t s2e_msssim_pyramid_bytes(int N, int H, int W, int levels);
+size_t s2e_msssim_maps_bytes(int N, int H, int W, int levels);
+int s2e_msssim_fwd(int dtype, const void* x, const void* y, int N, int H, int W, int levels, const float* weights, float* msssim,
+                   float* terms, float* coef, float* maps, size_t maps_bytes, void* pyramid, size_t pyramid_bytes, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int s2e_msssim_u8(const uint8_t* a, const uint8_t* b, int N, int H, int W, int levels, const float* weights, float* msssim, float* terms,
+                  void* pyramid, size_t pyramid_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int s2e_msssim_bwd(int dtype, const void* x, const void* y, const void* pyramid, const float* maps, const float* coef, const float* gout,
+                   int N, int H, int W, int levels, void* gbuf, size_t gbuf_bytes, void* dx, void* stream);
+
 /* ------------------------------------------------------------------ region-aware reconstruction error (an extension: the reference has none)
  * Statistics of d = x - y per image and label class, the class-balanced loss built from them, and its gradient with respect to x.
  * x, y: single-channel batches (N,H,W) of T in [-1, 1] (or uint8 0..255 for s2e_region_stats_u8); label: uint8 (N,Hl,Wl); ncls in 1..8.

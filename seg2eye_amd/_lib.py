@@ -174,6 +174,12 @@ SIGNATURES = {
     's2e_ssim_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
     's2e_ssim_u8': (STATUS, [_vp, _vp, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
     's2e_ssim_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    's2e_msssim_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_msssim_pyramid_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_msssim_maps_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_msssim_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    's2e_msssim_u8': (STATUS, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    's2e_msssim_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
     's2e_region_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
     's2e_region_loss_fwd': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     's2e_region_stats_u8': (STATUS, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),

@@ -8,37 +8,9 @@
 // values are du = u - cu, formed from the loaded numbers BEFORE the map to [0, 1] ((x - xc) / 2: exact or one small relative
 // rounding), and the means are put back as mu = cu + mean(du).  The backward does the same to the saved maps: with
 // A' = A + 2 cu B + cv C the gradient is sum g (A') + 2 du sum g B + dv sum g C, three correlations of small numbers.
-#include "common.h"
+#include "ssim_tile.h"
 
 namespace {
-
-constexpr int SS_TAPS = 11, SS_R = SS_TAPS - 1;             // window taps; rows / columns a window reaches past its first
-constexpr int SS_TH = 16, SS_TW = 32;                        // outputs of one workgroup (256 threads: two rows of 32 each)
-constexpr int SS_IH = SS_TH + SS_R, SS_IW = SS_TW + SS_R;    // the staged tile: 26 x 42
-constexpr float SS_C1 = 0.01f * 0.01f, SS_C2 = 0.03f * 0.03f;
-
-// the window, computed once on the host in fp64 and passed by value: the taps sit in scalar registers
-struct SsimWin { float g[SS_TAPS]; };
-
-// what a loaded number means: T in [-1, 1] -> u = (x + 1) / 2; uint8 0..255 -> u = a / 255.  centre: u of the tile's first pixel;
-// delta: u - centre from the loaded numbers themselves
-template <typename T> struct SsimIn {
-    static __device__ __forceinline__ float centre(float xc) { return (xc + 1.f) * 0.5f; }
-    static __device__ __forceinline__ float delta(float x, float xc) { return (x - xc) * 0.5f; }
-};
-template <> struct SsimIn<uint8_t> {
-    static __device__ __forceinline__ float centre(float xc) { return xc / 255.f; }
-    static __device__ __forceinline__ float delta(float x, float xc) { return (x - xc) / 255.f; }
-};
-
-// the block's sum of v (fp64), valid in thread 0: lanes by shuffles, then the four waves in order
-__device__ __forceinline__ double ssim_block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // ---------------------------------------------------------------------------------------- forward
 // grid (tiles, N).  part[n][tile] = sum of S over the tile's valid positions; maps (when not null): A = dS/dmu_u, B = dS/dE[u^2],
@@ -58,30 +30,9 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const T* __restrict__ x, 
     const float xc = load1<T>(xs + (size_t)ty0 * W + tx0), yc = load1<T>(ys + (size_t)ty0 * W + tx0);
     const float cu = In::centre(xc), cv = In::centre(yc);
 
-    for (int i = threadIdx.x; i < SS_IH * SS_IW; i += 256) {                       // rows of 42 consecutive elements
-        const int r = i / SS_IW, c = i - r * SS_IW, gy = ty0 + r, gx = tx0 + c;
-        float du = 0.f, dv = 0.f;                                                  // past the image: read by no valid output
-        if (gy < H && gx < W) {
-            const size_t o = (size_t)gy * W + gx;
-            du = In::delta(load1<T>(xs + o), xc);
-            dv = In::delta(load1<T>(ys + o), yc);
-        }
-        su[r][c] = du; sv[r][c] = dv;
-    }
+    ssim_stage_pair<In, T>(xs, ys, H, W, ty0, tx0, xc, yc, su, sv);
     __syncthreads();
-    // horizontal pass: the five products of every staged row at the 32 output columns (a half-wave reads 32 consecutive words)
-    for (int i = threadIdx.x; i < SS_IH * SS_TW; i += 256) {
-        const int r = i / SS_TW, c = i - r * SS_TW;
-        float mu = 0.f, mv = 0.f, uu = 0.f, vv = 0.f, uv = 0.f;
-#pragma unroll
-        for (int k = 0; k < SS_TAPS; ++k) {
-            const float a = su[r][c + k], b = sv[r][c + k], w = win.g[k];
-            const float wa = w * a, wb = w * b;
-            mu += wa; mv += wb;
-            uu = fmaf(wa, a, uu); vv = fmaf(wb, b, vv); uv = fmaf(wa, b, uv);
-        }
-        sh[0][r][c] = mu; sh[1][r][c] = mv; sh[2][r][c] = uu; sh[3][r][c] = vv; sh[4][r][c] = uv;
-    }
+    ssim_hpass5(su, sv, sh, win);
     __syncthreads();
     // vertical pass, S and its three derivatives: thread (ty, tx) serves rows ty and ty + 8
     const int tx = threadIdx.x & (SS_TW - 1), tyb = threadIdx.x / SS_TW;
@@ -90,13 +41,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const T* __restrict__ x, 
 #pragma unroll
     for (int h = 0; h < SS_TH / 8; ++h) {
         const int ty = tyb + 8 * h, oy = ty0 + ty, ox = tx0 + tx;
-        float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < SS_TAPS; ++k) {
-            const float w = win.g[k];
-#pragma unroll
-            for (int j = 0; j < 5; ++j) m[j] = fmaf(w, sh[j][ty + k][tx], m[j]);
-        }
+        float m[5];
+        ssim_vpass5(sh, ty, tx, win, m);
         if (oy < Ho && ox < Wo) {
             const float su2 = m[2] - m[0] * m[0], sv2 = m[3] - m[1] * m[1], suv = m[4] - m[0] * m[1];   // about (cu, cv): small numbers
             const float mu = cu + m[0], mv = cv + m[1];
@@ -156,44 +102,17 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const T* __restrict__ x, 
     const float* mB = mA + (size_t)N * plane;
     const float* mC = mB + (size_t)N * plane;
 
-    for (int i = threadIdx.x; i < SS_IH * SS_IW; i += 256) {                       // staged position (r, c) = (py0 - 10 + r, px0 - 10 + c)
-        const int r = i / SS_IW, c = i - r * SS_IW, qy = py0 - SS_R + r, qx = px0 - SS_R + c;
-        float a = 0.f, b = 0.f, cc = 0.f;
-        if (qy >= 0 && qy < Ho && qx >= 0 && qx < Wo) {
-            const size_t o = (size_t)qy * Wo + qx;
-            b = mB[o]; cc = mC[o];
-            a = fmaf(2.f * cu, b, fmaf(cv, cc, mA[o]));                            // A' = A + 2 cu B + cv C
-        }
-        sm[0][r][c] = a; sm[1][r][c] = b; sm[2][r][c] = cc;
-    }
+    ssim_stage_maps(mA, mB, mC, Ho, Wo, py0, px0, cu, cv, sm);
     __syncthreads();
-    // horizontal pass: pixel column c takes tap k from the position k columns to its left (staged column c + 10 - k)
-    for (int i = threadIdx.x; i < SS_IH * SS_TW; i += 256) {
-        const int r = i / SS_TW, c = i - r * SS_TW;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < SS_TAPS; ++k) {
-            const float w = win.g[k];
-            s0 = fmaf(w, sm[0][r][c + SS_R - k], s0);
-            s1 = fmaf(w, sm[1][r][c + SS_R - k], s1);
-            s2 = fmaf(w, sm[2][r][c + SS_R - k], s2);
-        }
-        sh[0][r][c] = s0; sh[1][r][c] = s1; sh[2][r][c] = s2;
-    }
+    ssim_hpass3(sm, sh, win);
     __syncthreads();
     const int tx = threadIdx.x & (SS_TW - 1), tyb = threadIdx.x / SS_TW;
     const float scale = gssim[n] / (float)plane * In::delta(1.f, 0.f);             // (du/dx = 1/2)
 #pragma unroll
     for (int h = 0; h < SS_TH / 8; ++h) {
         const int ty = tyb + 8 * h, py = py0 + ty, px = px0 + tx;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < SS_TAPS; ++k) {
-            const float w = win.g[k];
-            s0 = fmaf(w, sh[0][ty + SS_R - k][tx], s0);
-            s1 = fmaf(w, sh[1][ty + SS_R - k][tx], s1);
-            s2 = fmaf(w, sh[2][ty + SS_R - k][tx], s2);
-        }
+        float s0, s1, s2;
+        ssim_vpass3(sh, ty, tx, win, s0, s1, s2);
         if (py < H && px < W) {
             const size_t o = (size_t)py * W + px;
             const float du = In::delta(load1<T>(xs + o), xc), dv = In::delta(load1<T>(ys + o), yc);
@@ -201,18 +120,6 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const T* __restrict__ x, 
         }
     }
 }
-
-SsimWin ssim_window() {
-    double g[SS_TAPS], sum = 0.0;
-    for (int i = 0; i < SS_TAPS; ++i) { const double d = i - SS_R / 2; g[i] = exp(-d * d / (2.0 * 1.5 * 1.5)); sum += g[i]; }
-    SsimWin w;
-    for (int i = 0; i < SS_TAPS; ++i) w.g[i] = (float)(g[i] / sum);
-    return w;
-}
-
-// tiles of an h x w field (the outputs forward, the input pixels backward)
-inline long ssim_tiles_x(int w) { return (w + SS_TW - 1) / SS_TW; }
-inline long ssim_tiles(int h, int w) { return (long)((h + SS_TH - 1) / SS_TH) * ssim_tiles_x(w); }
 
 // the size checks every entry shares, after its own pointer checks: S2E_ERR_UNSUPPORTED
 int ssim_check_size(const char* name, int N, int H, int W) {

@@ -1,5 +1,5 @@
 """Loss reductions (hinge / L1 / feature matching with in-place gradient injection), the flat Adam step, and the OpenEDS validation
-metric, SSIM and region-error kernels."""
+metric, SSIM, MS-SSIM and region-error kernels."""
 import torch
 
 from .. import _lib as L
@@ -317,6 +317,116 @@ def ssim_u8(a, b):
     LaunchProfiler.run('ssim_fwd', flops, L.call.s2e_ssim_u8, (_p(a), _p(b), n, h, w, _p(out), _p(ws), ws.numel() * 8, _stream()),
                        nbytes=float(2 * a.numel()))
     return out
+
+
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)    # Wang, Simoncelli, Bovik 2003, as published (sum 1.0001: not renormalised)
+
+
+def msssim_min_size(levels=len(MSSSIM_WEIGHTS)):
+    """The smallest H (and W) with a window position at the last of `levels` levels: 11 << (levels - 1); 176 at five."""
+    return 11 << (int(levels) - 1)
+
+
+def _msssim_weights(weights):
+    """-> (levels, a ctypes array of that many floats: the host array the entry points read).  None: the published five."""
+    ws = [float(v) for v in (MSSSIM_WEIGHTS if weights is None else weights)]
+    if not 1 <= len(ws) <= 5:
+        raise ValueError('1 to 5 level weights expected, got %d' % len(ws))
+    return len(ws), (L.C.c_float * len(ws))(*ws)
+
+
+def _msssim_buffers(n, h, w, levels, device, maps):
+    """(workspace, pyramid, maps or None): uninitialised, sized by the library's queries (an illegal size gives empty buffers and the
+    entry point then says why)."""
+    q = L.call
+    ws = torch.empty(max(1, int(q.s2e_msssim_workspace_bytes(n, h, w, levels)) // 8), dtype=torch.float64, device=device)
+    pyr = torch.empty(int(q.s2e_msssim_pyramid_bytes(n, h, w, levels)) // 4, dtype=torch.float32, device=device)
+    mp = torch.empty(int(q.s2e_msssim_maps_bytes(n, h, w, levels)) // 4, dtype=torch.float32, device=device) if maps else None
+    return ws, pyr, mp
+
+
+def _msssim_cost(n, h, w, levels, planes):
+    """(algorithmic FLOPs, positions) over the levels, as _ssim_cost counts one."""
+    pos = sum(n * max((h >> j) - 10, 0) * max((w >> j) - 10, 0) for j in range(levels))
+    return float(2 * 2 * 11 * planes * pos), pos
+
+
+class MsSsimFn(torch.autograd.Function):
+    """(msssim (N,), terms (N,L)) of two (N,H,W) batches in [-1, 1] (s2e_msssim_fwd: three launches); the backward is s2e_msssim_bwd on the
+    saved pyramid, maps and coefficients (two launches), for x only.  When x needs no gradient nothing is saved and no maps are allocated."""
+
+    @staticmethod
+    def forward(ctx, x, y, weights):
+        a, b = _single_channel(x.detach()), _single_channel(y.detach().to(x.dtype))
+        _need(a, b)
+        n, h, w = a.shape
+        levels, wts = _msssim_weights(weights)
+        out = torch.empty(n, dtype=torch.float32, device=a.device)
+        terms = torch.empty(n, levels, dtype=torch.float32, device=a.device)
+        coef = torch.empty(n, levels, dtype=torch.float32, device=a.device)
+        ws, pyr, maps = _msssim_buffers(n, h, w, levels, a.device, ctx.needs_input_grad[0])
+        if maps is not None and maps.numel() == 0:
+            maps = None                                      # (an illegal size: the entry point refuses it below)
+        flops, pos = _msssim_cost(n, h, w, levels, 5)
+        LaunchProfiler.run('msssim_fwd', flops, L.call.s2e_msssim_fwd,
+                           (_dt(a), _p(a), _p(b), n, h, w, levels, wts, _p(out), _p(terms), _p(coef), _p(maps), maps.numel() * 4 if maps is not None else 0,
+                            _p(pyr) if pyr.numel() else None, pyr.numel() * 4, _p(ws), ws.numel() * 8, _stream()),
+                           nbytes=float(2 * a.numel() * a.element_size() + 3 * pyr.numel() * 4 + (12 * pos if maps is not None else 0)))
+        if maps is not None:
+            ctx.save_for_backward(a, b, pyr, maps, coef)
+        ctx.cfg = (x.shape, levels)
+        ctx.mark_non_differentiable(terms)
+        return out, terms
+
+    @staticmethod
+    def backward(ctx, gout, _gterms):
+        if not ctx.saved_tensors:
+            return None, None, None
+        a, b, pyr, maps, coef = ctx.saved_tensors
+        x_shape, levels = ctx.cfg
+        n, h, w = a.shape
+        gs = gout.detach().float().contiguous()
+        dx = torch.empty_like(a)
+        gbuf = torch.empty(pyr.numel() // 2, dtype=torch.float32, device=a.device)     # the coarse levels' gradients, at their own resolution
+        flops, pos = _msssim_cost(n, h, w, levels, 3)
+        LaunchProfiler.run('msssim_bwd', flops, L.call.s2e_msssim_bwd,
+                           (_dt(a), _p(a), _p(b), _p(pyr) if pyr.numel() else None, _p(maps), _p(coef), _p(gs), n, h, w, levels,
+                            _p(gbuf) if gbuf.numel() else None, gbuf.numel() * 4, _p(dx), _stream()),
+                           nbytes=float(3 * a.numel() * a.element_size() + 12 * pos + 3 * pyr.numel() * 4))
+        return dx.view(x_shape), None, None
+
+
+def ms_ssim(x, y, weights=None, return_terms=False):
+    """Per-image multi-scale structural similarity of two single-channel batches in [-1, 1] (ssim's window and constants on a
+    2 x 2-mean pyramid; the contrast-structure term on every level but the last, the full SSIM on the last; the product of the levels'
+    means, each clamped at 1e-3, to the powers `weights`).  weights: one positive number per level, 1 to 5 of them; None = the published
+    five, which need H, W >= 176.  -> fp32 (N,), higher is better, 1 for identical images; differentiable in x only (y is cast to x's
+    dtype).  return_terms: -> (msssim, terms (N, levels) fp32: the levels' means before the clamp, detached)."""
+    out, terms = MsSsimFn.apply(x, y, weights)
+    return (out, terms) if return_terms else out
+
+
+def ms_ssim_terms(x, y, weights=None):
+    """The per-level means m_j of ms_ssim (before the clamp) -> fp32 (N, levels), no gradient."""
+    return MsSsimFn.apply(x.detach(), y.detach(), weights)[1]
+
+
+def ms_ssim_u8(a, b, weights=None, return_terms=False):
+    """ms_ssim on uint8 images that already are 0..255 (u = a / 255).  -> fp32 (N,), no gradient."""
+    a, b = _single_channel(a), _single_channel(b)
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise ValueError('uint8 images expected')
+    _need(a, b)
+    n, h, w = a.shape
+    levels, wts = _msssim_weights(weights)
+    out = torch.empty(n, dtype=torch.float32, device=a.device)
+    terms = torch.empty(n, levels, dtype=torch.float32, device=a.device)
+    ws, pyr, _ = _msssim_buffers(n, h, w, levels, a.device, False)
+    flops, _ = _msssim_cost(n, h, w, levels, 5)
+    LaunchProfiler.run('msssim_fwd', flops, L.call.s2e_msssim_u8,
+                       (_p(a), _p(b), n, h, w, levels, wts, _p(out), _p(terms), _p(pyr) if pyr.numel() else None, pyr.numel() * 4, _p(ws),
+                        ws.numel() * 8, _stream()), nbytes=float(2 * a.numel() + 3 * pyr.numel() * 4))
+    return (out, terms) if return_terms else out
 
 
 _REGION_NORMS = {'l1': L.REGION_L1, 'l2': L.REGION_L2}

@@ -43,6 +43,7 @@ _DEFAULTS = dict(
     diffaug='',                # differentiable augmentation of D's input: parts of 'color,translation,cutout' (seg2eye_amd/diffaug.py); '' = off
     diffaug_seed=0,            # the sampler's CPU generator is seeded diffaug_seed + rank
     lambda_ssim=0.0,           # > 0: lambda_ssim * (1 - mean SSIM(fake, target)) joins the generator's loss (ops.ssim); 0 = off
+    lambda_msssim=0.0,         # > 0: lambda_msssim * (1 - mean MS-SSIM(fake, target)) joins the generator's loss (ops.ms_ssim); 0 = off
     lambda_region=0.0,         # > 0: lambda_region * the class-balanced reconstruction error joins the generator's loss (ops.region_loss); 0 = off
     region_norm='l1',          # 'l1' | 'l2': the per-pixel error of that term
     region_weights='',         # 'w0,w1,...': one non-negative weight per label class (parse_region_weights); '' = all ones
@@ -143,6 +144,9 @@ _CLI = [  # (name, type or 'flag', default, choices)
     # validation also scores SSIM on the 640 x 400 uint8 pair the OpenEDS error sees (ops.ssim_u8): 'ssim/<key>/<mode>' in
     # the statistics (higher is better), `ssim` in the error log; off = validation as it was
     ('val_ssim', 'flag', False, None),
+    # validation also scores five-level MS-SSIM on the same uint8 pair (ops.ms_ssim_u8): 'msssim/<key>/<mode>' in the statistics
+    # (higher is better), `msssim` in the error log; off = validation as it was
+    ('val_msssim', 'flag', False, None),
     # validation also takes the error apart by label class (ops.region_stats_u8 on the same uint8 pair):
     # 'region_mae/<key>/<mode>/<c>' and 'region_rmse/<key>/<mode>/<c>' in the statistics (grey levels), `region` in the error log
     ('val_regions', 'flag', False, None),
@@ -158,6 +162,9 @@ _CLI_TRAIN_BUILD = [
     # structural-similarity term of the generator's loss: lambda_ssim * (1 - mean SSIM(fake, target)); 'SSIM/raw' in the
     # loss log is the mean SSIM itself, so HIGHER is better (1 = identical); 0 = off, nothing is launched
     ('lambda_ssim', _F, 0.0, None),
+    # multi-scale structural-similarity term of the generator's loss: lambda_msssim * (1 - mean MS-SSIM(fake, target)), five
+    # levels with the published weights; 'MSSSIM/raw' in the loss log is the mean MS-SSIM itself, so HIGHER is better; 0 = off, nothing is launched
+    ('lambda_msssim', _F, 0.0, None),
     # class-balanced reconstruction term of the generator's loss: every label class counts by its weight, not by its area;
     # 'region/raw' in the loss log is the term before lambda_region; 0 = off, nothing is launched
     ('lambda_region', _F, 0.0, None), ('region_norm', _S, 'l1', ['l1', 'l2']), ('region_weights', _S, '', None),

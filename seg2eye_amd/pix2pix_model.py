@@ -31,6 +31,13 @@ class Pix2PixModel(nn.Module):
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
+        if opt.isTrain and getattr(opt, 'lambda_msssim', 0):
+            # --lambda_msssim: five levels halve the image four times and the last one must still hold an 11 x 11 window
+            from .options import image_hw
+            h, w = image_hw(opt)
+            if min(h, w) < ops.msssim_min_size():
+                raise ValueError('--lambda_msssim: images of %d x %d are too small for five levels (H, W >= %d: the last level, %d x %d, must '
+                                 'hold an 11 x 11 window)' % (h, w, ops.msssim_min_size(), h >> 4, w >> 4))
         self.cdtype = compute_dtype_of(opt)
         self.netG, self.netD, self.netE = self.initialize_networks(opt)
         self.netE.logvar_used = False        # (`logvar` enters no loss: pix2pix_model.py:271-305; see ConvEncoder.forward)
@@ -218,6 +225,11 @@ class Pix2PixModel(nn.Module):
             s = ops.ssim(fake_image, target_image).mean()
             G_losses['SSIM/weighted'] = (opt.lambda_ssim * (1.0 - s)).view(1)
             self.add_to_loss_log('SSIM/raw', s.detach())          # (the mean SSIM itself: higher is better)
+        if getattr(opt, 'lambda_msssim', 0):
+            # multi-scale structural similarity of the same pair (an extension): three launches, two in the backward
+            s = ops.ms_ssim(fake_image, target_image).mean()
+            G_losses['MSSSIM/weighted'] = (opt.lambda_msssim * (1.0 - s)).view(1)
+            self.add_to_loss_log('MSSSIM/raw', s.detach())        # (the mean MS-SSIM itself: higher is better)
         if getattr(opt, 'lambda_region', 0):
             # class-balanced error of the un-augmented fake against the target, keyed by the step's own label map (an
             # extension): two launches, one in the backward

@@ -1,0 +1,148 @@
+#!/usr/bin/env python3
+"""Cost of the MS-SSIM launches beside the stock-torch composition of the same rule, at the bench shape (N = 8, 256 x 256,
+bf16 by default, five levels with the published weights).
+
+Legs, alternated round by round (same process, same box), each `--launches` back-to-back calls between two HIP events after a warm-up:
+  msssim.fwd          ops.ms_ssim with x requiring a gradient: s2e_msssim_fwd writing every level's maps, 3 launches
+  msssim.fwd_nomaps   ops.ms_ssim on detached inputs (what a validation pass runs): 3 launches, no maps
+  msssim.bwd          s2e_msssim_bwd on the saved pyramid, maps and coefficients: 2 launches
+  msssim_u8.fwd       ops.ms_ssim_u8 on a (N, 640, 400) uint8 pair: 3 launches (the Tester's call under --val_msssim)
+  torch.fwd           the rule as tests/_msssim_ref.py states it, in fp32 on the GPU from the same bf16 images (fp32 NCHW copies, per level
+                      five F.conv2d with the 11 x 11 outer-product window and the elementwise tail, F.avg_pool2d between the levels, the
+                      clamped product), recording for autograd
+  torch.bwd           autograd's backward through that (the graph retained, the leaf's .grad cleared before each call)
+The figure of a leg is the median over `--rounds` rounds of its per-call mean, its spread the min .. max.  kernel_launches: ours by
+construction; the composition's counted by torch.profiler over one call (null where the profiler is not available).  One JSON line;
+`--out` also writes it to a file."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+
+
+def torch_ms_ssim(x, y, weights=WEIGHTS):
+    """The rule in stock torch, fp32: x, y (N,1,H,W) of any float dtype in [-1, 1] -> (N,)."""
+    u, v = (x.float() + 1) / 2, (y.float() + 1) / 2
+    i = torch.arange(11, dtype=torch.float64) - 5
+    g = torch.exp(-i * i / (2 * 1.5 ** 2))
+    k = torch.outer(g / g.sum(), g / g.sum()).float().to(x.device).view(1, 1, 11, 11)
+    terms = []
+    for j in range(len(weights)):
+        mu, mv = F.conv2d(u, k), F.conv2d(v, k)
+        su2, sv2, suv = F.conv2d(u * u, k) - mu * mu, F.conv2d(v * v, k) - mv * mv, F.conv2d(u * v, k) - mu * mv
+        t = (2 * suv + 0.03 ** 2) / (su2 + sv2 + 0.03 ** 2)
+        if j == len(weights) - 1:
+            t = t * (2 * mu * mv + 0.01 ** 2) / (mu * mu + mv * mv + 0.01 ** 2)
+        terms.append(t.mean(dim=(1, 2, 3)))
+        if j < len(weights) - 1:
+            u, v = F.avg_pool2d(u, 2), F.avg_pool2d(v, 2)
+    w = torch.tensor(weights, dtype=torch.float32, device=x.device)
+    return (torch.stack(terms, dim=1).clamp(min=1e-3) ** w).prod(dim=1)
+
+
+def count_kernels(fn):
+    """Device kernels one call of fn launches, by torch.profiler; None when it cannot tell."""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA') and 'memcpy' not in e.name.lower()
+                and 'memset' not in e.name.lower())
+        return n or None
+    except Exception:                                        # noqa: BLE001 -- a count, not a measurement: the timings stand without it
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--batch', type=int, default=8)
+    ap.add_argument('--size', type=int, default=256)
+    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+    ap.add_argument('--rounds', type=int, default=30)
+    ap.add_argument('--launches', type=int, default=20)
+    ap.add_argument('--no_count', action='store_true', help='skip the torch.profiler launch count of the composition')
+    ap.add_argument('--out', default=None, help='also write the JSON here (profiles/msssim.json)')
+    a = ap.parse_args()
+    from seg2eye_amd import _lib as L, ops
+    from seg2eye_amd.ops.core import _dt, _p, _stream
+    dev = 'cuda:0'
+    n, H, W = a.batch, a.size, a.size
+    levels = len(WEIGHTS)
+    dtype = torch.bfloat16 if a.dtype == 'bf16' else torch.float32
+    gen = torch.Generator().manual_seed(0)
+    x = (torch.rand(n, 1, H, W, generator=gen) * 2 - 1).to(dev, dtype)
+    y = (x.float() + 0.1 * torch.randn(n, 1, H, W, generator=gen).to(dev)).clamp(-1, 1).to(dtype)
+    gs = torch.randn(n, generator=gen).to(dev)
+    a8 = torch.randint(0, 256, (n, 1, 640, 400), generator=gen, dtype=torch.uint8).to(dev)
+    b8 = (a8.float() + 12 * torch.randn(n, 1, 640, 400, generator=gen).to(dev)).clamp(0, 255).to(torch.uint8)
+    xg = x.clone().requires_grad_(True)
+    kept = ops.ms_ssim(xg, y)                                # (alive for the run: its node owns what the backward leg reads)
+    _, _, pyr, maps, coef = kept.grad_fn.saved_tensors
+    dx = torch.empty(n, H, W, dtype=dtype, device=dev)
+    gbuf = torch.empty(pyr.numel() // 2, dtype=torch.float32, device=dev)
+    xt = x.clone().requires_grad_(True)
+    st = torch_ms_ssim(xt, y)
+
+    def torch_bwd():
+        xt.grad = None
+        st.backward(gs, retain_graph=True)
+
+    legs = {
+        'msssim.fwd': lambda: ops.ms_ssim(xg, y),
+        'msssim.fwd_nomaps': lambda: ops.ms_ssim(x, y),
+        'msssim.bwd': lambda: L.call.s2e_msssim_bwd(_dt(x), _p(x), _p(y), _p(pyr), _p(maps), _p(coef), _p(gs), n, H, W, levels, _p(gbuf),
+                                                     gbuf.numel() * 4, _p(dx), _stream()),
+        'msssim_u8.fwd': lambda: ops.ms_ssim_u8(a8, b8),
+        'torch.fwd': lambda: torch_ms_ssim(xt, y),
+        'torch.bwd': torch_bwd,
+    }
+    launches = {'msssim.fwd': 3, 'msssim.fwd_nomaps': 3, 'msssim.bwd': 2, 'msssim_u8.fwd': 3, 'torch.fwd': None, 'torch.bwd': None}
+    for f in legs.values():                                  # warm-up: code objects loaded, allocator blocks cached, clocks up
+        for _ in range(5):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(a.rounds):
+        for k, f in legs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.launches):
+                f()
+            e1.record()
+            e1.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / a.launches)
+    err = float((ops.ms_ssim(x, y) - torch_ms_ssim(x, y)).abs().max())
+    out = {'device': torch.cuda.get_device_name(0), 'arch': torch.cuda.get_device_properties(0).gcnArchName, 'batch': n, 'size': H,
+           'dtype': a.dtype, 'levels': levels, 'rounds': a.rounds, 'launches_per_round': a.launches, 'maps_bytes': maps.numel() * 4,
+           'pyramid_bytes': pyr.numel() * 4, 'max_abs_diff_msssim_vs_torch_fp32': err}
+    for k, xs in ms.items():
+        xs = sorted(xs)
+        out[k] = {'us_median': round(1e3 * xs[len(xs) // 2], 2), 'us_min': round(1e3 * xs[0], 2), 'us_max': round(1e3 * xs[-1], 2),
+                  'kernel_launches': launches[k]}
+    med = lambda k: out[k]['us_median']
+    out['fwd_bwd_us'] = {'msssim': round(med('msssim.fwd') + med('msssim.bwd'), 2), 'torch': round(med('torch.fwd') + med('torch.bwd'), 2)}
+
+    def write():
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                f.write(json.dumps(out, indent=1) + '\n')
+    write()                                                  # the timings are on disk before the profiler is touched
+    if not a.no_count:
+        for k in ('torch.fwd', 'torch.bwd'):
+            out[k]['kernel_launches'] = count_kernels(legs[k])
+        write()
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
