@@ -103,6 +103,8 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 }
 // (the kernels' ladders over a run-time count -- conv_duo, conv_patch, conv_stream, conv_wgrad_flat -- stay with their kernels: their
 // shapes differ, and conv_duo's compiles to other code through a shared recursive form)
+// (the multi-job kernels' search for a workgroup's job -- conv_wgrad.hip twice, conv_wgrad_flat.hip, conv_c8.hip -- stays written out in
+// each: through a shared helper, by pointer or by reference to the argument block, all four compile to other code)
 // ds_read_b64_tr_b16, the hardware 4x16 transpose read (lane roles: conv_wgrad.hip)
 __device__ __forceinline__ u32x2_t lds_tr16_b64(const char* p) {
     s16x4_t v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4_t __attribute__((address_space(3)))*)p);
@@ -178,6 +180,13 @@ __global__ void s2e_zero_kernel(uint32_t* __restrict__ p, size_t n_words);
 int s2e_zero_async(void* ptr, size_t bytes, hipStream_t st);
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+// a byte count rounded up to the 256 bytes every section of a workspace starts on
+static inline size_t s2e_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// do the byte ranges [a, a + na) and [b, b + nb) overlap?  (NULL or empty: no range.)  Jobs of one call may write the same dw / dbias
+static inline bool s2e_ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    if (!a || !b || !na || !nb) return false;
+    return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+}
 
 // ---------------------------------------------------------------- dtype dispatch and launch geometry (host)
 // f(T{}) with T the element type of dtype; any other dtype is S2E_ERR_ARG "<name>: bad dtype <dtype>".  A launcher whose dtype must be

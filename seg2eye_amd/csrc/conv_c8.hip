@@ -186,6 +186,8 @@ __global__ __launch_bounds__(256, 2) void conv_c8s2_dgrad_kernel(const C8DParams
 struct C8WJob { const void* x; const void* gy; float* dw; float* dbias; float* part; int N, Hi, Wi, Ho, Wo, G, pitch, rows; unsigned x_bytes, gy_bytes; };
 constexpr int C8W_TILE = 64 * 128 + 64;             // a workgroup's partial tile: dW [64][128], then the bias sums
 constexpr int C8W_MAX_JOBS = 4;
+constexpr int C8W_CHUNK_TILES = 512;                // partial tiles of a chunk's section of the workspace = the most workgroups a chunk launches with tiles
+constexpr size_t C8W_SECTION = (size_t)C8W_CHUNK_TILES * C8W_TILE * sizeof(float);
 struct C8WMulti { int n; int first[C8W_MAX_JOBS + 1]; C8WJob j[C8W_MAX_JOBS]; };
 
 constexpr int C8W_XB = 4 * C8_MAXPITCH * 16 + 1024, C8W_GB = 16 * C8_MAXG * 128, C8W_STAGE = C8W_XB + C8W_GB;     // 19,968 + 18,432
@@ -365,21 +367,25 @@ bool s2e_c8s2_wgrad_ok(int dtype, const s2e_conv_desc* d) {
 }
 
 size_t s2e_c8s2_wgrad_workspace_bytes(int n_jobs) {
-    return (size_t)ceil_div(n_jobs, C8W_MAX_JOBS) * 512 * C8W_TILE * sizeof(float);
+    return (size_t)ceil_div(n_jobs, C8W_MAX_JOBS) * C8W_SECTION;
 }
 
 int s2e_c8s2_wgrad_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n_all, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    static const double total_wg = s2e_env_double("S2E_C8W_WGS", 512.0);
+    static const double total_wg = s2e_env_double("S2E_C8W_WGS", C8W_CHUNK_TILES);
     char* ws = (char*)workspace;
     for (int base = 0; base < n_all; base += C8W_MAX_JOBS) {
         const int n = n_all - base < C8W_MAX_JOBS ? n_all - base : C8W_MAX_JOBS;
         C8WMulti b{};
         b.n = n;
-        const bool tiles = ws && workspace_bytes >= (size_t)(base / C8W_MAX_JOBS + 1) * 512 * C8W_TILE * sizeof(float) && total_wg <= 512.0;
+        // tiles for this chunk: when the bytes passed cover its section and every section before it.  With S2E_C8W_WGS above a section's
+        // tiles a chunk would launch more workgroups than its section has tiles, so it adds with atomics; the size query knows the job
+        // count alone and goes on reporting the sections (too much workspace is harmless, a size that moves with an experiment switch is not)
+        const size_t section = (size_t)(base / C8W_MAX_JOBS) * C8W_SECTION;
+        const bool tiles = ws && workspace_bytes >= section + C8W_SECTION && total_wg <= C8W_CHUNK_TILES;
         double work = 0.0;
         for (int i = 0; i < n; ++i) work += (double)jobs[idx[base + i]].d.N * jobs[idx[base + i]].d.Ho * jobs[idx[base + i]].d.Wo;
         // a job's share of the chunk's workgroups goes by its pixels, at least 1, at most its rows.  With partial tiles the shares must
-        // not sum past the chunk's 512 tiles of workspace (nor past S2E_C8W_WGS below that): the floor of 1 can lift a chunk of one big
+        // not sum past the chunk's C8W_CHUNK_TILES tiles of workspace (nor past S2E_C8W_WGS below that): the floor of 1 can lift a chunk of one big
         // and three tiny jobs to 511 + 1 + 1 + 1 -- the excess comes off the largest share
         int shares[C8W_MAX_JOBS], sum = 0;
         for (int i = 0; i < n; ++i) {
@@ -390,7 +396,7 @@ int s2e_c8s2_wgrad_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n
             sum += shares[i];
         }
         if (tiles) {
-            const int budget = (int)total_wg > n ? (int)total_wg : n;     // (<= 512: total_wg <= 512 and n <= C8W_MAX_JOBS)
+            const int budget = (int)total_wg > n ? (int)total_wg : n;     // (<= C8W_CHUNK_TILES: total_wg is, and n <= C8W_MAX_JOBS)
             while (sum > budget) {
                 int big = 0;
                 for (int i = 1; i < n; ++i) if (shares[i] > shares[big]) big = i;
@@ -410,10 +416,9 @@ int s2e_c8s2_wgrad_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n
             p.G = ceil_div(d->Wo, 16); p.pitch = 32 * p.G + 8; p.rows = d->N * d->Ho;
             p.x_bytes = (unsigned)((long)d->N * d->Hi * d->Wi * 16);
             p.gy_bytes = (unsigned)((long)d->N * d->Ho * d->Wo * 128);
-            const int share = shares[i];
-            if (tiles) p.part = (float*)(ws + ((size_t)(base / C8W_MAX_JOBS) * 512 + blocks) * C8W_TILE * sizeof(float));
+            if (tiles) p.part = (float*)(ws + section) + (size_t)blocks * C8W_TILE;
             b.first[i] = blocks;
-            blocks += share;
+            blocks += shares[i];
         }
         b.first[n] = blocks;
         conv_c8s2_wgrad_kernel<<<blocks, 256, 0, st>>>(b);

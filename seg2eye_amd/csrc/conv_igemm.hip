@@ -680,11 +680,9 @@ extern "C" int s2e_conv2d(int dtype, const void* x, const void* w, const float* 
     const int kpad = s2e_conv_k_pad(dtype, d->KH * d->KW * d->Cin);
     switch (r.kernel) {
     case ROUTE_SMALL: {                              // 1-channel heads: dedicated streaming kernels
-        SmallConvParams sp{};
+        SmallConvParams sp = s2e_small_conv_params(d);
         sp.x = x; sp.w = w; sp.bias = bias; sp.res = res; sp.aux = aux; sp.y = y;
-        sp.N = d->N; sp.Hi = d->Hi; sp.Wi = d->Wi; sp.Cin = d->Cin; sp.Ho = d->Ho; sp.Wo = d->Wo; sp.Cout = d->Cout;
-        sp.KH = d->KH; sp.KW = d->KW; sp.stride = d->stride; sp.pad = d->pad;
-        sp.in_act = d->in_act; sp.out_act = d->out_act; sp.aux_mode = d->aux_mode;
+        sp.out_act = d->out_act; sp.aux_mode = d->aux_mode;
         sp.Kpad = kpad;
         return s2e_small_conv_launch(dtype, r.small_kind, sp, st);
     }

@@ -366,6 +366,18 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_multi_kernel(const WgMu
                       r.atomic[k] != 0);
 }
 
+// the shape of d and the dW tiles that follow from it; the pointers and the pixel splits (generic_wgrad_plan) are the caller's
+static WgradParams wgrad_params(const s2e_conv_desc* d) {
+    WgradParams p{};
+    p.N = d->N; p.Hi = d->Hi; p.Wi = d->Wi; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
+    p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.in_act = d->in_act;
+    p.Ktot = d->KH * d->KW * d->Cin;
+    p.M = d->N * d->Ho * d->Wo;
+    p.tiles_k = ceil_div(p.Ktot, 128);
+    p.tiles_co = ceil_div(d->Cout, 128);
+    return p;
+}
+
 // Pixel splits of the generic kernel.  Two costs pull against each other (measured per shape, profiles/r01):
 //   * long pixel loops want MANY workgroups: c128->256 @256^2 runs 476 / 497 / 558 TFLOP/s at 512 / 1024 / 2048;
 //   * every split ends with a 64-KB partial tile (or, without a workspace, one fp32 atomic per dW element on addresses shared by
@@ -374,11 +386,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_reduce_multi_kernel(const WgMu
 // So: aim for S2E_WGRAD_WG (2048) workgroups, keep >= 32 pixel chunks per split (64 when dW is large), never more
 // than 512 splits -- unless that leaves the chip under-filled (< 512 workgroups), then allow 16-chunk splits
 // (8-chunk splits for a 1-2 tile dW).
-static void generic_wgrad_plan(const s2e_conv_desc* d, WgradParams* p, int* splits_out, int target_override = 0) {
-    p->Ktot = d->KH * d->KW * d->Cin;
-    p->M = d->N * d->Ho * d->Wo;
-    p->tiles_k = ceil_div(p->Ktot, 128);
-    p->tiles_co = ceil_div(d->Cout, 128);
+static void generic_wgrad_plan(WgradParams* p, int* splits_out, int target_override = 0) {
     const int tiles = p->tiles_k * p->tiles_co;
     // (c128->256 @256^2: 476 / 497 / 558 TFLOP/s at 512 / 1024 / 2048 workgroups; a job of a multi-job launch gets its share of the
     //  launch's workgroups instead: it does not have to fill the chip alone)
@@ -404,21 +412,22 @@ static void generic_wgrad_plan(const s2e_conv_desc* d, WgradParams* p, int* spli
 // stay.  One split needs neither (a single workgroup owns the tile: its atomics ARE deterministic).
 // S2E_WGRAD_PARTIAL=<n>: threshold (default 16); 2 = every split launch (bit-reproducible weight gradients of this kernel,
 // ~ +0.4 ms per step); 0 = never.
-static int wgrad_partial_min_splits() {
-    static const int n = s2e_env_int("S2E_WGRAD_PARTIAL", 16);
-    return s2e_deterministic() ? 2 : n;
-}
 // Partial tiles + fixed-order reduce for this launch?  S2E_DETERMINISTIC: always -- even an unsplit launch adds its k-tile
 // workgroups' bias sums with one float atomic each (9 addends for K = 1152: order-dependent in the last bit).
 static bool wgrad_use_partial(int splits) {
-    if (s2e_deterministic()) return true;
-    const int n = wgrad_partial_min_splits();
-    return n > 0 && splits >= 2 && splits >= n;
+    static const int n = s2e_env_int("S2E_WGRAD_PARTIAL", 16);
+    return s2e_deterministic() || (n > 0 && splits >= 2 && splits >= n);
 }
 
 // the generic kernel's workspace: one partial tile (+ 128 bias sums) per workgroup
 static size_t generic_partial_bytes(const WgradParams& p, int splits) {
     return (size_t)p.tiles_k * p.tiles_co * splits * (128 * 128 + 128) * sizeof(float);
+}
+// workgroups of the reduction of those tiles: they stride over the 64-element items, at most 2048 of them (wgrad_reduce_body), and the
+// first 2 * tiles_co also fold the bias sums
+static int wgrad_reduce_grid(const WgradParams& p) {
+    const int items = p.tiles_k * p.tiles_co * 256, g = items < 2048 ? items : 2048;
+    return g < 2 * p.tiles_co ? 2 * p.tiles_co : g;
 }
 // the kernels index pixels with 32-bit integers
 static bool wgrad_index_range_ok(const s2e_conv_desc* d) {
@@ -441,7 +450,8 @@ static WgradRoute wgrad_route(int dtype, const s2e_conv_desc* d) {
     } else if ((r.kind = s2e_wgrad_patch_plan(dtype, d))) {
         r.kernel = WG_PATCH; r.workspace_bytes = s2e_wgrad_patch_workspace_bytes(r.kind, d);
     } else {
-        generic_wgrad_plan(d, &r.tiling, &r.splits);
+        r.tiling = wgrad_params(d);
+        generic_wgrad_plan(&r.tiling, &r.splits);
         r.partial = wgrad_use_partial(r.splits);
         if ((r.kind = s2e_wgrad_c8_plan(dtype, d))) { r.kernel = WG_C8; r.workspace_bytes = s2e_wgrad_c8_workspace_bytes(r.kind, d); }
         else { r.kernel = WG_GENERIC; r.workspace_bytes = r.partial ? generic_partial_bytes(r.tiling, r.splits) : 0; }
@@ -484,10 +494,8 @@ extern "C" int s2e_conv2d_wgrad(int dtype, const void* x, const void* gy, float*
     const WgradRoute r = wgrad_route(dtype, d);
     hipStream_t st = (hipStream_t)stream;
     if (r.kernel == WG_SMALL) {                                     // 1-channel heads: dedicated streaming kernels
-        SmallConvParams sp{};
+        SmallConvParams sp = s2e_small_conv_params(d);
         sp.x = x; sp.gy = gy; sp.dw = dw;
-        sp.N = d->N; sp.Hi = d->Hi; sp.Wi = d->Wi; sp.Cin = d->Cin; sp.Ho = d->Ho; sp.Wo = d->Wo; sp.Cout = d->Cout;
-        sp.KH = d->KH; sp.KW = d->KW; sp.stride = d->stride; sp.pad = d->pad; sp.in_act = d->in_act;
         if (int rc = s2e_small_wgrad_launch(dtype, r.kind, d, sp, workspace, workspace_bytes, st)) return rc;
         if (dbias) return s2e_colsum(dtype, gy, (long)d->N * d->Ho * d->Wo, d->Cout, dbias, stream);
         return S2E_OK;
@@ -499,8 +507,6 @@ extern "C" int s2e_conv2d_wgrad(int dtype, const void* x, const void* gy, float*
         return s2e_wgrad_c8_launch(r.kind, x, gy, dw, dbias, d, workspace, st);
     WgradParams p = r.tiling;
     p.x = x; p.gy = gy; p.dw = dw; p.dbias = dbias;
-    p.N = d->N; p.Hi = d->Hi; p.Wi = d->Wi; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
-    p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.in_act = d->in_act;
     const int splits = r.splits, tiles = p.tiles_k * p.tiles_co, g = tiles * splits;
     // With a workspace the workgroups store their partial tiles and a second kernel adds them up in a fixed order:
     // deterministic, and cheaper than the atomics once a launch has more than a few splits (64 KB written + read per
@@ -509,87 +515,92 @@ extern "C" int s2e_conv2d_wgrad(int dtype, const void* x, const void* gy, float*
         p.partial = (float*)workspace;
         p.bpartial = p.partial + (size_t)g * (128 * 128);
     }
-    if (dtype == S2E_BF16) {
-        if (d->Cin % 8 == 0 && d->Cout % 8 == 0) conv_wgrad_kernel<bf16_t, true, 32><<<g, 256, 0, st>>>(p);    // (32 pixels per chunk: 64 measured no faster)
-        else conv_wgrad_kernel<bf16_t, false, 32><<<g, 256, 0, st>>>(p);
-    } else if (dtype == S2E_F32) {
-        if (d->Cin % 4 == 0 && d->Cout % 4 == 0) conv_wgrad_kernel<float, true, 32><<<g, 256, 0, st>>>(p);
-        else conv_wgrad_kernel<float, false, 32><<<g, 256, 0, st>>>(p);
-    } else S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d_wgrad: bad dtype %d", dtype);
+    if (const int rc = s2e_with_dtype(dtype, "s2e_conv2d_wgrad", [&](auto t) { using T = decltype(t);
+        if (d->Cin % Vec<T>::N == 0 && d->Cout % Vec<T>::N == 0) conv_wgrad_kernel<T, true, 32><<<g, 256, 0, st>>>(p);     // (32 pixels per chunk: 64 measured no faster)
+        else conv_wgrad_kernel<T, false, 32><<<g, 256, 0, st>>>(p);
+        return (int)S2E_OK; })) return rc;
     S2E_CHECK_LAUNCH("conv_wgrad_kernel");
     if (p.partial) {
-        const int items = tiles * 256;
-        int rgrid = items < 2048 ? items : 2048;
-        if (rgrid < 2 * p.tiles_co) rgrid = 2 * p.tiles_co;
-        conv_wgrad_reduce_kernel<<<rgrid, 256, 0, st>>>(p, splits, items);
+        conv_wgrad_reduce_kernel<<<wgrad_reduce_grid(p), 256, 0, st>>>(p, splits, tiles * 256);
         S2E_CHECK_LAUNCH("conv_wgrad_reduce_kernel");
     }
     return S2E_OK;
 }
 
 // ---- every generic weight gradient of a backward pass in one launch (+ one for the partial-tile reductions): conv_wgrad_multi_kernel
-// do the fp32 ranges [a, a + na) and [b, b + nb) share an element?  (NULL: no range)
-static bool ranges_overlap(const float* a, size_t na, const float* b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    return (uintptr_t)a < (uintptr_t)(b + nb) && (uintptr_t)b < (uintptr_t)(a + na);
-}
-static bool wgrad_multi_ok(int dtype, const s2e_conv_desc* d) {
-    if (!d || dtype != S2E_BF16 || d->transposed || (d->stride != 1 && d->stride != 2)) return false;
-    if (d->Cin % 8 != 0 || d->Cout % 8 != 0) return false;
+extern "C" int s2e_conv2d_wgrad_multi_supported(int dtype, const s2e_conv_desc* d) {
+    if (!d || dtype != S2E_BF16 || d->transposed || (d->stride != 1 && d->stride != 2)) return 0;
+    if (d->Cin % 8 != 0 || d->Cout % 8 != 0) return 0;
     return wgrad_index_range_ok(d) && wgrad_route(dtype, d).kernel == WG_GENERIC;
 }
-extern "C" int s2e_conv2d_wgrad_multi_supported(int dtype, const s2e_conv_desc* d) { return wgrad_multi_ok(dtype, d) ? 1 : 0; }
 
-// The plan of jobs [base, base + n) of a multi-job launch: a job's share of the launch's workgroups (S2E_WGRAD_MULTI_WGS in all, default
-// 6144: 12 per workgroup slot of the chip) goes by its MFMA work -- planned alone (2048 workgroups each) two dozen jobs made 30-40 k
-// workgroups and ~1 GB of partial tiles per step.  Fills ps[i] (shape, tiling, m_per_split) and splits[i].
-static void wgrad_multi_plan(const s2e_wgrad_multi_job* jobs, const int* idx, int n, WgradParams* ps, int* splits) {
+// which kernel a job of s2e_conv2d_wgrad_multi runs in: 0 = the generic tile kernel, 1..5 = conv_wgrad_flat.hip's kinds (1x1, 3x3 stride 1,
+// 3x3 stride 2, 4x4 stride 1, 4x4 stride 2), 6 = conv_c8.hip's 8-channel 4x4 stride-2 kernel, -1 = not a job of that call
+extern "C" int s2e_conv2d_wgrad_multi_kind(int dtype, const s2e_conv_desc* d) {
+    if (!s2e_conv2d_wgrad_multi_supported(dtype, d)) return -1;
+    if (const int k = s2e_wgrad_flat_kind(dtype, d)) return k;
+    return s2e_c8s2_wgrad_ok(dtype, d) ? 6 : 0;
+}
+
+// The plan of one s2e_conv2d_wgrad_multi call: what the call decides before it knows a pointer.  The size query adds up the
+// sections it asks of the workspace -- c8's, then need[] of every generic launch -- and the call hands out the same sections in that order.
+enum { WGF_FLAT, WGF_C8, WGF_GENERIC };      // conv_wgrad_flat.hip, conv_c8.hip, the generic kernel
+struct WgCallPlan {
+    int bad;                                 // the first job that is none of this call's (s2e_conv2d_wgrad_multi_kind < 0: the plan ends there), else -1
+    int n[3], idx[3][4096];                  // the jobs of each family, in the call's order
+    size_t c8_bytes;                         // the c8 launches' tile sections: ahead of the generic jobs', all or nothing
+};
+static void wgrad_call_plan(int dtype, const s2e_wgrad_multi_job* jobs, int n_jobs, WgCallPlan* c) {
+    c->bad = -1; c->n[WGF_FLAT] = c->n[WGF_C8] = c->n[WGF_GENERIC] = 0; c->c8_bytes = 0;
+    for (int i = 0; i < n_jobs; ++i) {
+        const int kind = s2e_conv2d_wgrad_multi_kind(dtype, &jobs[i].d);
+        if (kind < 0) { c->bad = i; return; }
+        const int f = kind == 0 ? WGF_GENERIC : kind == 6 ? WGF_C8 : WGF_FLAT;
+        c->idx[f][c->n[f]++] = i;
+    }
+    c->c8_bytes = s2e_align256(s2e_c8s2_wgrad_workspace_bytes(c->n[WGF_C8]));
+}
+
+// Generic launch `chunk` of the call: its next WGM_MAX_JOBS generic jobs (returns how many: 0 = the call has no such launch).  A job's
+// share of the launch's workgroups (S2E_WGRAD_MULTI_WGS in all, default 6144: 12 per workgroup slot of the chip) goes by its MFMA work --
+// planned alone (2048 workgroups each) two dozen jobs made 30-40 k workgroups and ~1 GB of partial tiles per step.
+struct WgChunkPlan {
+    const int* idx;                          // the launch's jobs
+    WgMulti b;                               // their shapes, tilings, splits and workgroup ranges; the pointers are the launch's to fill
+    size_t need[WGM_MAX_JOBS];               // a job's partial tiles in bytes, 256-aligned; 0: atomics, whatever workspace there is
+};
+static int wgrad_chunk_plan(const s2e_wgrad_multi_job* jobs, const WgCallPlan& c, int chunk, WgChunkPlan* k) {
     static const int total_wg = s2e_env_int("S2E_WGRAD_MULTI_WGS", 6144);
+    const int left = c.n[WGF_GENERIC] - chunk * WGM_MAX_JOBS, n = left < WGM_MAX_JOBS ? left : WGM_MAX_JOBS;
+    if (n <= 0) return 0;
+    *k = WgChunkPlan{c.idx[WGF_GENERIC] + chunk * WGM_MAX_JOBS};
+    WgMulti& b = k->b;
+    b.n = n;
     double work[WGM_MAX_JOBS], work_sum = 0.0;
     for (int i = 0; i < n; ++i) {
-        const s2e_conv_desc* d = &jobs[idx[i]].d;
-        work[i] = (double)ceil_div(d->Cout, 128) * ceil_div(d->KH * d->KW * d->Cin, 128) * ((double)d->N * d->Ho * d->Wo);
+        b.j[i] = wgrad_params(&jobs[k->idx[i]].d);
+        work[i] = (double)b.j[i].tiles_co * b.j[i].tiles_k * (double)b.j[i].M;
         work_sum += work[i];
     }
     for (int i = 0; i < n; ++i) {
-        const s2e_conv_desc* d = &jobs[idx[i]].d;
-        WgradParams& p = ps[i];
-        p.N = d->N; p.Hi = d->Hi; p.Wi = d->Wi; p.Cin = d->Cin; p.Ho = d->Ho; p.Wo = d->Wo; p.Cout = d->Cout;
-        p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.in_act = d->in_act;
-        generic_wgrad_plan(d, &p, &splits[i], total_wg > 0 ? (int)(total_wg * work[i] / work_sum) + 1 : 0);
+        WgradParams& p = b.j[i];
+        generic_wgrad_plan(&p, &b.splits[i], total_wg > 0 ? (int)(total_wg * work[i] / work_sum) + 1 : 0);
+        b.nblk[i] = p.tiles_k * p.tiles_co * b.splits[i];
+        b.first[i + 1] = b.first[i] + ((b.nblk[i] + 7) & ~7);     // (a job's first workgroup on a multiple of 8: xcd_remap's placement)
+        if (wgrad_use_partial(b.splits[i])) k->need[i] = s2e_align256(generic_partial_bytes(p, b.splits[i]));
     }
-}
-
-// the jobs of a multi-job call that stay in the generic kernel (the others: conv_wgrad_flat.hip, conv_c8.hip); returns their count
-static int wgrad_multi_generic_jobs(int dtype, const s2e_wgrad_multi_job* jobs, int n_jobs, int* idx, int* flat_idx, int* n_flat, int* c8_idx, int* n_c8) {
-    int n = 0, nf = 0, nc = 0;
-    for (int i = 0; i < n_jobs; ++i) {
-        if (s2e_wgrad_flat_kind(dtype, &jobs[i].d)) { if (flat_idx) flat_idx[nf] = i; ++nf; }
-        else if (s2e_c8s2_wgrad_ok(dtype, &jobs[i].d)) { if (c8_idx) c8_idx[nc] = i; ++nc; }
-        else idx[n++] = i;
-    }
-    if (n_flat) *n_flat = nf;
-    if (n_c8) *n_c8 = nc;
     return n;
 }
 
 extern "C" size_t s2e_conv2d_wgrad_multi_workspace_bytes(int dtype, const s2e_wgrad_multi_job* jobs, int n_jobs) {
-    size_t total = 0;
     if (!jobs || n_jobs <= 0 || n_jobs > 4096) return 0;
-    for (int i = 0; i < n_jobs; ++i) if (!wgrad_multi_ok(dtype, &jobs[i].d)) return 0;
-    int idx_all[4096];
-    int n_c8w = 0;
-    const int n_gen = wgrad_multi_generic_jobs(dtype, jobs, n_jobs, idx_all, nullptr, nullptr, nullptr, &n_c8w);
-    if (n_c8w) total += (s2e_c8s2_wgrad_workspace_bytes(n_c8w) + 255) & ~(size_t)255;
-    for (int base = 0; base < n_gen; base += WGM_MAX_JOBS) {
-        const int n = n_gen - base < WGM_MAX_JOBS ? n_gen - base : WGM_MAX_JOBS;
-        WgradParams ps[WGM_MAX_JOBS];
-        int splits[WGM_MAX_JOBS];
-        wgrad_multi_plan(jobs, idx_all + base, n, ps, splits);
-        for (int i = 0; i < n; ++i)
-            if (wgrad_use_partial(splits[i]))
-                total += (generic_partial_bytes(ps[i], splits[i]) + 255) & ~(size_t)255;
-    }
+    WgCallPlan c;
+    wgrad_call_plan(dtype, jobs, n_jobs, &c);
+    if (c.bad >= 0) return 0;
+    size_t total = c.c8_bytes;
+    WgChunkPlan k;
+    for (int chunk = 0; wgrad_chunk_plan(jobs, c, chunk, &k); ++chunk)
+        for (int i = 0; i < k.b.n; ++i) total += k.need[i];
     return total;
 }
 
@@ -597,79 +608,60 @@ extern "C" int s2e_conv2d_wgrad_multi(int dtype, const s2e_wgrad_multi_job* jobs
                                       void* stream) {
     if (!jobs || n_jobs <= 0 || n_jobs > 4096) S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d_wgrad_multi: no jobs (or more than 4096)");
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    size_t ws_left = workspace ? workspace_bytes : 0;
+    WgCallPlan c;
+    wgrad_call_plan(dtype, jobs, n_jobs, &c);
     for (int i = 0; i < n_jobs; ++i) {
-        if (!wgrad_multi_ok(dtype, &jobs[i].d)) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d_wgrad_multi: job %d is not a generic bf16 shape (s2e_conv2d_wgrad_multi_supported)", i);
+        if (i == c.bad) S2E_FAIL(S2E_ERR_UNSUPPORTED, "s2e_conv2d_wgrad_multi: job %d is not a generic bf16 shape (s2e_conv2d_wgrad_multi_supported)", i);
         if (!jobs[i].x || !jobs[i].gy || !jobs[i].dw) S2E_FAIL(S2E_ERR_ARG, "s2e_conv2d_wgrad_multi: null pointer in job %d", i);
     }
-    int idx_all[4096], flat_idx[4096], c8_idx[4096], n_flat = 0, n_c8 = 0;
-    const int n_gen = wgrad_multi_generic_jobs(dtype, jobs, n_jobs, idx_all, flat_idx, &n_flat, c8_idx, &n_c8);
+    // the workspace goes out section by section in the plan's order: a section that no longer fits gets none (its owner adds with atomics)
+    // and the ones behind it are still tried
+    char* ws = (char*)workspace;
+    size_t ws_left = workspace ? workspace_bytes : 0;
+    auto take = [&](size_t bytes) -> void* {
+        if (!ws || ws_left < bytes) return nullptr;
+        ws += bytes; ws_left -= bytes;
+        return ws - bytes;
+    };
     // the stride-2 / 4x4 / 1x1 layers: the flat-slab patch-resident kernel (atomics into dW; no workspace)
-    if (n_flat) if (int rc = s2e_wgrad_flat_launch(jobs, flat_idx, n_flat, st)) return rc;
+    if (c.n[WGF_FLAT]) if (int rc = s2e_wgrad_flat_launch(jobs, c.idx[WGF_FLAT], c.n[WGF_FLAT], st)) return rc;
     // the PatchGAN's 8-channel first layers (conv_c8.hip)
-    if (n_c8) {
-        const size_t need = (s2e_c8s2_wgrad_workspace_bytes(n_c8) + 255) & ~(size_t)255;
-        const bool have = ws && ws_left >= need;
-        if (int rc = s2e_c8s2_wgrad_launch(jobs, c8_idx, n_c8, have ? ws : nullptr, have ? need : 0, st)) return rc;
-        if (have) { ws += need; ws_left -= need; }
+    if (c.n[WGF_C8]) {
+        void* tiles = take(c.c8_bytes);
+        if (int rc = s2e_c8s2_wgrad_launch(jobs, c.idx[WGF_C8], c.n[WGF_C8], tiles, tiles ? c.c8_bytes : 0, st)) return rc;
     }
-    for (int base = 0; base < n_gen; base += WGM_MAX_JOBS) {
-        const int n = n_gen - base < WGM_MAX_JOBS ? n_gen - base : WGM_MAX_JOBS;
-        const int* idx = idx_all + base;
-        WgMulti b{};
+    WgChunkPlan k;
+    for (int chunk = 0; wgrad_chunk_plan(jobs, c, chunk, &k); ++chunk) {
+        WgMulti& b = k.b;
         WgMultiRed r{};
-        b.n = n;
-        int blocks = 0, rblocks = 0;
-        int splits_of[WGM_MAX_JOBS];
-        wgrad_multi_plan(jobs, idx, n, b.j, splits_of);
-        for (int i = 0; i < n; ++i) {
-            const s2e_wgrad_multi_job& J = jobs[idx[i]];
+        for (int i = 0; i < b.n; ++i) {
+            const s2e_wgrad_multi_job& J = jobs[k.idx[i]];
             WgradParams& p = b.j[i];
             p.x = J.x; p.gy = J.gy; p.dw = J.dw; p.dbias = J.dbias;
-            const int splits = splits_of[i];
-            const int g = p.tiles_k * p.tiles_co * splits;
-            const size_t need = generic_partial_bytes(p, splits);
-            if (wgrad_use_partial(splits) && ws && ws_left >= need) {
-                p.partial = (float*)ws;
-                p.bpartial = p.partial + (size_t)g * (128 * 128);
-                const size_t adv = (need + 255) & ~(size_t)255;
-                ws += adv; ws_left = ws_left > adv ? ws_left - adv : 0;
-                const int items = p.tiles_k * p.tiles_co * 256;
-                int rgrid = items < 2048 ? items : 2048;
-                if (rgrid < 2 * p.tiles_co) rgrid = 2 * p.tiles_co;
-                r.first[r.n] = rblocks; r.job[r.n] = i; ++r.n;
-                rblocks += rgrid;
+            if (k.need[i] && (p.partial = (float*)take(k.need[i]))) {
+                p.bpartial = p.partial + (size_t)b.nblk[i] * (128 * 128);
+                r.job[r.n] = i;
+                r.first[r.n + 1] = r.first[r.n] + wgrad_reduce_grid(p);
+                ++r.n;
             }
-            b.first[i] = blocks; b.nblk[i] = g; b.splits[i] = splits;
-            blocks += (g + 7) & ~7;                       // (a job's first workgroup on a multiple of 8: xcd_remap's placement)
         }
-        b.first[n] = blocks;
-        r.first[r.n] = rblocks;
         // jobs may share dw / dbias (the sums accumulate): the multi kernel's atomics are safe, but the reductions run side by side with
         // plain read-modify-writes -- a reduction whose dw or dbias range overlaps another's of this launch adds with atomics instead
         for (int a = 0; a < r.n; ++a)
-            for (int c = 0; c < r.n; ++c) {
+            for (int o = 0; o < r.n; ++o) {
                 const WgradParams& pa = b.j[r.job[a]];
-                const WgradParams& pc = b.j[r.job[c]];
-                if (c != a && (ranges_overlap(pa.dw, (size_t)pa.Cout * pa.Ktot, pc.dw, (size_t)pc.Cout * pc.Ktot) ||
-                               ranges_overlap(pa.dbias, (size_t)pa.Cout, pc.dbias, (size_t)pc.Cout)))
+                const WgradParams& po = b.j[r.job[o]];
+                if (o != a && (s2e_ranges_overlap(pa.dw, (size_t)pa.Cout * pa.Ktot * sizeof(float), po.dw, (size_t)po.Cout * po.Ktot * sizeof(float)) ||
+                               s2e_ranges_overlap(pa.dbias, pa.Cout * sizeof(float), po.dbias, po.Cout * sizeof(float))))
                     r.atomic[a] = 1;
             }
-        conv_wgrad_multi_kernel<<<blocks, 256, 0, st>>>(b);
+        conv_wgrad_multi_kernel<<<b.first[b.n], 256, 0, st>>>(b);
         S2E_CHECK_LAUNCH("conv_wgrad_multi_kernel");
         if (r.n) {
-            conv_wgrad_reduce_multi_kernel<<<rblocks, 256, 0, st>>>(b, r);
+            conv_wgrad_reduce_multi_kernel<<<r.first[r.n], 256, 0, st>>>(b, r);
             S2E_CHECK_LAUNCH("conv_wgrad_reduce_multi_kernel");
         }
     }
     return S2E_OK;
 }
 
-// which kernel a job of s2e_conv2d_wgrad_multi runs in: 0 = the generic tile kernel, 1..5 = conv_wgrad_flat.hip's kinds (1x1, 3x3 stride 1,
-// 3x3 stride 2, 4x4 stride 1, 4x4 stride 2), 6 = conv_c8.hip's 8-channel 4x4 stride-2 kernel, -1 = not a job of that call
-extern "C" int s2e_conv2d_wgrad_multi_kind(int dtype, const s2e_conv_desc* d) {
-    if (!wgrad_multi_ok(dtype, d)) return -1;
-    if (const int k = s2e_wgrad_flat_kind(dtype, d)) return k;
-    return s2e_c8s2_wgrad_ok(dtype, d) ? 6 : 0;
-}

@@ -554,7 +554,7 @@ extern "C" int s2e_wgrad_batch_supported(int dtype, int N, int H, int W, int Cin
 }
 
 extern "C" size_t s2e_wgrad_batch_workspace_bytes(void) {
-    return (size_t)WB_SLOTS * wb_workgroups() * WB_TILE * sizeof(float) + ((sizeof(WbPlan) + 255) & ~(size_t)255);      // fragments + the plan
+    return (size_t)WB_SLOTS * wb_workgroups() * WB_TILE * sizeof(float) + s2e_align256(sizeof(WbPlan));      // fragments + the plan
 }
 
 extern "C" int s2e_wgrad_batch(int dtype, const s2e_wgrad_batch_job* jobs, int n_jobs, void* workspace, size_t workspace_bytes, void* stream) {

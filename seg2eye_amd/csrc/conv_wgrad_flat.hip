@@ -409,14 +409,10 @@ int s2e_wgrad_flat_launch(const s2e_wgrad_multi_job* jobs, const int* idx, int n
             p.flags = noepi;
             // (another job whose dW range overlaps this one's: compared as address ranges, not only as pointers)
             bool shared = false;
-            const char* lo = (const char*)p.dw;
-            const char* hi = lo + (size_t)p.Cout * p.Ktot * sizeof(float);
             for (int k = 0; k < n_all && !shared; ++k) {
-                if (k == base + i) continue;
                 const s2e_conv_desc& dk = jobs[idx[k]].d;
-                const char* klo = (const char*)jobs[idx[k]].dw;
-                const char* khi = klo + (size_t)dk.Cout * dk.KH * dk.KW * dk.Cin * sizeof(float);
-                shared = klo < hi && lo < khi;
+                shared = k != base + i && s2e_ranges_overlap(p.dw, (size_t)p.Cout * p.Ktot * sizeof(float),
+                                                             jobs[idx[k]].dw, (size_t)dk.Cout * dk.KH * dk.KW * dk.Cin * sizeof(float));
             }
             if (p.splits == 1 && !shared) p.flags |= 8;
             b.first[i] = blocks;

@@ -534,6 +534,25 @@ __global__ __launch_bounds__(256) void wgrad_patch_reduce_kernel(const float* __
 
 }  // namespace
 
+// The slab of 128 pixels -- 64 x 2, 32 x 4 or 16 x 8 -- that tiles an H x W map with the least overhang: its width, or 0 when even that
+// one's slabs are less than 80 % inside the map.  (Ties go to the wider slab.)
+static int wgrad_best_slab(int H, int W) {
+    int best = 0; double best_fill = 0.0;
+    for (int tw = 64; tw >= 16; tw >>= 1) {
+        const int th = 128 / tw;
+        const long covered = (long)ceil_div(H, th) * th * ceil_div(W, tw) * tw;
+        const double fill = (double)H * W / (double)covered;
+        if (fill > best_fill + 1e-9) { best_fill = fill; best = tw; }
+    }
+    return best_fill >= 0.8 ? best : 0;
+}
+// f(int_c<log2 slab_w>{}): the slab kernels' template argument
+template <typename F> static inline void wgrad_with_slab(int slab_w, F&& f) {
+    if (slab_w == 64) f(int_c<6>{});
+    else if (slab_w == 32) f(int_c<5>{});
+    else f(int_c<4>{});
+}
+
 // Shapes this kernel takes: bf16, 3x3, stride 1, pad 1, no fused input activation, Cin a multiple of 64, Cout a
 // multiple of 8 and >= 64, slabs at least 80 % inside the image, and at least S2E_WGRAD_PATCH (default 256)
 // slab x tile work items -- one per CU; swept in round 2: 1024 -> 256 moves the 16^2 [gamma | beta] and 8^2 layers here from the
@@ -543,14 +562,8 @@ int s2e_wgrad_patch_plan(int dtype, const s2e_conv_desc* d) {
     if (min_items <= 0 || dtype != S2E_BF16) return 0;
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->in_act != S2E_ACT_NONE || d->transposed) return 0;
     if (d->Ho != d->Hi || d->Wo != d->Wi || d->Cin % 64 != 0 || d->Cout % 8 != 0 || d->Cout < 64) return 0;
-    int best = 0; double best_fill = 0.0;
-    for (int tw = 64; tw >= 16; tw >>= 1) {
-        const int th = 128 / tw;
-        const long covered = (long)ceil_div(d->Ho, th) * th * ceil_div(d->Wo, tw) * tw;
-        const double fill = (double)d->Ho * d->Wo / (double)covered;
-        if (fill > best_fill + 1e-9) { best_fill = fill; best = tw; }
-    }
-    if (best_fill < 0.8) return 0;
+    const int best = wgrad_best_slab(d->Ho, d->Wo);
+    if (!best) return 0;
     const long items = (long)d->N * ceil_div(d->Ho, 128 / best) * ceil_div(d->Wo, best) * ceil_div(d->Cout, 128) * (d->Cin / 64);
     return items >= min_items ? best : 0;
 }
@@ -569,14 +582,12 @@ static void wp_plan(int slab_w, const s2e_conv_desc* d, WpParams& p, int& splits
 
 // the partial-tile workspace pays off from a few splits on; below that the atomics are few
 size_t s2e_wgrad_patch_workspace_bytes(int slab_w, const s2e_conv_desc* d) {
-    const bool on = true;                            // (partial tiles through the workspace: 30 us against 58 us as atomics)
     WpParams p{}; int splits;
     wp_plan(slab_w, d, p, splits);
-    // (one split: every dW element has a single writer already.  Two or three -- the 1024-channel layers at 16^2: 128 tiles x 2 -- were
-    //  combined with atomics until round 4: 75 MB of fp32 atomics at ~1.3 TB/s; through the workspace the family is 2.69 against
-    //  2.76-2.83 ms per step, same box, alternating)
-    const int min_splits = 2;
-    if (!on || splits < min_splits) return s2e_deterministic() ? (size_t)p.tiles_co * p.tiles_ci * splits * 128 * sizeof(float) : 0;
+    // (partial tiles through the workspace: 30 us against 58 us as atomics.  One split: every dW element has a single writer already.
+    //  Two or three -- the 1024-channel layers at 16^2: 128 tiles x 2 -- were combined with atomics until round 4: 75 MB of fp32 atomics
+    //  at ~1.3 TB/s; through the workspace the family is 2.69 against 2.76-2.83 ms per step, same box, alternating)
+    if (splits < 2) return s2e_deterministic() ? (size_t)p.tiles_co * p.tiles_ci * splits * 128 * sizeof(float) : 0;
     return (size_t)p.tiles_co * p.tiles_ci * splits * (9 * 128 * 64 + (s2e_deterministic() ? 128 : 0)) * sizeof(float);
 }
 
@@ -595,9 +606,7 @@ int s2e_wgrad_patch_launch(int slab_w, const void* x, const void* gy, float* dw,
     p.ws = tiles_ws ? (float*)workspace : nullptr;
     // S2E_DETERMINISTIC: the workgroups' bias sums go through the tail of the workspace and are folded in a fixed order
     p.bws = (have && s2e_deterministic() && dbias) ? (float*)workspace + (tiles_ws ? (size_t)nwg * (9 * 128 * 64) : 0) : nullptr;
-    if (slab_w == 64) conv_wgrad_patch_kernel<6><<<nwg, 512, 0, st>>>(p);
-    else if (slab_w == 32) conv_wgrad_patch_kernel<5><<<nwg, 512, 0, st>>>(p);
-    else conv_wgrad_patch_kernel<4><<<nwg, 512, 0, st>>>(p);
+    wgrad_with_slab(slab_w, [&](auto s) { conv_wgrad_patch_kernel<decltype(s)::value><<<nwg, 512, 0, st>>>(p); });
     S2E_CHECK_LAUNCH("conv_wgrad_patch_kernel");
     if (p.ws) {
         const long threads = (long)d->Cout * (9 * d->Cin / 4);
@@ -621,14 +630,8 @@ int s2e_wgrad_c8_plan(int dtype, const s2e_conv_desc* d) {
     if (!on || dtype != S2E_BF16) return 0;
     if (d->KH != 3 || d->KW != 3 || d->stride != 1 || d->pad != 1 || d->in_act != S2E_ACT_NONE || d->transposed) return 0;
     if (d->Ho != d->Hi || d->Wo != d->Wi || d->Cin != 8 || d->Cout % 128 != 0) return 0;
-    int best = 0; double best_fill = 0.0;
-    for (int tw = 64; tw >= 16; tw >>= 1) {
-        const int th = 128 / tw;
-        const long covered = (long)ceil_div(d->Ho, th) * th * ceil_div(d->Wo, tw) * tw;
-        const double fill = (double)d->Ho * d->Wo / (double)covered;
-        if (fill > best_fill + 1e-9) { best_fill = fill; best = tw; }
-    }
-    if (best_fill < 0.8) return 0;
+    const int best = wgrad_best_slab(d->Ho, d->Wo);
+    if (!best) return 0;
     const long nslabs = (long)d->N * ceil_div(d->Ho, 128 / best) * ceil_div(d->Wo, best);
     return nslabs >= 256 ? best : 0;
 }
@@ -656,9 +659,7 @@ int s2e_wgrad_c8_launch(int slab_w, const void* x, const void* gy, float* dw, fl
     wc_plan(slab_w, d, p, splits, tiles_co);
     p.x = x; p.gy = gy; p.ws = (float*)workspace;
     const dim3 grid(splits, tiles_co);
-    if (slab_w == 64) conv_wgrad_c8_kernel<6><<<grid, 256, 0, st>>>(p);
-    else if (slab_w == 32) conv_wgrad_c8_kernel<5><<<grid, 256, 0, st>>>(p);
-    else conv_wgrad_c8_kernel<4><<<grid, 256, 0, st>>>(p);
+    wgrad_with_slab(slab_w, [&](auto s) { conv_wgrad_c8_kernel<decltype(s)::value><<<grid, 256, 0, st>>>(p); });
     S2E_CHECK_LAUNCH("conv_wgrad_c8_kernel");
     const int bx = ceil_div((long)d->Cout * 73, 256);
     int by = 1;
@@ -670,21 +671,11 @@ int s2e_wgrad_c8_launch(int slab_w, const void* x, const void* gy, float* dw, fl
 
 // ---- batched form (see conv_wgrad_c8_batch_kernel).  Host-side job descriptions; every job: bf16, x (N,H,W,8) one-hot map,
 // gy (N,H,W,128), 3x3 stride 1 pad 1; dw_oihw fp32 (128, ncls, 3, 3) and dbias fp32 (128) are ACCUMULATED into.
-static int wc_best_slab(int H, int W) {
-    int best = 0; double best_fill = 0.0;
-    for (int tw = 64; tw >= 16; tw >>= 1) {
-        const int th = 128 / tw;
-        const long covered = (long)ceil_div(H, th) * th * ceil_div(W, tw) * tw;
-        const double fill = (double)H * W / (double)covered;
-        if (fill > best_fill + 1e-9) { best_fill = fill; best = tw; }
-    }
-    return best_fill >= 0.8 ? best : 0;
-}
 extern "C" int s2e_wgrad_c8_batch_supported(int dtype, int H, int W, int cout) {
-    return dtype == S2E_BF16 && cout == 128 && wc_best_slab(H, W) != 0;
+    return dtype == S2E_BF16 && cout == 128 && wgrad_best_slab(H, W) != 0;
 }
 static void wc_job_plan(int N, const s2e_wgrad_c8_job& h, WcJob& J, int& slab_w) {
-    slab_w = h.rect_list ? 16 : wc_best_slab(h.H, h.W);         // (a rectangle list: its 16 x 16 rectangles as 8 x 16 slabs)
+    slab_w = h.rect_list ? 16 : wgrad_best_slab(h.H, h.W);         // (a rectangle list: its 16 x 16 rectangles as 8 x 16 slabs)
     J.x = h.x; J.gy = h.gy; J.dw = h.dw_oihw; J.dbias = h.dbias; J.H = h.H; J.W = h.W; J.ncls = h.ncls;
     J.rect_list = h.rect_list; J.rect_count = h.rect_count;
     J.sx = ceil_div(h.W, slab_w); J.sy = ceil_div(h.H, 128 / slab_w); J.nslabs = N * J.sy * J.sx;
@@ -697,7 +688,7 @@ extern "C" size_t s2e_wgrad_c8_batch_workspace_bytes(int N, const s2e_wgrad_c8_j
     if (!jobs || n_jobs <= 0 || N <= 0) return 0;
     size_t tiles = 0;
     for (int i = 0; i < n_jobs; ++i) {
-        if (!wc_best_slab(jobs[i].H, jobs[i].W)) return 0;
+        if (!wgrad_best_slab(jobs[i].H, jobs[i].W)) return 0;
         WcJob J; int sw;
         wc_job_plan(N, jobs[i], J, sw);
         tiles += J.splits;
@@ -718,7 +709,7 @@ extern "C" int s2e_wgrad_c8_batch(int dtype, int N, const s2e_wgrad_c8_job* jobs
         int ws_tile = 0;
         for (int i = 0; i < cnt; ++i) {
             const s2e_wgrad_c8_job& h = jobs[base + i];
-            if (!h.x || !h.gy || !h.dw_oihw || h.ncls <= 0 || h.ncls > 8 || !wc_best_slab(h.H, h.W) || (h.rect_list != nullptr) != (h.rect_count != nullptr)
+            if (!h.x || !h.gy || !h.dw_oihw || h.ncls <= 0 || h.ncls > 8 || !wgrad_best_slab(h.H, h.W) || (h.rect_list != nullptr) != (h.rect_count != nullptr)
                 || (h.rect_list && ((h.H | h.W) & 15)))
                 S2E_FAIL(S2E_ERR_ARG, "s2e_wgrad_c8_batch: bad job %d", base + i);
             wc_job_plan(N, h, all.j[i], slab[i]);
@@ -731,9 +722,7 @@ extern "C" int s2e_wgrad_c8_batch(int dtype, int N, const s2e_wgrad_c8_job* jobs
             for (int i = 0; i < cnt; ++i)
                 if (slab[i] == sw) { g.j[g.n] = all.j[i]; g.j[g.n].first = first; first += all.j[i].splits; ++g.n; }
             if (!g.n) continue;
-            if (sw == 64) conv_wgrad_c8_batch_kernel<6><<<first, 256, 0, st>>>(g, ws);
-            else if (sw == 32) conv_wgrad_c8_batch_kernel<5><<<first, 256, 0, st>>>(g, ws);
-            else conv_wgrad_c8_batch_kernel<4><<<first, 256, 0, st>>>(g, ws);
+            wgrad_with_slab(sw, [&](auto s) { conv_wgrad_c8_batch_kernel<decltype(s)::value><<<first, 256, 0, st>>>(g, ws); });
             S2E_CHECK_LAUNCH("conv_wgrad_c8_batch_kernel");
         }
         wgrad_c8_batch_reduce_kernel<<<dim3(cnt * 37, s2e_deterministic() ? 1 : 8), 256, 0, st>>>(all, ws);

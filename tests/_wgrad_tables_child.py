@@ -4,7 +4,7 @@
 Used in-process by tests/test_wgrad_job_tables_gpu.py and run by it as a child process for the switches the library reads once per
 process (S2E_C8W_WGS, S2E_WGRAD_MULTI_WGS, S2E_WGRAD_FLAT_WGS, S2E_WGRAD_PARTIAL):
 
-    python tests/_wgrad_tables_child.py [--tables a,b,...] [--modes exact,short,none]
+    python tests/_wgrad_tables_child.py [--tables a,b,...] [--modes exact,short,half,none]
 
 Every table is a list of jobs (n, hi, wi, cin, cout, k, stride, pad, kind, dw, db): `kind` is the kernel s2e_conv2d_wgrad_multi_kind
 must report, dw = (buffer, float offset) and db = (buffer, float offset) or None name ranges of the output buffers, which several jobs
@@ -207,8 +207,9 @@ def operands(table, seed, dev):
 
 def run(name, mode, dev=None, ops=None, seed=1):
     """One call of s2e_conv2d_wgrad_multi on table `name`; mode 'exact' (the workspace it asks for), 'short' (256 bytes less: the
-    partial-workspace fallback) or 'none' (no workspace: the atomic fallbacks).  Asserts kinds, guard band and sums; returns the
-    worst relative error."""
+    partial-workspace fallback), 'half' (half of it, rounded down to 256: the middle of the greedy fallback, some sections served and
+    the rest atomics) or 'none' (no workspace: the atomic fallbacks).  Asserts kinds, guard band and sums; returns the worst
+    relative error."""
     L, lb = lib()
     dev = dev or torch.device('cuda', 0)
     table = TABLES[name]
@@ -219,7 +220,7 @@ def run(name, mode, dev=None, ops=None, seed=1):
     start = {b: torch.randn(r.numel(), generator=g, device=dev) for b, r in ops['ref'].items()}
     ops['buf'] = {b: t.clone() for b, t in start.items()}
     wsb = workspace_bytes(table)
-    passed = {'exact': wsb, 'short': max(wsb - 256, 0), 'none': 0}[mode]
+    passed = {'exact': wsb, 'short': max(wsb - 256, 0), 'half': wsb // 2 // 256 * 256, 'none': 0}[mode]
     ws = torch.full((passed + GUARD,), PATTERN, dtype=torch.uint8, device=dev)
     arr = job_array(table, ops)
     st = torch.cuda.current_stream(dev).cuda_stream
@@ -339,7 +340,7 @@ def wgrad_c8_batch_guard(dev=None, seed=9):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--tables', default=','.join(TABLES))
-    ap.add_argument('--modes', default='exact,short,none')
+    ap.add_argument('--modes', default='exact,short,half,none')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     calls, worst = 0, 0.0

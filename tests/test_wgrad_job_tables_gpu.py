@@ -1,7 +1,7 @@
 """The weight-gradient job tables -- s2e_conv2d_wgrad_multi (generic tile kernel, conv_wgrad_flat.hip, conv_c8.hip), s2e_wgrad_batch and
 s2e_wgrad_c8_batch -- on tables built where their host planners can go wrong: chunk boundaries (WGM_MAX_JOBS 26, WF_MAX_JOBS 24,
 C8W_MAX_JOBS 4, WC_MAX_JOBS 24), lopsided shares of a fixed workgroup budget, jobs sharing dw / dbias (overlapping ranges included),
-a workspace that is exact, 256 bytes short or absent.  Every result is checked against fp64 sums of the same bf16 operands, accumulated
+a workspace that is exact, 256 bytes short, half the size or absent.  Every result is checked against fp64 sums of the same bf16 operands, accumulated
 into non-zero outputs, and every workspace is followed by a guard band that must come back unchanged (tests/_wgrad_tables_child.py)."""
 import os
 import subprocess
@@ -50,10 +50,11 @@ def test_generic_shared_jobs_each_use_partial_tiles():
         assert T.workspace_bytes([j]) > 0
 
 
-_NO_WORKSPACE = ('flat25',)        # (flat jobs use none: no 'short' case)
+_NO_WORKSPACE = ('flat25',)        # (flat jobs use none: no 'short' and no 'half' case)
 
 
-@pytest.mark.parametrize('name,mode', [(t, m) for t in T.TABLES for m in ('exact', 'short', 'none') if not (m == 'short' and t in _NO_WORKSPACE)])
+@pytest.mark.parametrize('name,mode', [(t, m) for t in T.TABLES for m in ('exact', 'short', 'half', 'none')
+                                       if not (m in ('short', 'half') and t in _NO_WORKSPACE)])
 def test_wgrad_multi_table_against_fp64(name, mode):
     """s2e_conv2d_wgrad_multi on one table: kinds as planned, guard band intact, every output buffer = its start + the fp64 sums of
     the jobs writing there (2e-4 x max |sum|)."""
