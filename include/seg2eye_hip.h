@@ -683,6 +683,47 @@ int s2e_msssim_u8(const uint8_t* a, const uint8_t* b, int N, int H, int W, int l
 int s2e_msssim_bwd(int dtype, const void* x, const void* y, const void* pyramid, const float* maps, const float* coef, const float* gout,
                    int N, int H, int W, int levels, void* gbuf, size_t gbuf_bytes, void* dx, void* stream);
 
+/* ------------------------------------------------------------------ focal frequency loss (an extension: the reference has none)
+ * The focal frequency loss (Jiang, Dai, Wu, Loy, ICCV 2021) of two single-channel batches x, y (N,H,W) and its gradient with respect to
+ * x: whole image, per image, no log, the per-image maximum (the paper's patch_factor, ave_spectrum, log_matrix and batch_matrix variants
+ * are not built).  Values in the tensor's own units, no clamp; u = a / 255 for the uint8 entry.  For image n:
+ *   1. d = x - y, formed in fp32 from the loaded values (the DFT is linear: only d is transformed).
+ *   2. Z[ky,kx] = (H W)^-1/2 sum_{r,c} d[r,c] exp(-2 pi i (ky r / H + kx c / W)): the orthonormal 2-D DFT, H W complex bins.
+ *   3. dist = Re Z^2 + Im Z^2.
+ *   4. the focal weight w = dist^(alpha/2) / max over the image's H W bins of dist^(alpha/2): a constant of the step, no gradient flows
+ *      through it.  alpha in [0, 4].  alpha = 0: w = 1 everywhere, bins with dist = 0 included; alpha > 0: a bin with dist = 0 has w = 0;
+ *      an image whose maximum is 0 (x == y) has w = 0 everywhere.
+ *   5. ffl[n] (fp32) = 1 / (H W) sum_bins w dist, the sum in fp64.
+ *   6. dx[n] (of T) = gout[n] 2 / (H W) Re(inverse orthonormal 2-D DFT of w Z).  y gets none.
+ * So ffl[n] = mean((x - y)^2) at alpha = 0 (Parseval), ffl and dx are exactly 0 for x == y, and ffl is symmetric in x and y.
+ * The kernels carry only the Wh = W/2 + 1 non-redundant columns of the Hermitian spectrum, with multiplicity 1 for kx = 0 and for
+ * kx = W/2 when W is even, 2 otherwise, forward and backward; the maximum over the half is the maximum over the whole.
+ * Each transform is a dense real matrix product on the exact-fp32 matrix instruction (v_mfma_f32_16x16x4_f32) with the DFT matrices
+ * cos, sin (2 pi (k j mod n) / n) n^-1/2, n = H and n = W, which s2e_ffl_tables fills on the device (one launch): the argument reduced in
+ * integers, evaluated in fp64, rounded once to fp32, zero-padded to the tile size.  The tables depend on (H, W) only.
+ * s2e_ffl_fwd, three launches: the row transform of d; the column transform, the 2H x 2H block matrix [C -S; S C], whose epilogue keeps
+ * Z in `spectrum` when that is not NULL and writes one fp64 partial sum of m dist^(1 + alpha/2) and one fp32 partial maximum of dist per
+ * block into `workspace` (plain stores); the per-image fold in index order: ffl[n] = sum / (H W max^(alpha/2)) and the backward's
+ * coef[n] = 2 / (H W max^(alpha/2)), both 0 when max = 0.  s2e_ffl_bwd, two launches: the column inverse transform of
+ * coef[n] gout[n] dist^(alpha/2) Z (dist recomputed from Z), then the row inverse transform with the multiplicities, which writes dx.
+ * alpha = 0, 1, 2 take 1, sqrt and the identity for dist^(alpha/2), any other alpha exp2(alpha/2 log2 dist).
+ * No atomics, no synchronisation, launch shapes from (N, H, W) alone, bit-reproducible.
+ * Sizes: s2e_ffl_tables_bytes(H, W), s2e_ffl_workspace_bytes(N, H, W) (forward and backward take the same) and
+ * s2e_ffl_spectrum_bytes(N, H, W); each is 0 where the call would be illegal.  workspace and spectrum are uninitialised.
+ * Before any launch: S2E_ERR_ARG on a null pointer (the spectrum of s2e_ffl_fwd excepted), N <= 0, a bad dtype, alpha negative,
+ * non-finite or above 4; S2E_ERR_UNSUPPORTED on H < 2 or W < 2, H or W above 1024, N > 65535 or N H W >= 2^31; S2E_ERR_ARG on a short
+ * buffer. */
+size_t s2e_ffl_tables_bytes(int H, int W);
+size_t s2e_ffl_workspace_bytes(int N, int H, int W);
+size_t s2e_ffl_spectrum_bytes(int N, int H, int W);
+int s2e_ffl_tables(int H, int W, float* tables, size_t tables_bytes, void* stream);
+int s2e_ffl_fwd(int dtype, const void* x, const void* y, int N, int H, int W, float alpha, const float* tables, size_t tables_bytes,
+                float* ffl, float* coef, float* spectrum, size_t spectrum_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int s2e_ffl_u8(const uint8_t* a, const uint8_t* b, int N, int H, int W, float alpha, const float* tables, size_t tables_bytes, float* ffl,
+               void* workspace, size_t workspace_bytes, void* stream);
+int s2e_ffl_bwd(int dtype, const float* spectrum, const float* coef, const float* gout, int N, int H, int W, float alpha,
+                const float* tables, size_t tables_bytes, void* workspace, size_t workspace_bytes, void* dx, void* stream);
+
 /* ------------------------------------------------------------------ region-aware reconstruction error (an extension: the reference has none)
  * Statistics of d = x - y per image and label class, the class-balanced loss built from them, and its gradient with respect to x.
  * x, y: single-channel batches (N,H,W) of T in [-1, 1] (or uint8 0..255 for s2e_region_stats_u8); label: uint8 (N,Hl,Wl); ncls in 1..8.

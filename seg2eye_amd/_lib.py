@@ -180,6 +180,13 @@ SIGNATURES = {
     's2e_msssim_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     's2e_msssim_u8': (STATUS, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
     's2e_msssim_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, C.c_size_t, _vp, _vp]),
+    's2e_ffl_tables_bytes': (SIZE, [_i, _i]),
+    's2e_ffl_workspace_bytes': (SIZE, [_i, _i, _i]),
+    's2e_ffl_spectrum_bytes': (SIZE, [_i, _i, _i]),
+    's2e_ffl_tables': (STATUS, [_i, _i, _vp, C.c_size_t, _vp]),
+    's2e_ffl_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _f, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _vp, C.c_size_t, _vp]),
+    's2e_ffl_u8': (STATUS, [_vp, _vp, _i, _i, _i, _f, _vp, C.c_size_t, _vp, _vp, C.c_size_t, _vp]),
+    's2e_ffl_bwd': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _f, _vp, C.c_size_t, _vp, C.c_size_t, _vp, _vp]),
     's2e_region_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
     's2e_region_loss_fwd': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     's2e_region_stats_u8': (STATUS, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),

@@ -13,7 +13,7 @@ One module per family (round 5; `ops.<name>` keeps resolving for every name, pri
   conv      packs, conv2d / wgrad launchers, Conv2dFn, the encoder's FC head
   spade     statistics, label convs, the SPADE+Style block (fused, label-sparse), InstanceNorm
   resample  upsampling, resize, pooling, the discriminator's input plumbing
-  losses    loss reductions, feature matching, Adam, the OpenEDS metric, SSIM and MS-SSIM, the region-aware error
+  losses    loss reductions, feature matching, Adam, the OpenEDS metric, SSIM and MS-SSIM, the region-aware error, the focal frequency loss
   preprocess  --device_preprocess: Pillow's bicubic resize and cv2's nearest resize of raw OpenEDS frames, `materialize`
   visual    the validation panels of the visualiser: five resized, normalised cells per sample as uint8 (`sidebyside_u8`)
   switches  the experiment switches (environment)"""

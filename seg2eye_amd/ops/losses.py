@@ -1,5 +1,5 @@
 """Loss reductions (hinge / L1 / feature matching with in-place gradient injection), the flat Adam step, and the OpenEDS validation
-metric, SSIM, MS-SSIM and region-error kernels."""
+metric, SSIM, MS-SSIM, focal-frequency and region-error kernels."""
 import torch
 
 from .. import _lib as L
@@ -427,6 +427,111 @@ def ms_ssim_u8(a, b, weights=None, return_terms=False):
                        (_p(a), _p(b), n, h, w, levels, wts, _p(out), _p(terms), _p(pyr) if pyr.numel() else None, pyr.numel() * 4, _p(ws),
                         ws.numel() * 8, _stream()), nbytes=float(2 * a.numel() + 3 * pyr.numel() * 4))
     return (out, terms) if return_terms else out
+
+
+_FFL_TABLES = {}     # (device index, H, W) -> the DFT tables of s2e_ffl_tables (fp32, they depend on the size alone)
+
+
+def ffl_tables(h, w, device):
+    """The DFT tables the s2e_ffl_* entries read for H x W images, built on the device by one launch (s2e_ffl_tables) and cached per
+    (device, H, W).  A model that uses the term builds them at construction; on a cache miss while a hipGraph is being captured the
+    tables are built into a buffer of the capture, as every other buffer of the call is, and not cached (the graph owns that memory).
+    An illegal size gives a one-element buffer and the entry point that gets it says why."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise L.Seg2EyeHipError('seg2eye_amd ops run on the GPU only (got a %s device); there is no CPU fallback' % device)
+    key = (device.index if device.index is not None else torch.cuda.current_device(), int(h), int(w))
+    t = _FFL_TABLES.get(key)
+    if t is None:
+        nbytes = int(L.call.s2e_ffl_tables_bytes(int(h), int(w)))
+        t = torch.empty(max(1, nbytes // 4), dtype=torch.float32, device=device)
+        if nbytes:
+            L.call.s2e_ffl_tables(int(h), int(w), _p(t), nbytes, _stream())
+            if not torch.cuda.is_current_stream_capturing():
+                _FFL_TABLES[key] = t
+    return t
+
+
+def _ffl_cost(n, h, w):
+    """(algorithmic FLOPs of the two real matrix products of one direction, bytes of the half spectrum): rows H x W x 2 Wh, columns
+    2H x 2H x Wh, two FLOPs per multiply-add."""
+    wh = w // 2 + 1
+    return float(2 * n * (h * w * 2 * wh + 2 * h * 2 * h * wh)), 8 * n * h * wh
+
+
+class FocalFreqFn(torch.autograd.Function):
+    """ffl (N,) of two (N,H,W) batches (s2e_ffl_fwd: three launches); the backward is s2e_ffl_bwd on the saved spectrum and coefficients
+    (two launches), for x only.  When x needs no gradient no spectrum is allocated and nothing is saved."""
+
+    @staticmethod
+    def forward(ctx, x, y, alpha):
+        a, b = _single_channel(x.detach()), _single_channel(y.detach().to(x.dtype))
+        _need(a, b)
+        if a.shape != b.shape:
+            raise ValueError('x and y of one shape expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+        n, h, w = a.shape
+        alpha = float(alpha)
+        tab = ffl_tables(h, w, a.device)
+        out = torch.empty(n, dtype=torch.float32, device=a.device)
+        coef = torch.empty(n, dtype=torch.float32, device=a.device)
+        ws = torch.empty(max(1, int(L.call.s2e_ffl_workspace_bytes(n, h, w)) // 4), dtype=torch.float32, device=a.device)
+        spec = None
+        if ctx.needs_input_grad[0]:
+            spec = torch.empty(int(L.call.s2e_ffl_spectrum_bytes(n, h, w)) // 4, dtype=torch.float32, device=a.device)
+            if spec.numel() == 0:
+                spec = None                                      # (an illegal size: the entry point refuses it below)
+        flops, sbytes = _ffl_cost(n, h, w)
+        LaunchProfiler.run('ffl_fwd', flops, L.call.s2e_ffl_fwd,
+                           (_dt(a), _p(a), _p(b), n, h, w, alpha, _p(tab), tab.numel() * 4, _p(out), _p(coef), _p(spec),
+                            spec.numel() * 4 if spec is not None else 0, _p(ws), ws.numel() * 4, _stream()),
+                           nbytes=float(2 * a.numel() * a.element_size() + 2 * sbytes + (sbytes if spec is not None else 0)))
+        if spec is not None:
+            ctx.save_for_backward(spec, coef, tab)
+        ctx.cfg = (x.shape, (n, h, w), a.dtype, alpha)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if not ctx.saved_tensors:
+            return None, None, None
+        spec, coef, tab = ctx.saved_tensors
+        x_shape, (n, h, w), dtype, alpha = ctx.cfg
+        gs = gout.detach().float().contiguous()
+        dx = torch.empty(n, h, w, dtype=dtype, device=spec.device)
+        ws = torch.empty(int(L.call.s2e_ffl_workspace_bytes(n, h, w)) // 4, dtype=torch.float32, device=spec.device)
+        flops, sbytes = _ffl_cost(n, h, w)
+        LaunchProfiler.run('ffl_bwd', flops, L.call.s2e_ffl_bwd,
+                           (_dt(dtype), _p(spec), _p(coef), _p(gs), n, h, w, alpha, _p(tab), tab.numel() * 4, _p(ws), ws.numel() * 4, _p(dx), _stream()),
+                           nbytes=float(dx.numel() * dx.element_size() + 3 * sbytes))
+        return dx.view(x_shape), None, None
+
+
+def focal_freq_loss(x, y, alpha=1.0):
+    """Per-image focal frequency loss (Jiang et al., ICCV 2021) of two single-channel batches, (N,1,H,W) or (N,H,W), fp32 or
+    bf16, in the tensors' own units: with Z the orthonormal 2-D DFT of x - y and dist = |Z|^2, ffl[n] = mean over the H W bins of
+    w dist, w = dist^(alpha/2) / max_bins dist^(alpha/2) (a constant of the step; alpha in [0, 4]; alpha = 0: w = 1 and ffl is the mean
+    squared error).  Whole image, per image, no log.  -> fp32 (N,), lower is better, 0 for identical images; differentiable in x only
+    (y is cast to x's dtype)."""
+    return FocalFreqFn.apply(x, y, alpha)
+
+
+def focal_freq_loss_u8(a, b, alpha=1.0):
+    """focal_freq_loss on uint8 images that already are 0..255 (u = a / 255).  -> fp32 (N,), no gradient."""
+    a, b = _single_channel(a), _single_channel(b)
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise ValueError('uint8 images expected')
+    _need(a, b)
+    if a.shape != b.shape:
+        raise ValueError('a and b of one shape expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    n, h, w = a.shape
+    tab = ffl_tables(h, w, a.device)
+    out = torch.empty(n, dtype=torch.float32, device=a.device)
+    ws = torch.empty(max(1, int(L.call.s2e_ffl_workspace_bytes(n, h, w)) // 4), dtype=torch.float32, device=a.device)
+    flops, sbytes = _ffl_cost(n, h, w)
+    LaunchProfiler.run('ffl_fwd', flops, L.call.s2e_ffl_u8,
+                       (_p(a), _p(b), n, h, w, float(alpha), _p(tab), tab.numel() * 4, _p(out), _p(ws), ws.numel() * 4, _stream()),
+                       nbytes=float(2 * a.numel() + 2 * sbytes))
+    return out
 
 
 _REGION_NORMS = {'l1': L.REGION_L1, 'l2': L.REGION_L2}

@@ -47,6 +47,8 @@ _DEFAULTS = dict(
     lambda_region=0.0,         # > 0: lambda_region * the class-balanced reconstruction error joins the generator's loss (ops.region_loss); 0 = off
     region_norm='l1',          # 'l1' | 'l2': the per-pixel error of that term
     region_weights='',         # 'w0,w1,...': one non-negative weight per label class (parse_region_weights); '' = all ones
+    lambda_ffl=0.0,            # > 0: lambda_ffl * mean focal frequency loss(fake, target) joins the generator's loss (ops.focal_freq_loss); 0 = off
+    ffl_alpha=1.0,             # the focal exponent of that term, in [0, 4]: a bin's weight is its spectral distance to the power alpha / 2, over the image's largest
 )
 
 
@@ -150,6 +152,9 @@ _CLI = [  # (name, type or 'flag', default, choices)
     # validation also takes the error apart by label class (ops.region_stats_u8 on the same uint8 pair):
     # 'region_mae/<key>/<mode>/<c>' and 'region_rmse/<key>/<mode>/<c>' in the statistics (grey levels), `region` in the error log
     ('val_regions', 'flag', False, None),
+    # validation also scores the focal frequency loss, alpha = 1, on the same uint8 pair (ops.focal_freq_loss_u8): 'ffl/<key>/<mode>'
+    # in the statistics (lower is better), `ffl` in the error log; off = validation as it was
+    ('val_ffl', 'flag', False, None),
 ]
 _CLI_TRAIN_BUILD = [
     ('ema_decay', _F, 0.0, None), ('ema_start', _I, 0, None),        # averaged generator weights; 0 = off
@@ -168,6 +173,10 @@ _CLI_TRAIN_BUILD = [
     # class-balanced reconstruction term of the generator's loss: every label class counts by its weight, not by its area;
     # 'region/raw' in the loss log is the term before lambda_region; 0 = off, nothing is launched
     ('lambda_region', _F, 0.0, None), ('region_norm', _S, 'l1', ['l1', 'l2']), ('region_weights', _S, '', None),
+    # focal frequency term of the generator's loss: lambda_ffl * mean_n ffl[n](fake, target), the spectrum's squared distance with
+    # every frequency weighted by how badly it is missed; 'FFL/raw' in the loss log is the mean before lambda, so LOWER is better; 0 = off,
+    # nothing is launched
+    ('lambda_ffl', _F, 0.0, None), ('ffl_alpha', _F, 1.0, None),
 ]
 _CLI_TEST_BUILD = [
     ('use_ema', 'flag', False, None),                                 # score / generate with the averaged weights' checkpoint files
@@ -220,6 +229,8 @@ def parse(argv=None, is_train=True):
         raise ValueError('--ema_decay must lie in [0, 1) (0 = off) and --ema_start must not be negative')
     if not opt.grad_clip_norm >= 0.0 or opt.max_consecutive_skips < 0:
         raise ValueError('--grad_clip_norm (0 = off) and --max_consecutive_skips (0 = never stop) must not be negative')
+    if not 0.0 <= opt.ffl_alpha <= 4.0:                     # (a NaN fails both comparisons)
+        raise ValueError('--ffl_alpha must lie in [0, 4] (got %r)' % (opt.ffl_alpha,))
     parse_region_weights(opt.region_weights, opt.label_nc)   # (a malformed list raises ValueError here, not at the first step)
     if opt.diffaug:
         from .diffaug import parse_policy

@@ -52,6 +52,11 @@ class Pix2PixModel(nn.Module):
             from .options import parse_region_weights
             self.region_w = torch.tensor(parse_region_weights(getattr(opt, 'region_weights', ''), opt.label_nc), dtype=torch.float32,
                                          device=self.device())
+        # --lambda_ffl: the DFT tables of the image size, built once and outside any graph capture -- a captured step reads
+        # the cached tables at every replay; the flag absent: nothing is allocated or launched
+        if opt.isTrain and getattr(opt, 'lambda_ffl', 0) and self.device().type == 'cuda':
+            from .options import image_hw
+            ops.ffl_tables(*image_hw(opt), self.device())
         if opt.isTrain:
             self.criterionGAN = networks.GANLoss(opt.gan_mode, opt=opt)
             if not opt.no_vgg_loss:
@@ -236,6 +241,11 @@ class Pix2PixModel(nn.Module):
             r, _ = ops.region_loss(fake_image, target_image, seg.label, self.region_w, getattr(opt, 'region_norm', 'l1'))
             G_losses['region/weighted'] = (opt.lambda_region * r).view(1)
             self.add_to_loss_log('region/raw', r.detach().view(1))
+        if getattr(opt, 'lambda_ffl', 0):
+            # focal frequency loss of the un-augmented fake against the target (an extension): three launches, two in the backward
+            f = ops.focal_freq_loss(fake_image, target_image, getattr(opt, 'ffl_alpha', 1.0)).mean()
+            G_losses['FFL/weighted'] = (opt.lambda_ffl * f).view(1)
+            self.add_to_loss_log('FFL/raw', f.detach())           # (the mean before lambda: lower is better)
         if getattr(self.opt, 'lambda_openeds', 0):
             # pix2pix_model.py:206-210: the OpenEDS metric of the batch (per image; no gradient -- the reference's
             # `.int()` cuts the graph too), weighted into the logged loss

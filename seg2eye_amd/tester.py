@@ -12,7 +12,8 @@ statistics lines (`run(log=True)`) and the panels of `run_visual_validation`; wi
 its own Visualizer there; TensorBoard events are not built).  With `--val_ssim` every scored pair also gets its structural similarity
 (`s2e_ssim_u8` on the same 640 x 400 uint8 pair): `ssim/<dataset_key>/<mode>` in the statistics of `run` (the mean; higher is
 better) and one more dataset, `ssim` (float64, one per sample), in the error log; `--val_msssim` does the same with five-level MS-SSIM
-(`s2e_msssim_u8`): `msssim/<dataset_key>/<mode>` and the dataset `msssim`.  With `--val_regions` the same pair is also taken apart by
+(`s2e_msssim_u8`): `msssim/<dataset_key>/<mode>` and the dataset `msssim`; `--val_ffl` with the focal frequency loss at alpha = 1
+(`s2e_ffl_u8`; lower is better): `ffl/<dataset_key>/<mode>`, printed `%.3e`, and the dataset `ffl`.  With `--val_regions` the same pair is also taken apart by
 label class (`s2e_region_stats_u8` with the batch's label map, looked up at [(r Hl) // 640, (c Wl) // 400]; DESIGN 3.16): per class c seen in
 a scored sample `region_mae/<dataset_key>/<mode>/<c>` = sum |d| / pixels and `region_rmse/<dataset_key>/<mode>/<c>` = sqrt(sum d^2 / pixels)
 over the scored samples, in grey levels, and the dataset `region` (samples, label_nc, 3) float64 = {pixels, sum |d|, sum d^2} in the error
@@ -48,6 +49,8 @@ class Tester:
         self.all_ssim = []                                   # --val_ssim: per-sample SSIM of the last run_validation, beside its errors
         self.val_msssim = bool(getattr(self.opt, 'val_msssim', False))
         self.all_msssim = []                                 # --val_msssim: per-sample MS-SSIM of the last run_validation
+        self.val_ffl = bool(getattr(self.opt, 'val_ffl', False))
+        self.all_ffl = []                                    # --val_ffl: per-sample focal frequency loss of the last run_validation
         self.val_regions = bool(getattr(self.opt, 'val_regions', False))
         self.all_regions = []                                # --val_regions: per-sample (label_nc, 3) float64 records of the last run_validation
         self.N = getattr(self.dataloader, 'N', len(self.dataloader) * self.opt.batchSize)
@@ -103,11 +106,13 @@ class Tester:
             log['ssim'] = np.zeros((self.N,), dtype=np.float64)
         if self.val_msssim:
             log['msssim'] = np.zeros((self.N,), dtype=np.float64)
+        if self.val_ffl:
+            log['ffl'] = np.zeros((self.N,), dtype=np.float64)
         if self.val_regions:
             log['region'] = np.zeros((self.N, self.opt.label_nc, 3), dtype=np.float64)
         return log
 
-    def _write_error_log_batch(self, error_log, data_i, i, errors, fake=None, ssim=None, regions=None, msssim=None):
+    def _write_error_log_batch(self, error_log, data_i, i, errors, fake=None, ssim=None, regions=None, msssim=None, ffl=None):
         """tester.py:76-91; the panels of a batch are normalised over that batch, as there."""
         a = i * self.opt.batchSize
         b = min(a + len(errors), self.N)
@@ -118,6 +123,8 @@ class Tester:
             error_log['ssim'][a:b] = np.asarray(ssim, dtype=np.float64)[:b - a]
         if 'msssim' in error_log:
             error_log['msssim'][a:b] = np.asarray(msssim, dtype=np.float64)[:b - a]
+        if 'ffl' in error_log:
+            error_log['ffl'][a:b] = np.asarray(ffl, dtype=np.float64)[:b - a]
         if 'region' in error_log:
             error_log['region'][a:b] = np.asarray(regions, dtype=np.float64)[:b - a]
         if 'visualisation' in error_log:
@@ -145,6 +152,7 @@ class Tester:
         all_errors, counter = [], 0
         self.all_ssim = []
         self.all_msssim = []
+        self.all_ffl = []
         self.all_regions = []
         for i, data_i in enumerate(generator):
             data_i = materialize(data_i, self.opt, model.device())          # (--device_preprocess: raw frames -> the batch contract)
@@ -166,6 +174,11 @@ class Tester:
                 from . import ops
                 msssim = ops.ms_ssim_u8(fake_resized, target).cpu().numpy()
                 self.all_msssim += list(msssim)
+            ffl = None
+            if self.val_ffl:                                 # the same pair's spectra, alpha = 1
+                from . import ops
+                ffl = ops.focal_freq_loss_u8(fake_resized, target, 1.0).cpu().numpy()
+                self.all_ffl += list(ffl)
             regions = None
             if self.val_regions:                             # the same pair again, keyed by the batch's label map
                 from . import ops
@@ -173,7 +186,7 @@ class Tester:
                 regions = ops.region_stats_u8(fake_resized, target, label.unsqueeze(0) if label.dim() == 2 else label, self.opt.label_nc).cpu().numpy()
                 self.all_regions += list(regions)
             if error_log is not None:
-                self._write_error_log_batch(error_log, data_i, i, errors, fake, ssim, regions, msssim)
+                self._write_error_log_batch(error_log, data_i, i, errors, fake, ssim, regions, msssim, ffl)
         if error_log is not None:
             print('error log: %s' % self._close_error_log(error_log))
         return all_errors
@@ -183,7 +196,7 @@ class Tester:
         print('------------------')
         print('Error calculated on %d / %d samples' % (len(all_errors), self.N))
         for k in sorted(errors_dict):
-            print(('  %s, %.4f' if k.startswith(('ssim/', 'msssim/')) else '  %s, %.2f') % (k, errors_dict[k]))
+            print(('  %s, %.4f' if k.startswith(('ssim/', 'msssim/')) else '  %s, %.3e' if k.startswith('ffl/') else '  %s, %.2f') % (k, errors_dict[k]))
         print('  dataset_key: %s, model: %s, epoch: %s, n_steps: %s' % (self.opt.dataset_key, self.opt.name, epoch, n_steps))
 
     def run_visual_validation(self, model, mode, epoch, n_steps, limit):
@@ -229,6 +242,8 @@ class Tester:
             errors_dict['ssim/%s/%s' % (self.opt.dataset_key, mode)] = float(np.mean(np.asarray(self.all_ssim, dtype=np.float64)))
         if self.val_msssim:
             errors_dict['msssim/%s/%s' % (self.opt.dataset_key, mode)] = float(np.mean(np.asarray(self.all_msssim, dtype=np.float64)))
+        if self.val_ffl:
+            errors_dict['ffl/%s/%s' % (self.opt.dataset_key, mode)] = float(np.mean(np.asarray(self.all_ffl, dtype=np.float64)))
         if self.val_regions and self.all_regions:
             tot = np.sum(np.asarray(self.all_regions, dtype=np.float64), axis=0)                   # (label_nc, 3) over the scored samples
             for c in range(tot.shape[0]):
