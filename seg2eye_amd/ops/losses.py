@@ -229,11 +229,31 @@ def adam_flat_ema_guarded_step(p, g, m, v, ema, hyper, ema_hyper, guard, skips_m
                        nbytes=float((7 if skips_m else 9) * 4 * p.numel()))     # (adam_flat_ema_step's)
 
 
+def _one_shape(a, b, names):
+    if a.shape != b.shape:
+        raise ValueError('%s of one shape expected, got %s and %s' % (names, tuple(a.shape), tuple(b.shape)))
+    _need(a, b)
+    return a, b
+
+
+def _image_pair(x, y):
+    """The two images of a float quality op as contiguous (N,H,W) device tensors of x's dtype, detached (y is cast, as openeds_error
+    always did).  The entry points take one (N,H,W) for both pointers, so the shapes are compared here -- before the device check."""
+    return _one_shape(_single_channel(x.detach()), _single_channel(y.detach().to(x.dtype)), 'x and y')
+
+
+def _u8_pair(a, b):
+    """The same for the ops on uint8 images that already are 0..255."""
+    a, b = _single_channel(a), _single_channel(b)
+    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+        raise ValueError('uint8 images expected')
+    return _one_shape(a, b, 'a and b')
+
+
 def openeds_error(produced, target):
     """Per-image OpenEDS error of two batches in [-1, 1] (models/networks/loss.py:135-155 `calculate_mse_for_tensors`):
     both mapped to 0..255 with the reference's int truncation, then sqrt(sum d^2) / (H*W).  -> fp32 (N,), no gradient."""
-    a, b = _single_channel(produced.detach()), _single_channel(target.detach().to(produced.dtype))
-    _need(a, b)
+    a, b = _image_pair(produced, target)
     n, h, w = a.shape
     err = torch.empty(n, dtype=torch.float32, device=a.device)
     L.call.s2e_openeds_error(_dt(a), _p(a), _p(b), n, h, w, _p(err), _stream())
@@ -242,10 +262,7 @@ def openeds_error(produced, target):
 
 def openeds_error_u8(produced, target):
     """The same on uint8 images that already are 0..255 (loss.py:116-133 `calculate_mse_for_images`)."""
-    a, b = _single_channel(produced), _single_channel(target)
-    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
-        raise ValueError('uint8 images expected')
-    _need(a, b)
+    a, b = _u8_pair(produced, target)
     n, h, w = a.shape
     err = torch.empty(n, dtype=torch.float32, device=a.device)
     L.call.s2e_openeds_error_u8(_p(a), _p(b), n, h, w, _p(err), _stream())
@@ -268,8 +285,7 @@ class SsimFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y):
-        a, b = _single_channel(x.detach()), _single_channel(y.detach().to(x.dtype))
-        _need(a, b)
+        a, b = _image_pair(x, y)
         n, h, w = a.shape
         out = torch.empty(n, dtype=torch.float32, device=a.device)
         ws = _ssim_workspace(n, h, w, a.device)
@@ -306,10 +322,7 @@ def ssim(x, y):
 
 def ssim_u8(a, b):
     """The same on uint8 images that already are 0..255 (u = a / 255).  -> fp32 (N,), no gradient."""
-    a, b = _single_channel(a), _single_channel(b)
-    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
-        raise ValueError('uint8 images expected')
-    _need(a, b)
+    a, b = _u8_pair(a, b)
     n, h, w = a.shape
     out = torch.empty(n, dtype=torch.float32, device=a.device)
     ws = _ssim_workspace(n, h, w, a.device)
@@ -357,8 +370,7 @@ class MsSsimFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, weights):
-        a, b = _single_channel(x.detach()), _single_channel(y.detach().to(x.dtype))
-        _need(a, b)
+        a, b = _image_pair(x, y)
         n, h, w = a.shape
         levels, wts = _msssim_weights(weights)
         out = torch.empty(n, dtype=torch.float32, device=a.device)
@@ -413,10 +425,7 @@ def ms_ssim_terms(x, y, weights=None):
 
 def ms_ssim_u8(a, b, weights=None, return_terms=False):
     """ms_ssim on uint8 images that already are 0..255 (u = a / 255).  -> fp32 (N,), no gradient."""
-    a, b = _single_channel(a), _single_channel(b)
-    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
-        raise ValueError('uint8 images expected')
-    _need(a, b)
+    a, b = _u8_pair(a, b)
     n, h, w = a.shape
     levels, wts = _msssim_weights(weights)
     out = torch.empty(n, dtype=torch.float32, device=a.device)
@@ -465,10 +474,7 @@ class FocalFreqFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, alpha):
-        a, b = _single_channel(x.detach()), _single_channel(y.detach().to(x.dtype))
-        _need(a, b)
-        if a.shape != b.shape:
-            raise ValueError('x and y of one shape expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+        a, b = _image_pair(x, y)
         n, h, w = a.shape
         alpha = float(alpha)
         tab = ffl_tables(h, w, a.device)
@@ -517,12 +523,7 @@ def focal_freq_loss(x, y, alpha=1.0):
 
 def focal_freq_loss_u8(a, b, alpha=1.0):
     """focal_freq_loss on uint8 images that already are 0..255 (u = a / 255).  -> fp32 (N,), no gradient."""
-    a, b = _single_channel(a), _single_channel(b)
-    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
-        raise ValueError('uint8 images expected')
-    _need(a, b)
-    if a.shape != b.shape:
-        raise ValueError('a and b of one shape expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    a, b = _u8_pair(a, b)
     n, h, w = a.shape
     tab = ffl_tables(h, w, a.device)
     out = torch.empty(n, dtype=torch.float32, device=a.device)
@@ -562,11 +563,9 @@ class RegionLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, y, label, weights, norm):
-        a, b = _single_channel(x.detach()), _single_channel(y.detach().to(x.dtype))
+        a, b = _image_pair(x, y)
         lb = _region_label(label, a.shape[0])
-        if a.shape != b.shape:
-            raise ValueError('x and y of one shape expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
-        _need(a, b, lb, weights)
+        _need(lb, weights)
         n, h, w = a.shape
         ncls = weights.numel()
         stats = torch.empty(n, ncls, 3, dtype=torch.float64, device=a.device)
@@ -617,14 +616,10 @@ def region_loss(x, y, label, weights, norm='l1'):
 def region_stats_u8(a, b, label, ncls):
     """{count, sum |a - b|, sum (a - b)^2} per image and class of uint8 images that already are 0..255, by the label lookup of
     region_loss.  -> (N, ncls, 3) float64, every number exact; no gradient."""
-    a, b = _single_channel(a), _single_channel(b)
-    if a.dtype != torch.uint8 or b.dtype != torch.uint8:
-        raise ValueError('uint8 images expected')
     ncls = _region_ncls(ncls)
+    a, b = _u8_pair(a, b)
     lb = _region_label(label, a.shape[0])
-    if a.shape != b.shape:
-        raise ValueError('a and b of one shape expected, got %s and %s' % (tuple(a.shape), tuple(b.shape)))
-    _need(a, b, lb)
+    _need(lb)
     n, h, w = a.shape
     stats = torch.empty(n, ncls, 3, dtype=torch.float64, device=a.device)
     ws = _region_workspace(n, h, w, ncls, a.device)

@@ -20,6 +20,7 @@ from ._lib import LOSS_L1
 from .networks.base_network import compute_dtype_of
 from .networks.normalization import SegMap
 from .optim import FlatAdam
+from .quality import TERMS
 
 
 class Pix2PixModel(nn.Module):
@@ -31,13 +32,10 @@ class Pix2PixModel(nn.Module):
     def __init__(self, opt):
         super().__init__()
         self.opt = opt
-        if opt.isTrain and getattr(opt, 'lambda_msssim', 0):
-            # --lambda_msssim: five levels halve the image four times and the last one must still hold an 11 x 11 window
-            from .options import image_hw
-            h, w = image_hw(opt)
-            if min(h, w) < ops.msssim_min_size():
-                raise ValueError('--lambda_msssim: images of %d x %d are too small for five levels (H, W >= %d: the last level, %d x %d, must '
-                                 'hold an 11 x 11 window)' % (h, w, ops.msssim_min_size(), h >> 4, w >> 4))
+        # the image-quality terms of quality.TERMS whose training flag is set, in the table's order
+        quality_terms = [t for t in TERMS if opt.isTrain and getattr(opt, t.train_flag, 0)]
+        for t in quality_terms:
+            t.check(opt)                                     # (what can be refused before any network is built)
         self.cdtype = compute_dtype_of(opt)
         self.netG, self.netD, self.netE = self.initialize_networks(opt)
         self.netE.logvar_used = False        # (`logvar` enters no loss: pix2pix_model.py:271-305; see ConvEncoder.forward)
@@ -45,18 +43,11 @@ class Pix2PixModel(nn.Module):
         # trainer around each G / D step; None (always, outside a trainer's step): D sees its input as it is
         self.diffaug = diffaug.parse_policy(getattr(opt, 'diffaug', '') or '') if opt.isTrain else frozenset()
         self.diffaug_rows = None
-        # --lambda_region: the class weights as the fp32 device tensor s2e_region_loss_fwd reads, made once -- a captured
-        # step reads the same address at every replay; None (the flag absent): nothing is allocated
+        # what a term's step reads at a fixed address, made once and outside any graph capture (the region term's class weights, here;
+        # the DFT tables of the frequency term, in the ops' cache); a flag absent: nothing is allocated or launched
         self.region_w = None
-        if opt.isTrain and getattr(opt, 'lambda_region', 0):
-            from .options import parse_region_weights
-            self.region_w = torch.tensor(parse_region_weights(getattr(opt, 'region_weights', ''), opt.label_nc), dtype=torch.float32,
-                                         device=self.device())
-        # --lambda_ffl: the DFT tables of the image size, built once and outside any graph capture -- a captured step reads
-        # the cached tables at every replay; the flag absent: nothing is allocated or launched
-        if opt.isTrain and getattr(opt, 'lambda_ffl', 0) and self.device().type == 'cuda':
-            from .options import image_hw
-            ops.ffl_tables(*image_hw(opt), self.device())
+        for t in quality_terms:
+            t.prepare(self, opt)
         if opt.isTrain:
             self.criterionGAN = networks.GANLoss(opt.gan_mode, opt=opt)
             if not opt.no_vgg_loss:
@@ -225,27 +216,14 @@ class Pix2PixModel(nn.Module):
             l1 = ops.loss_sum(a, b, LOSS_L1, 1.0 / a.numel()).view(1)
             G_losses['L1/weighted'] = l1 * self.opt.lambda_l1
             self.add_to_loss_log('L1/raw', l1.detach())
-        if getattr(opt, 'lambda_ssim', 0):
-            # structural similarity of the un-augmented fake and the target (an extension): two launches, one in the backward
-            s = ops.ssim(fake_image, target_image).mean()
-            G_losses['SSIM/weighted'] = (opt.lambda_ssim * (1.0 - s)).view(1)
-            self.add_to_loss_log('SSIM/raw', s.detach())          # (the mean SSIM itself: higher is better)
-        if getattr(opt, 'lambda_msssim', 0):
-            # multi-scale structural similarity of the same pair (an extension): three launches, two in the backward
-            s = ops.ms_ssim(fake_image, target_image).mean()
-            G_losses['MSSSIM/weighted'] = (opt.lambda_msssim * (1.0 - s)).view(1)
-            self.add_to_loss_log('MSSSIM/raw', s.detach())        # (the mean MS-SSIM itself: higher is better)
-        if getattr(opt, 'lambda_region', 0):
-            # class-balanced error of the un-augmented fake against the target, keyed by the step's own label map (an
-            # extension): two launches, one in the backward
-            r, _ = ops.region_loss(fake_image, target_image, seg.label, self.region_w, getattr(opt, 'region_norm', 'l1'))
-            G_losses['region/weighted'] = (opt.lambda_region * r).view(1)
-            self.add_to_loss_log('region/raw', r.detach().view(1))
-        if getattr(opt, 'lambda_ffl', 0):
-            # focal frequency loss of the un-augmented fake against the target (an extension): three launches, two in the backward
-            f = ops.focal_freq_loss(fake_image, target_image, getattr(opt, 'ffl_alpha', 1.0)).mean()
-            G_losses['FFL/weighted'] = (opt.lambda_ffl * f).view(1)
-            self.add_to_loss_log('FFL/raw', f.detach())           # (the mean before lambda: lower is better)
+        for t in TERMS:
+            # the image-quality extensions, each on the un-augmented fake and the target: `<X>/weighted` = lambda * to_loss(raw) enters the
+            # loss, `<X>/raw` (the term itself, before lambda) the log
+            lam = getattr(opt, t.train_flag, 0)
+            if lam:
+                v = t.raw(self, fake_image, target_image, seg)
+                G_losses[t.loss_key] = (lam * t.to_loss(v)).view(1)
+                self.add_to_loss_log(t.log_key, v.detach().view(t.log_shape))
         if getattr(self.opt, 'lambda_openeds', 0):
             # pix2pix_model.py:206-210: the OpenEDS metric of the batch (per image; no gradient -- the reference's
             # `.int()` cuts the graph too), weighted into the logged loss

@@ -9,16 +9,22 @@ What differs from the reference: the generated batch never leaves the GPU before
 filename (h5 with h5py, else npz) and, with `--visuals`, the reference's fourth dataset `visualisation`: the side-by-side panels,
 built on the device too (seg2eye_amd/visualizer.py).  A `visualizer` handed to the constructor receives the
 statistics lines (`run(log=True)`) and the panels of `run_visual_validation`; without one neither happens (the reference builds
-its own Visualizer there; TensorBoard events are not built).  With `--val_ssim` every scored pair also gets its structural similarity
-(`s2e_ssim_u8` on the same 640 x 400 uint8 pair): `ssim/<dataset_key>/<mode>` in the statistics of `run` (the mean; higher is
-better) and one more dataset, `ssim` (float64, one per sample), in the error log; `--val_msssim` does the same with five-level MS-SSIM
-(`s2e_msssim_u8`): `msssim/<dataset_key>/<mode>` and the dataset `msssim`; `--val_ffl` with the focal frequency loss at alpha = 1
-(`s2e_ffl_u8`; lower is better): `ffl/<dataset_key>/<mode>`, printed `%.3e`, and the dataset `ffl`.  With `--val_regions` the same pair is also taken apart by
-label class (`s2e_region_stats_u8` with the batch's label map, looked up at [(r Hl) // 640, (c Wl) // 400]; DESIGN 3.16): per class c seen in
-a scored sample `region_mae/<dataset_key>/<mode>/<c>` = sum |d| / pixels and `region_rmse/<dataset_key>/<mode>/<c>` = sqrt(sum d^2 / pixels)
-over the scored samples, in grey levels, and the dataset `region` (samples, label_nc, 3) float64 = {pixels, sum |d|, sum d^2} in the error
-log.  The dataset is whatever `data.create_dataloader`
-yields (synthetic, or the OpenEDS H5 dataset) -- batches must carry `target_original` (N, 1, 640, 400) for validation."""
+its own Visualizer there; TensorBoard events are not built).
+
+The image-quality extensions (seg2eye_amd/quality.py: one record per term, walked in the table's order) all follow one pattern: under a
+term's `--val_*` flag every scored pair -- the same 640 x 400 uint8 pair the error saw -- also goes through the record's `score_u8`, the
+per-sample rows go to one more float64 dataset of the error log and to `tester.all_*`, and the record's `summarise` adds its keys to the
+statistics of `run`, printed in the record's format:
+  --val_ssim     `s2e_ssim_u8` (DESIGN 3.15; higher is better): dataset `ssim` (N,), `ssim/<dataset_key>/<mode>` = the mean, %.4f;
+  --val_msssim   five-level `s2e_msssim_u8` (DESIGN 3.17): dataset `msssim` (N,), `msssim/<dataset_key>/<mode>`, %.4f;
+  --val_regions  `s2e_region_stats_u8` with the batch's label map, looked up at [(r Hl) // 640, (c Wl) // 400] (DESIGN 3.16): dataset
+                 `region` (N, label_nc, 3) = {pixels, sum |d|, sum d^2}; per class c seen in a scored sample
+                 `region_mae/<dataset_key>/<mode>/<c>` = sum |d| / pixels and `region_rmse/<dataset_key>/<mode>/<c>` = sqrt(sum d^2 / pixels)
+                 over the scored samples, in grey levels, %.2f;
+  --val_ffl      `s2e_ffl_u8` at alpha = 1 (lower is better): dataset `ffl` (N,), `ffl/<dataset_key>/<mode>`, %.3e.
+
+The dataset is whatever `data.create_dataloader` yields (synthetic, or the OpenEDS H5 dataset) -- batches must carry `target_original`
+(N, 1, 640, 400) for validation."""
 import os
 import re
 from copy import deepcopy
@@ -30,6 +36,7 @@ from . import data as data_mod
 from .networks.loss import MSECalculator
 from .ops.preprocess import materialize
 from .postprocessor import ImageProcessor
+from .quality import TERMS
 from .visualizer import CAPTION_ROWS, visualize_sidebyside
 
 
@@ -45,17 +52,18 @@ class Tester:
         self.dataloader = data_mod.create_dataloader(self.opt)
         self.visualizer = visualizer
         self.is_validation = self.opt.dataset_key in ['validation', 'train']
-        self.val_ssim = bool(getattr(self.opt, 'val_ssim', False))
-        self.all_ssim = []                                   # --val_ssim: per-sample SSIM of the last run_validation, beside its errors
-        self.val_msssim = bool(getattr(self.opt, 'val_msssim', False))
-        self.all_msssim = []                                 # --val_msssim: per-sample MS-SSIM of the last run_validation
-        self.val_ffl = bool(getattr(self.opt, 'val_ffl', False))
-        self.all_ffl = []                                    # --val_ffl: per-sample focal frequency loss of the last run_validation
-        self.val_regions = bool(getattr(self.opt, 'val_regions', False))
-        self.all_regions = []                                # --val_regions: per-sample (label_nc, 3) float64 records of the last run_validation
+        self.terms = [t for t in TERMS if getattr(self.opt, t.val_flag, False)]     # the quality terms this Tester scores with
+        self._reset_scores()
         self.N = getattr(self.dataloader, 'N', len(self.dataloader) * self.opt.batchSize)
         self.results_dir = os.path.join(opt.checkpoints_dir, self.opt.name, self.opt.results_dir, self.opt.dataset_key)
         os.makedirs(self.results_dir, exist_ok=True)
+
+    def _reset_scores(self):
+        """`scores`: dataset name -> the per-sample rows of the last run_validation, beside its errors; the same lists are readable as
+        `all_ssim`, `all_msssim`, `all_regions`, `all_ffl` (empty without the term's flag)."""
+        self.scores = {t.dataset: [] for t in TERMS}
+        for t in TERMS:
+            setattr(self, t.all_attr, self.scores[t.dataset])
 
     def forward(self, model, data_i):
         """tester.py:44-47: (fake in [-1,1], fake resized to 640 x 400 as 0..255); both stay on the device."""
@@ -102,31 +110,20 @@ class Tester:
                'filename': np.zeros((self.N,), dtype='S13')}
         if getattr(self.opt, 'visuals', False):
             log['visualisation'] = np.zeros((self.N, 1, 320 + CAPTION_ROWS, 5 * 200), dtype=np.uint8)
-        if self.val_ssim:
-            log['ssim'] = np.zeros((self.N,), dtype=np.float64)
-        if self.val_msssim:
-            log['msssim'] = np.zeros((self.N,), dtype=np.float64)
-        if self.val_ffl:
-            log['ffl'] = np.zeros((self.N,), dtype=np.float64)
-        if self.val_regions:
-            log['region'] = np.zeros((self.N, self.opt.label_nc, 3), dtype=np.float64)
+        for t in self.terms:
+            log[t.dataset] = np.zeros((self.N,) + tuple(t.row_shape(self.opt)), dtype=t.dtype)
         return log
 
-    def _write_error_log_batch(self, error_log, data_i, i, errors, fake=None, ssim=None, regions=None, msssim=None, ffl=None):
-        """tester.py:76-91; the panels of a batch are normalised over that batch, as there."""
+    def _write_error_log_batch(self, error_log, data_i, i, errors, fake=None, scores=None):
+        """tester.py:76-91; the panels of a batch are normalised over that batch, as there.  scores: {dataset name: the batch's rows} of the
+        quality terms."""
         a = i * self.opt.batchSize
         b = min(a + len(errors), self.N)
         error_log['user'][a:b] = np.array(list(data_i['user']), dtype='S4')[:b - a]
         error_log['filename'][a:b] = np.array(list(data_i['filename']), dtype='S13')[:b - a]
         error_log['error'][a:b] = np.asarray(errors, dtype=np.float64)[:b - a]
-        if 'ssim' in error_log:
-            error_log['ssim'][a:b] = np.asarray(ssim, dtype=np.float64)[:b - a]
-        if 'msssim' in error_log:
-            error_log['msssim'][a:b] = np.asarray(msssim, dtype=np.float64)[:b - a]
-        if 'ffl' in error_log:
-            error_log['ffl'][a:b] = np.asarray(ffl, dtype=np.float64)[:b - a]
-        if 'region' in error_log:
-            error_log['region'][a:b] = np.asarray(regions, dtype=np.float64)[:b - a]
+        for k, v in (scores or {}).items():
+            error_log[k][a:b] = np.asarray(v, dtype=error_log[k].dtype)[:b - a]
         if 'visualisation' in error_log:
             visuals = visualize_sidebyside({**data_i, 'fake': fake}, error_list=errors)
             error_log['visualisation'][a:b] = np.stack(list(visuals.values()))[:b - a]
@@ -150,10 +147,7 @@ class Tester:
         print('write error log: %s' % write_error_log)
         error_log = self._prepare_error_log() if write_error_log else None
         all_errors, counter = [], 0
-        self.all_ssim = []
-        self.all_msssim = []
-        self.all_ffl = []
-        self.all_regions = []
+        self._reset_scores()
         for i, data_i in enumerate(generator):
             data_i = materialize(data_i, self.opt, model.device())          # (--device_preprocess: raw frames -> the batch contract)
             counter += data_i['label'].shape[0]
@@ -164,29 +158,12 @@ class Tester:
                 print('Error so far: %s' % (np.sum(all_errors) / len(all_errors) * 1471))
             errors, fake, fake_resized, target = self.run_batch(data_i, model)
             all_errors += list(errors)
-            ssim = None
-            if self.val_ssim:                                # the same uint8 pair the error saw
-                from . import ops
-                ssim = ops.ssim_u8(fake_resized, target).cpu().numpy()
-                self.all_ssim += list(ssim)
-            msssim = None
-            if self.val_msssim:                              # the same pair, five levels
-                from . import ops
-                msssim = ops.ms_ssim_u8(fake_resized, target).cpu().numpy()
-                self.all_msssim += list(msssim)
-            ffl = None
-            if self.val_ffl:                                 # the same pair's spectra, alpha = 1
-                from . import ops
-                ffl = ops.focal_freq_loss_u8(fake_resized, target, 1.0).cpu().numpy()
-                self.all_ffl += list(ffl)
-            regions = None
-            if self.val_regions:                             # the same pair again, keyed by the batch's label map
-                from . import ops
-                label = torch.as_tensor(data_i['label']).to(fake_resized.device).to(torch.uint8)
-                regions = ops.region_stats_u8(fake_resized, target, label.unsqueeze(0) if label.dim() == 2 else label, self.opt.label_nc).cpu().numpy()
-                self.all_regions += list(regions)
+            scores = {}
+            for t in self.terms:                             # the same uint8 pair the error saw
+                scores[t.dataset] = t.score_u8(fake_resized, target, data_i, self.opt)
+                self.scores[t.dataset] += list(scores[t.dataset])
             if error_log is not None:
-                self._write_error_log_batch(error_log, data_i, i, errors, fake, ssim, regions, msssim, ffl)
+                self._write_error_log_batch(error_log, data_i, i, errors, fake, scores)
         if error_log is not None:
             print('error log: %s' % self._close_error_log(error_log))
         return all_errors
@@ -196,7 +173,8 @@ class Tester:
         print('------------------')
         print('Error calculated on %d / %d samples' % (len(all_errors), self.N))
         for k in sorted(errors_dict):
-            print(('  %s, %.4f' if k.startswith(('ssim/', 'msssim/')) else '  %s, %.3e' if k.startswith('ffl/') else '  %s, %.2f') % (k, errors_dict[k]))
+            fmt = next((t.fmt for t in TERMS if k.startswith(t.name)), '%.2f')      # a term's statistics in its format, the rest as the error
+            print(('  %s, ' + fmt) % (k, errors_dict[k]))
         print('  dataset_key: %s, model: %s, epoch: %s, n_steps: %s' % (self.opt.dataset_key, self.opt.name, epoch, n_steps))
 
     def run_visual_validation(self, model, mode, epoch, n_steps, limit):
@@ -238,18 +216,8 @@ class Tester:
         generator = self.get_iterator(self.dataloader, indices=self._get_validation_indices(mode, limit))
         all_errors = self.run_validation(model, generator, limit=limit, write_error_log=write_error_log)
         errors_dict = MSECalculator.calculate_error_statistics(all_errors, mode=mode, dataset_key=self.opt.dataset_key)
-        if self.val_ssim:
-            errors_dict['ssim/%s/%s' % (self.opt.dataset_key, mode)] = float(np.mean(np.asarray(self.all_ssim, dtype=np.float64)))
-        if self.val_msssim:
-            errors_dict['msssim/%s/%s' % (self.opt.dataset_key, mode)] = float(np.mean(np.asarray(self.all_msssim, dtype=np.float64)))
-        if self.val_ffl:
-            errors_dict['ffl/%s/%s' % (self.opt.dataset_key, mode)] = float(np.mean(np.asarray(self.all_ffl, dtype=np.float64)))
-        if self.val_regions and self.all_regions:
-            tot = np.sum(np.asarray(self.all_regions, dtype=np.float64), axis=0)                   # (label_nc, 3) over the scored samples
-            for c in range(tot.shape[0]):
-                if tot[c, 0] > 0:
-                    errors_dict['region_mae/%s/%s/%d' % (self.opt.dataset_key, mode, c)] = float(tot[c, 1] / tot[c, 0])
-                    errors_dict['region_rmse/%s/%s/%d' % (self.opt.dataset_key, mode, c)] = float(np.sqrt(tot[c, 2] / tot[c, 0]))
+        for t in self.terms:
+            errors_dict.update(t.summarise(self.scores[t.dataset], self.opt.dataset_key, mode))
         self.print_results(all_errors, errors_dict, epoch, n_steps)
         if log and self.visualizer is not None:
             self.log_visualizer(errors_dict, epoch, n_steps)

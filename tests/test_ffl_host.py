@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import _ffl_ref as R
+from _quality_harness import check_error_table
 
 F32, BF16, BAD = 0, 1, 7
 P = 4096                                                      # a dummy non-null pointer: must never reach a kernel
@@ -286,16 +287,9 @@ def test_ffl_entry_points_reject_bad_calls_before_any_launch():
     if torch.cuda.is_available():
         pytest.skip('dummy pointers: host-only by construction')
     from seg2eye_amd import _lib
-    L = _lib.lib()
     assert (_lib.S2E_BF16, _lib.S2E_F32) == (BF16, F32)
     for name, table in _error_tables():
-        wrong = []
-        for args, code, text in table:
-            rc = getattr(L, name)(*args)
-            got = (rc, L.s2e_last_error().decode() if rc else '')
-            if got != (code, text):
-                wrong.append((got, (code, text)))
-        assert not wrong, wrong
+        check_error_table(name, table)
     with pytest.raises(_lib.Seg2EyeHipError, match='s2e_ffl_fwd failed'):
         _lib.call.s2e_ffl_fwd(*_fwd(x=None))
 

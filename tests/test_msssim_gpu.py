@@ -50,8 +50,6 @@ The kernels take their moments about each tile's first pixel at every level, so 
 (measured on an MI355X in fp32: score within 1.3e-7 and per-level means within 3.7e-7 in every case; the gradient within 5.2e-6 of the
 image's largest on copy, smooth, split and neg inputs, 4.3e-5 on bright-flat ones)."""
 import functools
-import glob
-import os
 
 import numpy as np
 import pytest
@@ -60,6 +58,7 @@ import torch.nn.functional as F
 
 import _msssim_ref as M
 import _ssim_ref as R
+from _quality_harness import PARENT_LOSS_KEYS, batch as _batch, load_log as _load_log, trainer as _trainer
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -269,38 +268,6 @@ def test_the_op_refuses_what_the_library_refuses():
 
 
 # ------------------------------------------------------------------------------------------------ the generator's loss term
-PARENT_LOSS_KEYS = {'GAN', 'GAN_Feat', 'D/Fake', 'D/real'}     # the step's losses with no extension flag set, as on the parent commit
-
-
-def _opt(**kw):
-    from seg2eye_amd.options import default_opt
-    kw.setdefault('gpu_ids', [0])
-    kw.setdefault('compute_dtype', 'fp32')
-    return default_opt(ngf=8, ndf=8, crop_size=256, aspect_ratio=1.0, batchSize=2, **kw)
-
-
-@functools.lru_cache(maxsize=None)
-def _batch(seed=21):
-    from seg2eye_amd import synthetic as syn
-    b = syn.make_batch(2, 256, 256, seed=seed)
-    return {'label': torch.from_numpy(b['label']), 'style_image': torch.from_numpy(b['style_image']), 'target': torch.from_numpy(b['target'])}
-
-
-def _trainer(**kw):
-    """A trainer on the hash-filled weights (the same for every trainer of this file)."""
-    from seg2eye_amd import synthetic as syn
-    from seg2eye_amd.pix2pix_trainer import Pix2PixTrainer
-    tr = Pix2PixTrainer(_opt(**kw))
-    m = tr.pix2pix_model
-    with torch.no_grad():
-        for net in (m.netG, m.netD, m.netE):
-            sd = net.state_dict()
-            filled = syn.fill_state_dict([(k, tuple(v.shape)) for k, v in sd.items()])
-            for k, v in sd.items():
-                v.copy_(torch.from_numpy(filled[k]))
-    return tr
-
-
 def test_generator_loss_term_matches_the_restatement_and_reaches_netG():
     """ngf = ndf = 8, batch 2, fp32, at 256 x 256: MSSSIM/weighted = 3 (1 - mean MS-SSIM(fake, target)) of the fake the step returns, within
     the bound of the op test (times the weight); the backward runs and moves netG's gradient; without the flag the keys do not exist and
@@ -362,16 +329,6 @@ def test_hip_graph_replays_follow_the_eager_msssim_log():
 
 
 # ------------------------------------------------------------------------------------------------ the Tester
-def _load_log(tester):
-    logs = glob.glob(os.path.join(tester.results_dir, 'error_log_validation.*'))
-    assert len(logs) == 1, logs
-    if logs[0].endswith('.npz'):
-        return dict(np.load(logs[0]))
-    import h5py
-    with h5py.File(logs[0], 'r') as f:
-        return {k: np.asarray(v) for k, v in f.items()}
-
-
 def test_tester_scores_msssim_only_under_the_flag(tmp_path):
     from seg2eye_amd.options import parse
     from seg2eye_amd.pix2pix_model import Pix2PixModel

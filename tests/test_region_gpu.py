@@ -23,14 +23,13 @@ Measured on an MI355X (largest over the label plans and norms of a shape; relati
     2x256x256    0.0e+00        3.4e-08    4.8e-08    1.4e-07         3.7e-03         3.4e-08, 5.9e-08
 """
 import functools
-import glob
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import _region_ref as R
+from _quality_harness import batch as _batch, load_log as _load_log, trainer as _trainer
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -185,35 +184,6 @@ def test_stats_u8_are_bit_equal_to_the_restatement(shape, lshape):
 
 
 # ------------------------------------------------------------------------------------------------ the generator's loss term
-def _opt(**kw):
-    from seg2eye_amd.options import default_opt
-    kw.setdefault('gpu_ids', [0])
-    kw.setdefault('compute_dtype', 'fp32')
-    return default_opt(ngf=8, ndf=8, crop_size=256, aspect_ratio=1.0, batchSize=2, **kw)
-
-
-@functools.lru_cache(maxsize=None)
-def _batch(seed=21):
-    from seg2eye_amd import synthetic as syn
-    b = syn.make_batch(2, 256, 256, seed=seed)
-    return {'label': torch.from_numpy(b['label']), 'style_image': torch.from_numpy(b['style_image']), 'target': torch.from_numpy(b['target'])}
-
-
-def _trainer(**kw):
-    """A trainer on the hash-filled weights (the same for every trainer of this file)."""
-    from seg2eye_amd import synthetic as syn
-    from seg2eye_amd.pix2pix_trainer import Pix2PixTrainer
-    tr = Pix2PixTrainer(_opt(**kw))
-    m = tr.pix2pix_model
-    with torch.no_grad():
-        for net in (m.netG, m.netD, m.netE):
-            sd = net.state_dict()
-            filled = syn.fill_state_dict([(k, tuple(v.shape)) for k, v in sd.items()])
-            for k, v in sd.items():
-                v.copy_(torch.from_numpy(filled[k]))
-    return tr
-
-
 def test_generator_loss_term_matches_the_restatement_and_reaches_netG():
     """ngf = ndf = 8, batch 2, fp32, 256 x 256: region/weighted = 3 * the restatement's loss on the fake the step returns and the batch's
     label; the two keys exist only under the flag; netG's gradient moves by at least 10 x the run-to-run noise of two runs without the term."""
@@ -269,16 +239,6 @@ def test_hip_graph_replays_follow_the_eager_region_log():
 
 
 # ------------------------------------------------------------------------------------------------ the Tester
-def _load_log(tester):
-    logs = glob.glob(os.path.join(tester.results_dir, 'error_log_validation.*'))
-    assert len(logs) == 1, logs
-    if logs[0].endswith('.npz'):
-        return dict(np.load(logs[0]))
-    import h5py
-    with h5py.File(logs[0], 'r') as f:
-        return {k: np.asarray(v) for k, v in f.items()}
-
-
 def test_tester_takes_the_error_apart_only_under_the_flag(tmp_path):
     from seg2eye_amd.options import parse
     from seg2eye_amd.pix2pix_model import Pix2PixModel

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import _region_ref as R
+from _quality_harness import check_error_table
 
 F32, BF16, BAD = 0, 1, 7
 L1, L2 = 0, 1
@@ -214,15 +215,9 @@ def test_region_entry_points_reject_bad_calls_before_any_launch():
     if torch.cuda.is_available():
         pytest.skip('dummy pointers: host-only by construction')
     from seg2eye_amd import _lib
-    L = _lib.lib()
     assert (_lib.S2E_BF16, _lib.S2E_F32, _lib.REGION_L1, _lib.REGION_L2) == (BF16, F32, L1, L2)
     for name, table in (('s2e_region_loss_fwd', FWD_ERRORS), ('s2e_region_stats_u8', U8_ERRORS), ('s2e_region_loss_bwd', BWD_ERRORS)):
-        got = []
-        for args, _, _ in table:
-            rc = getattr(L, name)(*args)
-            got.append((args, rc, L.s2e_last_error().decode() if rc else ''))
-        wrong = [(g, w) for g, w in zip(got, table) if g != w]
-        assert not wrong, wrong
+        check_error_table(name, table)
     with pytest.raises(_lib.Seg2EyeHipError, match='s2e_region_loss_fwd failed'):
         _lib.call.s2e_region_loss_fwd(*FWD_ERRORS[0][0])
 

@@ -25,6 +25,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _bench_legs import count_kernels, time_legs, write_json  # noqa: E402  (beside this file)
 
 
 def torch_ffl(x, y, alpha=1.0):
@@ -41,21 +42,6 @@ def torch_ffl(x, y, alpha=1.0):
     if W % 2 == 0:
         m[W // 2] = 1.0
     return (w * dist * m).sum(dim=(1, 2)) / (H * W)
-
-
-def count_kernels(fn):
-    """Device kernels one call of fn launches, by torch.profiler; None when it cannot tell."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA') and 'memcpy' not in e.name.lower()
-                and 'memset' not in e.name.lower())
-        return n or None
-    except Exception:                                        # noqa: BLE001 -- a count, not a measurement: the timings stand without it
-        return None
 
 
 def main():
@@ -111,43 +97,22 @@ def main():
     legs['u8/ffl_u8.fwd'] = lambda: ops.focal_freq_loss_u8(a8, b8, alpha)
     legs['u8/torch_u8.fwd'] = lambda: torch_ffl(u8f(a8), u8f(b8), alpha)
     launches.update({'u8/ffl_u8.fwd': 3, 'u8/torch_u8.fwd': None})
-    for f in legs.values():                                  # warm-up: code objects loaded, allocator blocks cached, clocks up
-        for _ in range(5):
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, f in legs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.launches):
-                f()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1) / a.launches)
+    timed = time_legs(legs, a.rounds, a.launches)
     out = {'device': torch.cuda.get_device_name(0), 'arch': torch.cuda.get_device_properties(0).gcnArchName, 'batch': n, 'size': H, 'alpha': alpha,
            'rounds': a.rounds, 'launches_per_round': a.launches, 'u8_shape': [n, 640, 400]}
-    for k, xs in ms.items():
-        xs = sorted(xs)
+    for k, t in timed.items():
         grp, leg = k.split('/')
-        out.setdefault(grp, dict(info.get(grp, {})))[leg] = {'us_median': round(1e3 * xs[len(xs) // 2], 2), 'us_min': round(1e3 * xs[0], 2),
-                                                              'us_max': round(1e3 * xs[-1], 2), 'kernel_launches': launches[k]}
+        out.setdefault(grp, dict(info.get(grp, {})))[leg] = {**t, 'kernel_launches': launches[k]}
     for name in info:
         med = lambda leg: out[name][leg]['us_median']
         out[name]['fwd_bwd_us'] = {'ffl': round(med('ffl.fwd') + med('ffl.bwd'), 2), 'torch': round(med('torch.fwd') + med('torch.bwd'), 2)}
-
-    def write():
-        if a.out:
-            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-            with open(a.out, 'w') as f:
-                f.write(json.dumps(out, indent=1) + '\n')
-    write()                                                  # the timings are on disk before the profiler is touched
+    write_json(out, a.out)                                   # the timings are on disk before the profiler is touched
     if not a.no_count:
         for k in legs:
             if launches[k] is None:
                 grp, leg = k.split('/')
                 out[grp][leg]['kernel_launches'] = count_kernels(legs[k])
-        write()
+        write_json(out, a.out)
     print(json.dumps(out))
 
 

@@ -23,6 +23,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _bench_legs import count_kernels, time_legs, write_json  # noqa: E402  (beside this file)
 
 WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
 
@@ -45,21 +46,6 @@ def torch_ms_ssim(x, y, weights=WEIGHTS):
             u, v = F.avg_pool2d(u, 2), F.avg_pool2d(v, 2)
     w = torch.tensor(weights, dtype=torch.float32, device=x.device)
     return (torch.stack(terms, dim=1).clamp(min=1e-3) ** w).prod(dim=1)
-
-
-def count_kernels(fn):
-    """Device kernels one call of fn launches, by torch.profiler; None when it cannot tell."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA') and 'memcpy' not in e.name.lower()
-                and 'memset' not in e.name.lower())
-        return n or None
-    except Exception:                                        # noqa: BLE001 -- a count, not a measurement: the timings stand without it
-        return None
 
 
 def main():
@@ -106,41 +92,20 @@ def main():
         'torch.bwd': torch_bwd,
     }
     launches = {'msssim.fwd': 3, 'msssim.fwd_nomaps': 3, 'msssim.bwd': 2, 'msssim_u8.fwd': 3, 'torch.fwd': None, 'torch.bwd': None}
-    for f in legs.values():                                  # warm-up: code objects loaded, allocator blocks cached, clocks up
-        for _ in range(5):
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, f in legs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.launches):
-                f()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1) / a.launches)
+    timed = time_legs(legs, a.rounds, a.launches)
     err = float((ops.ms_ssim(x, y) - torch_ms_ssim(x, y)).abs().max())
     out = {'device': torch.cuda.get_device_name(0), 'arch': torch.cuda.get_device_properties(0).gcnArchName, 'batch': n, 'size': H,
            'dtype': a.dtype, 'levels': levels, 'rounds': a.rounds, 'launches_per_round': a.launches, 'maps_bytes': maps.numel() * 4,
            'pyramid_bytes': pyr.numel() * 4, 'max_abs_diff_msssim_vs_torch_fp32': err}
-    for k, xs in ms.items():
-        xs = sorted(xs)
-        out[k] = {'us_median': round(1e3 * xs[len(xs) // 2], 2), 'us_min': round(1e3 * xs[0], 2), 'us_max': round(1e3 * xs[-1], 2),
-                  'kernel_launches': launches[k]}
+    for k, t in timed.items():
+        out[k] = {**t, 'kernel_launches': launches[k]}
     med = lambda k: out[k]['us_median']
     out['fwd_bwd_us'] = {'msssim': round(med('msssim.fwd') + med('msssim.bwd'), 2), 'torch': round(med('torch.fwd') + med('torch.bwd'), 2)}
-
-    def write():
-        if a.out:
-            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-            with open(a.out, 'w') as f:
-                f.write(json.dumps(out, indent=1) + '\n')
-    write()                                                  # the timings are on disk before the profiler is touched
+    write_json(out, a.out)                                   # the timings are on disk before the profiler is touched
     if not a.no_count:
         for k in ('torch.fwd', 'torch.bwd'):
             out[k]['kernel_launches'] = count_kernels(legs[k])
-        write()
+        write_json(out, a.out)
     print(json.dumps(out))
 
 

@@ -23,6 +23,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from _bench_legs import count_kernels, time_legs, write_json  # noqa: E402  (beside this file)
 
 
 def torch_region_loss(x, y, label, w, norm):
@@ -51,21 +52,6 @@ def torch_region_stats_u8(a, b, label, ncls):
         m = (l == c).double()
         rows.append(torch.stack([m.sum(dim=(1, 2)), (d.abs() * m).sum(dim=(1, 2)), (d * d * m).sum(dim=(1, 2))], dim=1))
     return torch.stack(rows, dim=1)
-
-
-def count_kernels(fn):
-    """Device kernels one call of fn launches, by torch.profiler; None when it cannot tell."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA') and 'memcpy' not in e.name.lower()
-                and 'memset' not in e.name.lower())
-        return n or None
-    except Exception:                                        # noqa: BLE001 -- a count, not a measurement: the timings stand without it
-        return None
 
 
 def main():
@@ -113,43 +99,22 @@ def main():
         'torch_u8.fwd': lambda: torch_region_stats_u8(a8, b8, label, ncls),
     }
     launches = {'region.fwd': 2, 'region.bwd': 1, 'region_u8.fwd': 2, 'torch.fwd': None, 'torch.bwd': None, 'torch_u8.fwd': None}
-    for f in legs.values():                                  # warm-up: code objects loaded, allocator blocks cached, clocks up
-        for _ in range(5):
-            f()
-    torch.cuda.synchronize()
-    ms = {k: [] for k in legs}
-    for _ in range(a.rounds):
-        for k, f in legs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(a.launches):
-                f()
-            e1.record()
-            e1.synchronize()
-            ms[k].append(e0.elapsed_time(e1) / a.launches)
+    timed = time_legs(legs, a.rounds, a.launches)
     ours, theirs = ops.region_loss(x, y, label, w, a.norm)[0], torch_region_loss(x, y, label, w, a.norm)
     same_u8 = bool(torch.equal(ops.region_stats_u8(a8, b8, label, ncls), torch_region_stats_u8(a8, b8, label, ncls)))
     out = {'device': torch.cuda.get_device_name(0), 'arch': torch.cuda.get_device_properties(0).gcnArchName, 'batch': n, 'size': H,
            'dtype': a.dtype, 'norm': a.norm, 'classes': ncls, 'rounds': a.rounds, 'launches_per_round': a.launches,
            'bytes_moved_fwd': 2 * x.numel() * x.element_size() + label.numel(),
            'rel_diff_loss_vs_torch': float((ours - theirs).abs() / theirs.abs()), 'stats_u8_equal_torch': same_u8}
-    for k, xs_ in ms.items():
-        xs_ = sorted(xs_)
-        out[k] = {'us_median': round(1e3 * xs_[len(xs_) // 2], 2), 'us_min': round(1e3 * xs_[0], 2), 'us_max': round(1e3 * xs_[-1], 2),
-                  'kernel_launches': launches[k]}
+    for k, t in timed.items():
+        out[k] = {**t, 'kernel_launches': launches[k]}
     med = lambda k: out[k]['us_median']
     out['fwd_bwd_us'] = {'region': round(med('region.fwd') + med('region.bwd'), 2), 'torch': round(med('torch.fwd') + med('torch.bwd'), 2)}
-
-    def write():
-        if a.out:
-            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-            with open(a.out, 'w') as f:
-                f.write(json.dumps(out, indent=1) + '\n')
-    write()                                                  # the timings are on disk before the profiler is touched
+    write_json(out, a.out)                                   # the timings are on disk before the profiler is touched
     if not a.no_count:
         for k in ('torch.fwd', 'torch.bwd', 'torch_u8.fwd'):
             out[k]['kernel_launches'] = count_kernels(legs[k])
-        write()
+        write_json(out, a.out)
     print(json.dumps(out))
 
 
