@@ -751,6 +751,29 @@ int s2e_region_stats_u8(const uint8_t* a, const uint8_t* b, const uint8_t* label
 int s2e_region_loss_bwd(int dtype, const void* x, const void* y, const uint8_t* label, const float* coef, const float* gloss,
                         int N, int H, int W, int Hl, int Wl, int ncls, int norm, void* dx, void* stream);
 
+/* ------------------------------------------------------------------ style reference rankings
+ * The reference's --style_ref file ranks, for every target mask, a person's style frames "by their L2 distance to the target
+ * segmentation mask" (refinenet/README.md); it ships no program that does so.  Two integer entry points, exact and run-to-run identical.
+ *   s2e_mask_dist: a (M, pitch) and b (K, pitch) uint8 are rows of label maps of P <= pitch bytes; bytes P .. pitch-1 of a row may
+ *       hold anything and influence nothing.  dist (M, K) int32 is OVERWRITTEN with
+ *         S2E_RANK_L2        sum_p (a[m][p] - b[k][p])^2           (as sum a^2 + sum b^2 - 2 sum a b, the product on v_mfma_i32_16x16x64_i8)
+ *         S2E_RANK_MISMATCH  #{p : a[m][p] != b[k][p]}             (as P - sum_c sum_p [a = c][b = c], c < ncls)
+ *       Two launches: dist is zeroed, then one kernel whose workgroups split the pixel axis and add their partial tiles with
+ *       int32 atomicAdd (associative: any order gives the same bits).  A byte >= ncls (>= 128 for l2) in the data gives an unspecified
+ *       distance; nothing is read or written out of bounds.
+ *       Before any launch, in this order: S2E_ERR_ARG on a null pointer, an unknown metric, M, K or P < 1, pitch < P, then a, b or
+ *       pitch not a multiple of 16 bytes (dist: of 4); S2E_ERR_UNSUPPORTED on ncls outside 1..128 (l2) or 1..16 (mismatch), then
+ *       (ncls-1)^2 P > 2^31 - 1 or P > 2^31 - 1, then M or K above 65535 * 64.
+ *   s2e_rank_topk: for every row of dist (M, K) int32 the min(k, K') candidates of smallest (distance, index) -- distance ascending,
+ *       ties to the lower index: one total order -- into idx (M, k) and val (M, k) int32; unused slots hold -1.  exclude: NULL, or (M,)
+ *       int32 naming one candidate per row that is not returned (a value outside 0..K-1 names none); K' counts the rest.  One launch,
+ *       one workgroup per row, the keys sorted in LDS: K <= s2e_rank_topk_max_candidates() (above it: rank chunks, then the winners).
+ *       S2E_ERR_ARG on a null dist, idx or val, then M, K or k < 1; S2E_ERR_UNSUPPORTED on K above the limit. */
+enum { S2E_RANK_L2 = 0, S2E_RANK_MISMATCH = 1 };
+int s2e_mask_dist(const uint8_t* a, const uint8_t* b, int M, int K, long P, long pitch, int ncls, int metric, int32_t* dist, void* stream);
+int s2e_rank_topk_max_candidates(void);
+int s2e_rank_topk(const int32_t* dist, int M, int K, int k, const int32_t* exclude, int32_t* idx, int32_t* val, void* stream);
+
 /* ------------------------------------------------------------------ side-by-side validation panels
  * The reference's visualize_sidebyside (util/visualizer.py:131-166) for a batch of n samples, as three launches on the caller's
  * stream with no host synchronisation between them: out[i] = [ style | label | target_original | fake | heat ], five h x w cells of

@@ -21,6 +21,7 @@ NORM_SPADE_STYLE, NORM_PLAIN_IN, NORM_SPADE_STYLE_BATCH = 0, 1, 2
 NORM_ACCUMULATE_DX = 0x100
 LOSS_NEG_MEAN, LOSS_HINGE_REAL, LOSS_HINGE_FAKE, LOSS_L1, LOSS_L1_NANGRAD = 0, 1, 2, 3, 4
 REGION_L1, REGION_L2 = 0, 1
+RANK_L2, RANK_MISMATCH = 0, 1
 
 
 class ConvDesc(C.Structure):
@@ -191,6 +192,9 @@ SIGNATURES = {
     's2e_region_loss_fwd': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     's2e_region_stats_u8': (STATUS, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
     's2e_region_loss_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    's2e_mask_dist': (STATUS, [_vp, _vp, _i, _i, _l, _l, _i, _i, _vp, _vp]),
+    's2e_rank_topk_max_candidates': (VALUE, []),
+    's2e_rank_topk': (STATUS, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     's2e_bilinear_resize_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_bilinear_resize_bwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_upsample2x_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -12,6 +12,7 @@ Built: the reference's training recipe -- `--preprocess_mode fixed` (resize to c
 cv2.INTER_NEAREST for masks, PIL bicubic for images), ToTensor + Normalize(0.5, 0.5) -> [-1, 1], horizontal flip
 augmentation, the train/validation vs test key sets, style sampling `random` / `first` / `ref` / `ref_random<N>`,
 `target_original`, `get_particular`, `get_validation_indices`, `get_random_indices`.  Other preprocess modes raise.
+The ranking the `ref` modes read (`--style_ref`, or `style_refs=`) is written by seg2eye_amd/style_rank.py.
 cv2 is not in this image: its nearest-neighbour resize is restated by its rule (source index = floor(dst * src / dst)).
 
 `--device_preprocess`: `__getitem__` makes the same random draws in the same order but returns the RAW 640 x 400
@@ -82,6 +83,9 @@ class OpenEDSDataset(torch.utils.data.Dataset):
         if store is None:
             self._path = opt.dataroot
         self.style_image_refs = style_refs
+        if style_refs is None and 'ref' in opt.style_sample_method and str(getattr(opt, 'style_ref', '')).endswith('.npz'):
+            from .style_rank import load_refs                    # the ranking style_rank.save_refs wrote without h5py
+            self.style_image_refs = load_refs(opt.style_ref)
         self.rng = rng or np.random
         h5 = self._h5()
         self.user_ids = list(h5.keys())
