@@ -286,8 +286,13 @@ int s2e_modulate_fwd(int dtype, int mode, const void* x, const void* gb, const f
  * "need never exist in HBM").  gamma_out: NULL (no-grad forward), or (N,H,W,C): gamma is stored for s2e_modulate_bwd's
  * gamma-only form (its `out` argument).  actv (N,H,W,nh), x / out (N,H,W,C) NHWC; stats (N,C,2); style / style_ld as s2e_modulate_fwd.
  * Taken shapes (s2e_spade_conv_modulate_supported != 0): C % 64 == 0, nh a multiple of the 128-byte K row, enough
- * 256-pixel x 64-channel tiles to fill the chip (flags & 1: any tile count -- tests).  Other shapes return
- * S2E_ERR_UNSUPPORTED: run s2e_conv2d + s2e_modulate_fwd. */
+ * 256-pixel x 64-channel tiles to fill the chip (S2E_SPADE_ANY_TILES: any tile count -- tests).  Other shapes return
+ * S2E_ERR_UNSUPPORTED: run s2e_conv2d + s2e_modulate_fwd.
+ * flags, of every entry point of the fused launch and of the host functions in front of them (ops.spade_style_fused): */
+#define S2E_SPADE_ANY_TILES 1   /* the fused launch at any tile count (tests; the duo kernel leaves such a launch to conv_patch.hip) */
+#define S2E_SPADE_DENSE     2   /* the dense launch whatever the label map; read by the host only, the library never sees it matter */
+#define S2E_SPADE_ANY_RECTS 4   /* the label-sparse form at any rectangle count; read by the host only */
+#define S2E_SPADE_X_HALF    8   /* x is the tensor BEFORE the nearest 2x upsampling: (N, H/2, W/2, C), see below */
 int s2e_spade_conv_modulate_supported(int dtype, int N, int H, int W, int C, int nh, int flags);
 int s2e_spade_conv_modulate(int dtype, const void* actv, const void* w_packed, const float* bias, const void* x,
                             const float* stats, const float* style, int style_ld, void* out, void* gamma_out,
@@ -315,7 +320,7 @@ int s2e_spade_conv_modulate(int dtype, const void* actv, const void* w_packed, c
  *   (caller: all-reduce sum over samples of S0, S1 across the replicas and fold the difference into ws[0,:,0:2])
  *   stage 2: coefficients + dx, with the normalisation count batch_count (= world * N * HW; 0 = N * HW) in BATCH mode.
  * x_up_w != 0 (`out` given, stage 0, per-sample statistics, even H and W): x is (N, H/2, W/2, C) with W = x_up_w -- the generator's
- *   nearest 2x upsampling in front of the block folded into the read of x, as flags & 8 does in the forward launches; g, gamma, out,
+ *   nearest 2x upsampling in front of the block folded into the read of x, as S2E_SPADE_X_HALF does in the forward launches; g, gamma, out,
  *   dx, dgb are at full resolution -- unless dx_quad != 0 (SPADE_STYLE mode): then dx (and dx_add) is (N, H/2, W/2, C), the gradient
  *   w.r.t. the half-resolution x itself (each element the sum over the 2 x 2 pixels it was replicated to: the upsampling's
  *   backward folded in). */
@@ -385,7 +390,7 @@ int s2e_wgrad_batch(int dtype, const s2e_wgrad_batch_job* jobs, int n_jobs, void
  *                                 w_sh fp32 (nh, ncls, 3, 3), nh <= 128; w_packed as the conv launches take it.
  *   s2e_spade_modulate_uniform  : the modulation of the rectangles uni_list[0 .. counts[1]) with gamma | beta from that table.
  * Together the two launches write every pixel of out (and gamma_out) exactly once.
- * flags & 8 of the conv launches / x_up of the uniform one: x is (N, H/2, W/2, C) -- the nearest 2x upsampling that precedes the
+ * S2E_SPADE_X_HALF of the conv launches / x_up of the uniform one: x is (N, H/2, W/2, C) -- the nearest 2x upsampling that precedes the
  * block in the generator (generator.py:77-92) is folded into the read of x, the upsampled tensor is never read (H, W even;
  * out and gamma_out are at full resolution). */
 int s2e_spade_conv_modulate_rect(int dtype, int N, int H, int W, int C, int nh, int flags, int* tw, int* th);

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('S2E_LIB_PATH') or os.path.join(_HERE, 'lib', 'libseg2
 
 S2E_F32, S2E_BF16 = 0, 1
 UNI_REPLICAS = 16           # S2E_UNI_REPLICAS of include/seg2eye_hip.h
+SPADE_ANY_TILES, SPADE_DENSE, SPADE_ANY_RECTS, SPADE_X_HALF = 1, 2, 4, 8     # S2E_SPADE_* of include/seg2eye_hip.h: the fused launch's flags
 ACT_NONE, ACT_LRELU, ACT_TANH = 0, 1, 2
 AUX_NONE, AUX_RELU_MASK, AUX_LRELU_GRAD = 0, 1, 2
 NORM_SPADE_STYLE, NORM_PLAIN_IN, NORM_SPADE_STYLE_BATCH = 0, 1, 2

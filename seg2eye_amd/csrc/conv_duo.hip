@@ -866,7 +866,7 @@ int s2e_spade_conv_modulate_duo(int dtype, const void* actv, const void* w_packe
                                 const float* stats, const float* style, int style_ld, void* out, void* gamma_out,
                                 int N, int H, int W, int C, int nh, int lrelu, int flags, int tw, int th,
                                 const int* rect_list, const int* rect_count, hipStream_t st) {
-    if (duo_min_items() <= 0 || dtype != S2E_BF16 || nh % 32 != 0 || C % 64 != 0 || (flags & 1)) return 0;
+    if (duo_min_items() <= 0 || dtype != S2E_BF16 || nh % 32 != 0 || C % 64 != 0 || (flags & S2E_SPADE_ANY_TILES)) return 0;
     if (!duo_rect_ok(tw, th, H, W)) return 0;
     const long rects = (long)N * (H / th) * (W / tw);
     if (rects * (C / 64) < duo_min_items()) return 0;
@@ -881,7 +881,7 @@ int s2e_spade_conv_modulate_duo(int dtype, const void* actv, const void* w_packe
     p.tiles_n = C / 64;
     p.w_bytes = (unsigned)((long)s2e_conv_cout_pad(2 * C) * kpad * 2);
     p.mx = x; p.mstats = stats; p.mstyle = style; p.msld = style_ld > 0 ? style_ld : 2 * C; p.mgamma = gamma_out;
-    p.mC = C; p.mlrelu = lrelu; p.mup = (flags & 8) != 0;
+    p.mC = C; p.mlrelu = lrelu; p.mup = (flags & S2E_SPADE_X_HALF) != 0;
     p.rect_list = rect_list; p.rect_count = rect_count;
     // (rects: an upper bound -- a sparse launch reads the count on the device)
     const int rc = duo_launch<true>(p, rects, st);

@@ -695,18 +695,18 @@ int s2e_conv_patch_launch(int dtype, const s2e_patch_plan* plan, const void* x, 
 // columns) and nh a multiple of the 128-byte K row; never split over channel chunks (the modulation needs the finished sums).
 // It takes smaller maps than s2e_conv_patch_plan does: measured at batch 8 (tools/bench_spade_fused.py), one launch of 128
 // workgroups beats conv + modulation as two launches even at 16x16 (33 -> 23 us) and at 8x8, where three quarters of a tile's
-// rows are idle (31 -> 22 us).  Below S2E_SPADE_FUSED_TILES (default 96) tiles the two-launch path runs; flags & 1 forces the
+// rows are idle (31 -> 22 us).  Below S2E_SPADE_FUSED_TILES (default 96) tiles the two-launch path runs; S2E_SPADE_ANY_TILES forces the
 // fused kernel at any tile count (tests).
 static int fused_plan(int dtype, int N, int H, int W, int C, int nh, int flags, s2e_conv_desc* d, s2e_patch_plan* plan) {
     static const int min_tiles = s2e_env_int("S2E_SPADE_FUSED_TILES", 96);
-    if (min_tiles <= 0 && !(flags & 1)) return 0;
+    if (min_tiles <= 0 && !(flags & S2E_SPADE_ANY_TILES)) return 0;
     if (C <= 0 || C % 64 != 0 || N <= 0 || H <= 0 || W <= 0) return 0;
     const int vec = s2e_vec_lanes(dtype);
     if (nh % (8 * vec) != 0) return 0;
     *d = s2e_conv_desc{N, H, W, nh, H, W, 2 * C, 3, 3, 1, 1, 0, S2E_ACT_NONE, S2E_ACT_NONE, S2E_AUX_NONE};
     plan->splits = 1; plan->tw = plan->th = 0;
     const double fill = s2e_patch_rectangle(d, 3, &plan->tw, &plan->th);
-    if (fill < ((flags & 1) ? 0.01 : 0.2)) return 0;
+    if (fill < ((flags & S2E_SPADE_ANY_TILES) ? 0.01 : 0.2)) return 0;
     // among the rectangles that fill as well, the SQUAREST one (16 x 16 before 8 x 32 before 4 x 64): the smallest patch with its
     // halo (324 vs 340 vs 396 pixels of DMA per chunk) and -- what matters for the label-sparse launch -- the shape most
     // likely to lie inside one label region (bench maps at 256^2: 72 % / 70 % / 58 % of the rectangles are label-uniform)
@@ -718,7 +718,7 @@ static int fused_plan(int dtype, int N, int H, int W, int C, int nh, int flags, 
         if (f >= fill - 1e-9) { plan->tw = tw; plan->th = th; break; }
     }
     const long tiles = (long)N * ceil_div(H, plan->th) * ceil_div(W, plan->tw) * (C / 64);
-    return (flags & 1) || tiles >= min_tiles;
+    return (flags & S2E_SPADE_ANY_TILES) || tiles >= min_tiles;
 }
 
 extern "C" int s2e_spade_conv_modulate_supported(int dtype, int N, int H, int W, int C, int nh, int flags) {
@@ -763,7 +763,7 @@ static int spade_conv_modulate_impl(int dtype, const void* actv, const void* w_p
     p.splits = 1; p.cps = nh / s2e_k_tile(dtype); p.tiles = p.tiles_out;
     p.M = N * H * W; p.partial = nullptr;
     p.mx = x; p.mstats = stats; p.mstyle = style; p.msld = style_ld > 0 ? style_ld : 2 * C; p.mgamma = gamma_out;
-    p.mup = (flags & 8) != 0;
+    p.mup = (flags & S2E_SPADE_X_HALF) != 0;
     if (p.mup && ((H | W) & 1)) S2E_FAIL(S2E_ERR_ARG, "s2e_spade_conv_modulate: flags 8 (x at half resolution) needs even H, W");
     p.mC = C; p.mlrelu = lrelu;
     p.rect_list = rect_list; p.rect_count = rect_count;

@@ -11,6 +11,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from .._lib import SPADE_X_HALF
 
 
 class SegMap:
@@ -187,7 +188,7 @@ class SPADE_STYLE_Block(nn.Module):
             style, kw = sb[1], dict(off=sb[0][id(self.adain.linear)], dbig=sb[2])
         else:
             style, kw = self.adain.linear(latent_style), {}         # (N, 2C) fp32
-        fl = 8 if up else 0
+        fl = SPADE_X_HALF if up else 0
         if ops.spade_fused_supported(x, sp.mlp_shared[0].out_channels, fl) and not (up and batch):
             # the big layers: [gamma | beta] conv and modulation in ONE launch, gamma / beta never written (ops.SpadeFusedFn)
             return ops.spade_style_fused(x, seg.label, sp.mlp_shared[0].weight, sp.mlp_shared[0].bias, sp.mlp_gamma.weight,

@@ -108,6 +108,12 @@ class LaunchProfiler:
                              nbytes() if callable(nbytes) else nbytes, flops if executed is None else executed))
         return r
 
+    @classmethod
+    def executed_fraction(cls, counts, total):
+        """The part of its `total` rectangles that a launch over a device-side rectangle list executes, counts[0] / total, for
+        `executed` and the byte counts of `run` -- read from the device (a sync) only while a profiler is installed; 1.0 otherwise."""
+        return float(int(counts[0])) / max(total, 1) if cls.current is not None else 1.0
+
     def summary(self):
         """family -> dict(launches, flops, ms, bytes); call after a device synchronize."""
         out = {}

@@ -260,8 +260,7 @@ class GradSink:
             f, frac = 2.0 * n * h * w * cin * cout * 9, 1.0
             if j.rects is not None:
                 a.rect_list, a.rect_count = j.rects[0].data_ptr(), j.rects[1].data_ptr()
-                if LaunchProfiler.active():
-                    frac = float(int(j.rects[1][0])) / max(n * (h // 16) * (w // 16), 1)
+                frac = LaunchProfiler.executed_fraction(j.rects[1], n * (h // 16) * (w // 16))
             flops += f
             executed += f * frac
             nbytes += (j.x.numel() + j.gy.numel()) * 2.0 * frac + j.dw.numel() * 4.0
@@ -330,27 +329,22 @@ class GradSink:
 
     # ------------------------------------------------------------------ 8-channel weight gradients (mlp_shared)
     @staticmethod
-    def c8_would_queue(dtype, h, w, dw, db):
-        """Would push_c8 take this layer (so that its caller may leave d(actv) undefined outside the rectangle list it passes)?"""
-        return (ZeroPool.active() is not None and dw is not None and db is not None and dtype == torch.bfloat16
-                and bool(L.call.s2e_wgrad_c8_batch_supported(L.S2E_BF16, h, w, 128)))
+    def c8_takes(dtype, h, w, nh, dw, db, rects):
+        """Does push_c8 queue this layer?  A trainer step open, gradient destinations given, bf16, nh = 128 output channels, a map the
+        batch kernel takes, and with a rectangle list 16-aligned sides.  Said here alone: push_c8 acts on it, and the SPADE backward's
+        plan asks it before it leaves d(actv) undefined outside the rectangle list it passes."""
+        return bool(ZeroPool.active() is not None and dw is not None and db is not None and dtype == torch.bfloat16 and nh == 128
+                    and memo('wgrad_c8', (h, w), L.call.s2e_wgrad_c8_batch_supported, L.S2E_BF16, h, w, 128) and (rects is None or not ((h | w) & 15)))
 
     @staticmethod
     def push_c8(oh, dactv, dw, db, ncls, rects=None):
         """Queue the weight / bias gradient of a 3x3 conv on the 8-channel one-hot map `oh` (N,h,w,8) with output gradient
         `dactv` (N,h,w,128), accumulated straight into dw (128,ncls,3,3) / db (128) fp32 at the next flush -- all queued layers
         in one launch per slab shape (s2e_wgrad_c8_batch).  rects = (rect_list, counts): only the pixels of those 16 x 16 rectangles
-        contribute (the label-sparse backward: dactv is defined there only).  False: not queued (no scope, or a shape the batch
-        does not take)."""
-        pool = ZeroPool.active()
-        if pool is None or dw is None or db is None or oh.dtype != torch.bfloat16:
+        contribute (the label-sparse backward: dactv is defined there only).  False: not queued (c8_takes says no)."""
+        if not GradSink.c8_takes(oh.dtype, oh.shape[1], oh.shape[2], dactv.shape[-1], dw, db, rects):
             return False
-        n, h, w, _ = oh.shape
-        if dactv.shape[-1] != 128 or not L.call.s2e_wgrad_c8_batch_supported(L.S2E_BF16, h, w, 128):
-            return False
-        if rects is not None and ((h | w) & 15):
-            return False
-        pool.sink.c8.append(C8Job(oh, dactv, dw, db, int(ncls), rects))
+        ZeroPool.active().sink.c8.append(C8Job(oh, dactv, dw, db, int(ncls), rects))
         return True
 
     def _flush_c8(self):

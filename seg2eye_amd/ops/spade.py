@@ -1,12 +1,14 @@
 """The SPADE+Style block (normalization.py:91-192): InstanceNorm statistics, label-map convs and their batched prepass, the
 [gamma | beta] branch with its label-sparse forward and backward, the modulation (two-launch and fused into the conv), plain InstanceNorm."""
 import ctypes as C
+from collections import namedtuple
 
 import torch
 
 from .. import _lib as L
 from .. import packing
-from .._lib import NORM_SPADE_STYLE_BATCH, NORM_ACCUMULATE_DX, ACT_NONE, AUX_NONE, AUX_RELU_MASK, NORM_SPADE_STYLE
+from .._lib import (NORM_SPADE_STYLE_BATCH, NORM_ACCUMULATE_DX, ACT_NONE, AUX_NONE, AUX_RELU_MASK, NORM_SPADE_STYLE, SPADE_DENSE, SPADE_ANY_RECTS,
+                    SPADE_X_HALF)
 from . import switches
 from .core import (IN_EPS, LaunchProfiler, ZeroPool, _adjacent, _cl_dense, _cl_rows, _dt, _grad_dst, _need, _p, _span2, _stream,
                    device_job_table)
@@ -304,135 +306,139 @@ def _gb_grad_targets(ctx, fused, w_sh, b_sh, w_g, b_g, w_b, b_b, nh):
 _SPARSE_BWD_MIN = 96      # (round 4 sweep, ms per step at 48 / 96 / 192: 18.44-18.60 / 18.43-18.48 / 18.40-18.44; a constant since round 5)
 
 
-def _sparse_bwd_lists(ctx, g, h, w, cch, nh, ncls):
-    """(cls, work_list, ui_list, counts) for the label-sparse backward of this SPADE layer, or None: the forward ran label-sparse
-    on 16 x 16 rectangles (ctx.rects), a trainer step is open (zeroed scratch, deferred flush), mlp_shared's gradients go straight
-    to the arena, and the data-gradient's kernel takes a rectangle list.  S2E_SPADE_SPARSE_BWD=0 / S2E_DETERMINISTIC=1 (the sums
-    use float atomics): off."""
-    rects = getattr(ctx, 'rects', None)
-    pool = ZeroPool.active()
-    if switches.SPARSE_BWD_OFF or rects is None or pool is None or g.dtype != torch.bfloat16 or ncls > 4 or nh > 128:
-        return None
-    cls, _, _, _, tw, th = rects
-    wdst, bdst = ctx.sh_dst
-    if tw != 16 or th != 16 or h < _SPARSE_BWD_MIN or w < _SPARSE_BWD_MIN or 2 * cch not in (128, 256, 512, 1024) or wdst is None or bdst is None or not wdst.is_contiguous():
-        return None
-    n = g.shape[0]
-    if not _conv_shape(False, _dt(g), n, h, w, 2 * cch, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK).rects:
-        return None
-    ck = ('rects_bwd', cls.data_ptr(), h, w)
-    ent = pool.step_cache.get(ck)
-    if ent is None:
-        lists = torch.empty(2, cls.numel(), dtype=torch.int32, device=g.device)
+# the forms of the [gamma | beta] conv's weight gradient: over the backward's work rectangles into the channels-last arena slice; dense
+# into that slice's rows; dense into a packed buffer that is unpacked into a torch-order arena slice; dense, handed back to autograd
+GB_RECTS, GB_ARENA_ROWS, GB_ARENA_UNPACK, GB_AUTOGRAD = 'rects', 'arena_rows', 'arena_unpack', 'autograd'
+# lists: (cls, work_list, ui_list, counts) of the label-sparse backward, None = the dense one; lazy_dactv: d(actv) stays undefined off the work rectangles
+SpadeBwdPlan = namedtuple('SpadeBwdPlan', 'lists gb_wgrad lazy_dactv')
+
+
+def _plan_spade_bwd(ctx, g, nh, ncls):
+    """What the backward of one SPADE branch does, decided here once; the stages of _spade_param_grads launch what it says.
+    Label-sparse (lists): the forward ran label-sparse on 16 x 16 rectangles (ctx.rects), a trainer step is open (zeroed scratch,
+    deferred flush), mlp_shared's gradients go straight to the arena, and the data-gradient's kernel takes a rectangle list.
+    S2E_SPADE_SPARSE_BWD=0 / S2E_DETERMINISTIC=1 (the sums use float atomics): off."""
+    (h, w, C), (wdst, bdst), n, dt = ctx.cfg, ctx.sh_dst, g.shape[0], _dt(g)
+    rects, pool = getattr(ctx, 'rects', None), ZeroPool.active()
+    sparse = not (switches.SPARSE_BWD_OFF or rects is None or pool is None or g.dtype != torch.bfloat16 or ncls > 4 or nh > 128)
+    sparse = (sparse and rects[4] == 16 and rects[5] == 16 and h >= _SPARSE_BWD_MIN and w >= _SPARSE_BWD_MIN and 2 * C in (128, 256, 512, 1024)
+              and wdst is not None and bdst is not None and wdst.is_contiguous()
+              and _conv_shape(False, dt, n, h, w, 2 * C, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK).rects)
+    lists = pool.step_cache.get(('rects_bwd', rects[0].data_ptr(), h, w)) if sparse else None
+    if sparse and lists is None:                              # once per step and resolution
+        both = torch.empty(2, rects[0].numel(), dtype=torch.int32, device=g.device)
         counts = torch.empty(2, dtype=torch.int32, device=g.device)
-        L.call.s2e_label_rect_lists_bwd(_p(cls), n, h // 16, w // 16, _p(lists[0]), _p(lists[1]), _p(counts), _stream())
-        ent = pool.step_cache[ck] = (cls, lists[0], lists[1], counts)
-    return ent
+        L.call.s2e_label_rect_lists_bwd(_p(rects[0]), n, h // 16, w // 16, _p(both[0]), _p(both[1]), _p(counts), _stream())
+        lists = pool.step_cache[('rects_bwd', rects[0].data_ptr(), h, w)] = (rects[0], both[0], both[1], counts)
+    dw, db = ctx.gb_dst if ctx.gb_dst is not None else (None, None)
+    # the rectangle form: a channels-last arena slice (_cl_dense: the dense (co, ky, kx, ci) strides with which the uniform rectangles'
+    # rank-1 update walks dW) and a shape whose weight-gradient kernel takes a list (else no workspace size: the dense one runs)
+    by_rects = (lists is not None and db is not None
+                and _conv_shape(True, dt, n, h, w, nh, h, w, 2 * C, 3, 3, 1, 1, 0, ACT_NONE, ACT_NONE, AUX_NONE).rects_workspace_bytes)
+    gb_wgrad = GB_AUTOGRAD if dw is None else GB_ARENA_UNPACK if not _cl_dense(dw) else GB_RECTS if by_rects else GB_ARENA_ROWS
+    # d(actv) exists on the work rectangles only.  When its one reader -- mlp_shared's weight gradient -- is queued with the same
+    # rectangle list (round 6) the rest is never read: no zero-fill (0.5 GB per G step at the bench's size).  Otherwise zeros.
+    lazy = lists is not None and not switches.C8_SPARSE_OFF and GradSink.c8_takes(g.dtype, h, w, nh, wdst, bdst, lists)
+    return SpadeBwdPlan(lists, gb_wgrad, lazy)
 
 
-def _sparse_wgrad(g, actv, gb_dst, sp):
+def _gb_wgrad_rects(g, actv, gb_dst, lists):
     """The [gamma | beta] conv's weight (and bias) gradient over the backward's work rectangles only (s2e_conv2d_wgrad_rects),
     accumulated straight into the channels-last arena slice; the uniform-interior rectangles' part -- rank one per class -- is
-    added by s2e_spade_uniform_grads at the flush.  False: this shape's kernel takes no list (the caller runs the dense one)."""
-    n, h, w, nh = actv.shape
-    c2 = g.shape[-1]
-    d, _, wsb = _conv_shape(True, _dt(g), n, h, w, nh, h, w, c2, 3, 3, 1, 1, 0, ACT_NONE, ACT_NONE, AUX_NONE)
-    dw, db = gb_dst
-    if not wsb or db is None or w_strides_differ(dw):
-        return False
-    cls, work_list, ui_list, counts = sp
+    added by s2e_spade_uniform_grads at the flush."""
+    (n, h, w, nh), c2, (dw, db) = actv.shape, g.shape[-1], gb_dst
+    cls, work_list, ui_list, counts = lists
     if GradSink.push_wgrad(actv, g, _cl_rows(dw), db, rects=(work_list, counts)):
-        return True
+        return
+    d, _, wsb = _conv_shape(True, _dt(g), n, h, w, nh, h, w, c2, 3, 3, 1, 1, 0, ACT_NONE, ACT_NONE, AUX_NONE)
     ws = torch.empty(max(wsb // 4, 4), dtype=torch.float32, device=g.device)
     flops = 2.0 * n * h * w * nh * c2 * 9
-    frac = 1.0
-    if LaunchProfiler.active():
-        frac = float(int(counts[0])) / max(cls.numel(), 1)
+    frac = LaunchProfiler.executed_fraction(counts, cls.numel())
     LaunchProfiler.run(
         'conv_wgrad_patch', flops, L.call.s2e_conv2d_wgrad_rects,
         (_dt(g), _p(actv), _p(g), _p(_cl_rows(dw)), _p(db), d, _p(work_list), _p(counts), _p(ws), wsb, _stream()),
         tag=lambda: 'W n%d %dx%d c%d->%d k3 s1 sparse' % (n, h, w, nh, c2),
         nbytes=lambda: float((actv.numel() + g.numel()) * frac * g.element_size()), executed=flops * frac)
-    return True
 
 
-def w_strides_differ(dw):
-    """The rank-1 update walks dW with the weight's strides: both must be the dense channels-last (co, ky, kx, ci) layout."""
-    co, ci, kh, kw = dw.shape
-    return tuple(dw.stride()) != (kh * kw * ci, 1, kw * ci, ci)
-
-
-def _spade_param_grads(ctx, g, label, w_sh, w_gb, actv):
-    """Backward of gb = conv3x3(ReLU(conv3x3(one_hot(label)))) given g = d/d[gamma | beta] (N,h,w,2C):
-    -> (gw_sh, gb_sh, gw_g, gb_g, gw_b, gb_b), None where the gradient went straight into the arena.
-    The ReLU mask is fused into the data-gradient epilogue; the mlp_shared weight gradient is an MFMA wgrad against the
-    (tiny) 8-channel one-hot map; bias gradients come out of the wgrad kernels."""
-    h, w, C = ctx.cfg
-    c2, nh = w_gb.shape[0], w_gb.shape[1]
-    ncls = w_sh.shape[1]
-    gw_g = gb_g = gw_b = gb_b = gw_sh = gb_sh = None
-    sp = _sparse_bwd_lists(ctx, g, h, w, C, nh, ncls)
-    uni_gb = None                                            # (dW, db) of [gamma | beta] that take the uniform rectangles' rank-1 part
-    if sp is not None and ctx.gb_dst is not None and _cl_dense(ctx.gb_dst[0]) and _sparse_wgrad(g, actv, ctx.gb_dst, sp):
-        uni_gb = ctx.gb_dst
-    elif ctx.gb_dst is not None and _cl_dense(ctx.gb_dst[0]):     # channels-last arena: straight into [dW_gamma; dW_beta]
+def _gb_wgrad(plan, ctx, g, w_gb, actv):
+    """Stage 1: the [gamma | beta] conv's weight and bias gradient in the plan's form -> (gw_g, gb_g, gw_b, gb_b), None where the
+    gradient went straight into the arena."""
+    C, c2, nh = ctx.cfg[2], w_gb.shape[0], w_gb.shape[1]
+    if plan.gb_wgrad == GB_RECTS:
+        _gb_wgrad_rects(g, actv, ctx.gb_dst, plan.lists)
+    elif plan.gb_wgrad == GB_ARENA_ROWS:                      # straight into [dW_gamma; dW_beta]
         conv2d_wgrad_raw(actv, g, 3, 3, 1, 1, ACT_NONE, True, ctx.gb_dst[1], dw_out=_cl_rows(ctx.gb_dst[0]), defer_ok=True)
-    elif ctx.gb_dst is not None:
+    elif plan.gb_wgrad == GB_ARENA_UNPACK:
         dwp, _ = conv2d_wgrad_raw(actv, g, 3, 3, 1, 1, ACT_NONE, True, ctx.gb_dst[1], defer_ok=True)
         unpack_weight_grad_into(dwp, ctx.gb_dst[0], c2, nh, 3, 3, nh)
     else:
         dwp, gb_gb = conv2d_wgrad_raw(actv, g, 3, 3, 1, 1, ACT_NONE, True)
         gw_gb = _unpack_dw(dwp, c2, nh, 3, 3, nh)
-        gw_g, gw_b, gb_g, gb_b = gw_gb[:C], gw_gb[C:], gb_gb[:C], gb_gb[C:]
+        return gw_gb[:C], gb_gb[:C], gw_gb[C:], gb_gb[C:]
+    return None, None, None, None
+
+
+def _dactv(plan, ctx, g, w_sh, w_gb, actv):
+    """Stage 2: the data gradient d(actv) of the [gamma | beta] conv, ReLU mask fused into its epilogue.  Dense: one conv.
+    Label-sparse (csrc/spade_sparse_bwd.hip): the data gradient -- only ever used for mlp_shared's gradients -- on the rectangles that
+    cross a label boundary (or touch the image border); the uniform-interior ones contribute through nine shifted sums of dgb per
+    class, folded into mlp_shared's gradients (and, in the GB_RECTS form, into the [gamma | beta] conv's) when the step's sink flushes."""
+    (h, w, _), n = ctx.cfg, g.shape[0]
+    c2, nh, ncls = w_gb.shape[0], w_gb.shape[1], w_sh.shape[1]
     wpt = packed_weight(w_gb, g.dtype, nh, True, None, ctx.plan, ctx.plan_gen, stable=ctx.fused)
-    if sp is not None:
-        # label-sparse backward (csrc/spade_sparse_bwd.hip): the data gradient -- only ever used for mlp_shared's gradients -- on the
-        # rectangles that cross a label boundary (or touch the image border); the uniform-interior ones contribute through nine
-        # shifted sums of dgb per class, folded into mlp_shared's gradients when the step's sink flushes
-        cls, work_list, ui_list, counts = sp
-        n = g.shape[0]
-        # d(actv) exists on the work rectangles only.  When its one reader -- mlp_shared's weight gradient -- is queued with the same
-        # rectangle list (round 6) the rest is never read: no zero-fill (0.5 GB per G step at the bench's size).  Otherwise zeros.
-        lazy = not switches.C8_SPARSE_OFF and nh == 128 and GradSink.c8_would_queue(g.dtype, h, w, ctx.sh_dst[0], ctx.sh_dst[1]) and not ((h | w) & 15)
-        dactv = torch.empty(n, h, w, nh, dtype=g.dtype, device=g.device) if lazy else \
-            ZeroPool.take(n * h * w * nh, g.dtype, g.device).view(n, h, w, nh)               # (zero where no conv runs)
-        c8_rects = (work_list, counts) if lazy else None
-        d = _conv_shape(False, _dt(g), n, h, w, c2, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK).d
-        flops = 2.0 * n * h * w * c2 * nh * 9
-        frac = 1.0
-        if LaunchProfiler.active():
-            frac = float(int(counts[0])) / max(cls.numel(), 1)
-        LaunchProfiler.run(
-            'conv_patch', flops, L.call.s2e_conv2d_rects,
-            (_dt(g), _p(g), _p(wpt), None, None, _p(actv), _p(dactv), d, _p(work_list), _p(counts), _stream()),
-            tag=lambda: 'D n%d %dx%d c%d->%d k3 s1 sparse' % (n, h, w, nh, c2),
-            nbytes=lambda: float((g.numel() + 2 * dactv.numel()) * frac * g.element_size() + wpt.numel() * g.element_size()), executed=flops * frac)
-        R = ZeroPool.take(L.UNI_REPLICAS * ncls * 9 * c2, torch.float32, g.device)
-        A = ZeroPool.take(ncls * nh, torch.float32, g.device)
-        LaunchProfiler.run(
-            'spade_uniform_bwd', 0.0, L.call.s2e_spade_uniform_sums,
-            (_dt(g), _p(g), n, h, w, c2, ncls, _p(cls), _p(ui_list), _p(counts), _p(R), _stream()), nbytes=float(g.numel() * g.element_size() * (1.0 - frac) * 1.27))
-        wdst, bdst = ctx.sh_dst
-        assert uni_gb is None or tuple(w_gb.stride()) == tuple(uni_gb[0].stride()), 'weight and gradient arenas are laid out alike'
-        dw_gb, db_gb = uni_gb if uni_gb is not None else (None, None)
-        GradSink.push_uniform(R, A, w_gb.detach(), w_sh.detach(), ctx.b_sh_f, wdst, bdst, dw_gb, db_gb, c2, nh, ncls, g.dtype == torch.bfloat16)
-    else:
-        c8_rects = None
-        dactv = conv2d_raw(g, wpt, None, None, actv, (h, w, nh), 3, 3, 1, 1, True, ACT_NONE, ACT_NONE, AUX_RELU_MASK)
-    # (a streaming class-bucket kernel for this gradient was tried twice -- LDS float atomics, then per-wave
-    # queues of boundary pixels -- and lost to the MFMA wgrad against the 8-channel one-hot map: 1.7 vs 0.75 ms
-    # per step; see DESIGN.md "tried and dropped")
-    oh = onehot_nhwc_raw(label, None, h, w, ncls, 8, g.dtype)
-    wdst, bdst = ctx.sh_dst
+    if plan.lists is None:
+        return conv2d_raw(g, wpt, None, None, actv, (h, w, nh), 3, 3, 1, 1, True, ACT_NONE, ACT_NONE, AUX_RELU_MASK)
+    cls, work_list, ui_list, counts = plan.lists
+    dactv = torch.empty(n, h, w, nh, dtype=g.dtype, device=g.device) if plan.lazy_dactv else \
+        ZeroPool.take(n * h * w * nh, g.dtype, g.device).view(n, h, w, nh)               # (zero where no conv runs)
+    d = _conv_shape(False, _dt(g), n, h, w, c2, h, w, nh, 3, 3, 1, 1, 1, ACT_NONE, ACT_NONE, AUX_RELU_MASK).d
+    flops = 2.0 * n * h * w * c2 * nh * 9
+    frac = LaunchProfiler.executed_fraction(counts, cls.numel())
+    LaunchProfiler.run(
+        'conv_patch', flops, L.call.s2e_conv2d_rects,
+        (_dt(g), _p(g), _p(wpt), None, None, _p(actv), _p(dactv), d, _p(work_list), _p(counts), _stream()),
+        tag=lambda: 'D n%d %dx%d c%d->%d k3 s1 sparse' % (n, h, w, nh, c2),
+        nbytes=lambda: float((g.numel() + 2 * dactv.numel()) * frac * g.element_size() + wpt.numel() * g.element_size()), executed=flops * frac)
+    R = ZeroPool.take(L.UNI_REPLICAS * ncls * 9 * c2, torch.float32, g.device)
+    A = ZeroPool.take(ncls * nh, torch.float32, g.device)
+    LaunchProfiler.run(
+        'spade_uniform_bwd', 0.0, L.call.s2e_spade_uniform_sums,
+        (_dt(g), _p(g), n, h, w, c2, ncls, _p(cls), _p(ui_list), _p(counts), _p(R), _stream()), nbytes=float(g.numel() * g.element_size() * (1.0 - frac) * 1.27))
+    # (dW, db) of [gamma | beta] take the uniform rectangles' rank-1 part when their work rectangles' part went the same way
+    dw_gb, db_gb = ctx.gb_dst if plan.gb_wgrad == GB_RECTS else (None, None)
+    assert dw_gb is None or tuple(w_gb.stride()) == tuple(dw_gb.stride()), 'weight and gradient arenas are laid out alike'
+    GradSink.push_uniform(R, A, w_gb.detach(), w_sh.detach(), ctx.b_sh_f, *ctx.sh_dst, dw_gb, db_gb, c2, nh, ncls, g.dtype == torch.bfloat16)
+    return dactv
+
+
+def _sh_wgrad(plan, ctx, label, dactv, nh, ncls):
+    """Stage 3: mlp_shared's weight and bias gradient, an MFMA wgrad against the (tiny) 8-channel one-hot map -> (gw_sh, gb_sh), None
+    where the gradient went straight into the arena.
+    (a streaming class-bucket kernel for this gradient was tried twice -- LDS float atomics, then per-wave queues of boundary
+    pixels -- and lost to the MFMA wgrad against the 8-channel one-hot map: 1.7 vs 0.75 ms per step; see DESIGN.md "tried and dropped")"""
+    (h, w, _), (wdst, bdst) = ctx.cfg, ctx.sh_dst
+    oh = onehot_nhwc_raw(label, None, h, w, ncls, 8, dactv.dtype)
+    c8_rects = (plan.lists[1], plan.lists[3]) if plan.lazy_dactv else None
     if GradSink.push_c8(oh, dactv, wdst, bdst, ncls, c8_rects):    # inside a trainer step: all mlp_shared gradients in one launch, later
-        return gw_sh, gb_sh, gw_g, gb_g, gw_b, gb_b
-    if c8_rects is not None:
+        return None, None
+    if c8_rects is not None:                                       # (the plan asked push_c8's own predicate: this cannot happen)
         raise L.Seg2EyeHipError('label-sparse SPADE backward: d(actv) was left undefined outside the work rectangles but the 8-channel weight gradient was not queued')
     dwp, gb_sh = conv2d_wgrad_raw(oh, dactv, 3, 3, 1, 1, ACT_NONE, True, bdst, defer_ok=wdst is not None and bdst is not None)
     if wdst is not None:
         unpack_weight_grad_into(dwp, wdst, nh, ncls, 3, 3, 8)
-    else:
-        gw_sh = _unpack_dw(dwp, nh, ncls, 3, 3, 8)
+        return None, gb_sh
+    return _unpack_dw(dwp, nh, ncls, 3, 3, 8), gb_sh
+
+
+def _spade_param_grads(ctx, g, label, w_sh, w_gb, actv):
+    """Backward of gb = conv3x3(ReLU(conv3x3(one_hot(label)))) given g = d/d[gamma | beta] (N,h,w,2C):
+    -> (gw_sh, gb_sh, gw_g, gb_g, gw_b, gb_b), None where the gradient went straight into the arena.  One plan, three stages."""
+    nh, ncls = w_gb.shape[1], w_sh.shape[1]
+    plan = _plan_spade_bwd(ctx, g, nh, ncls)
+    gw_g, gb_g, gw_b, gb_b = _gb_wgrad(plan, ctx, g, w_gb, actv)
+    dactv = _dactv(plan, ctx, g, w_sh, w_gb, actv)
+    gw_sh, gb_sh = _sh_wgrad(plan, ctx, label, dactv, nh, ncls)
     return gw_sh, gb_sh, gw_g, gb_g, gw_b, gb_b
 
 
@@ -526,6 +532,8 @@ def _modulate_grads(ctx, g, g_relay, x, gb, fout, style, stats):
     if g_relay is not None and not acc:
         dx = dx + g_relay
     return dx, dgb, dstyle
+
+
 _SPARSE_MIN_RECTS = 256    # (256^2 and 128^2 at batch 8; below that the classification costs what it saves: round 2; a constant since round 5)
 
 
@@ -545,7 +553,7 @@ def label_rects(label, h, w, dtype, c, nh, flags=0):
         return None
     tw, th = tw.value, th.value
     rects = n * ((h + th - 1) // th) * ((w + tw - 1) // tw)
-    if rects < _SPARSE_MIN_RECTS and not (flags & 4):
+    if rects < _SPARSE_MIN_RECTS and not (flags & SPADE_ANY_RECTS):
         return None
     pool = ZeroPool.active()
     key = ('rects', label.data_ptr(), label._version, n, H, W, h, w, tw, th)
@@ -573,15 +581,15 @@ class SpadeFusedFn(torch.autograd.Function):
     def forward(ctx, x, label, w_sh, b_sh, w_g, b_g, w_b, b_b, style, stats, lrelu, off, dbig, batch, relay, flags, grad_mode):
         _need(x, style, stats)
         n, h, w, c = x.shape
-        # flags & 8: x is the tensor BEFORE the block's nearest 2x upsampling.  The launches read it at (y/2, x/2); the backward
+        # SPADE_X_HALF: x is the tensor BEFORE the block's nearest 2x upsampling.  The launches read it at (y/2, x/2); the backward
         # does too and returns the gradient w.r.t. THIS tensor (the 2 x 2 sums: the upsampling's backward folded in as well).
         # Neither the upsampled tensor nor its gradient ever exists.
-        up = bool(flags & 8)
+        up = bool(flags & SPADE_X_HALF)
         xr = x
         if up:
             h, w = 2 * h, 2 * w
             if batch:
-                raise ValueError('spade_style_fused: the folded upsampling (flags 8) is not built for BatchNorm SPADE')
+                raise ValueError('spade_style_fused: the folded upsampling (SPADE_X_HALF) is not built for BatchNorm SPADE')
         _, H, W = label.shape
         nh = w_sh.shape[0]
         dtype = x.dtype
@@ -600,7 +608,7 @@ class SpadeFusedFn(torch.autograd.Function):
         sp = style.data_ptr() + 4 * (off or 0)
         b_f = b_gb.float().contiguous()
         flops = 2.0 * n * h * w * nh * 2 * c * 9
-        sparse = None if (flags & 2) else label_rects(label, h, w, x.dtype, c, nh, flags)
+        sparse = None if (flags & SPADE_DENSE) else label_rects(label, h, w, x.dtype, c, nh, flags)
         if sparse is None:
             LaunchProfiler.run(
                 'conv_patch', flops, L.call.s2e_spade_conv_modulate,
@@ -614,10 +622,7 @@ class SpadeFusedFn(torch.autograd.Function):
             cls, dense_list, uni_list, counts, tw, th = sparse
             ncls = w_sh.shape[1]
             table = SpadePrepass.table(x.dtype, w_sh, b_sh, wp, b_f, ncls, nh, c, wp_persistent and b_f.data_ptr() == b_gb.data_ptr())
-            frac = 1.0
-            if LaunchProfiler.active():                         # executed work of this launch (a sync: profiling runs only)
-                rects = cls.numel()
-                frac = float(int(counts[0])) / max(rects, 1)
+            frac = LaunchProfiler.executed_fraction(counts, cls.numel())
             LaunchProfiler.run(
                 'conv_patch', flops, L.call.s2e_spade_conv_modulate_sparse,
                 (_dt(x), _p(actv), _p(wp), _p(b_f), _p(xr), _p(stats), sp, ld, _p(out), _p(gamma),
@@ -628,7 +633,7 @@ class SpadeFusedFn(torch.autograd.Function):
             LaunchProfiler.run(
                 'modulate_fwd', 0.0, L.call.s2e_spade_modulate_uniform,
                 (_dt(x), _p(xr), _p(stats), sp, ld, _p(table), _p(cls), _p(uni_list), _p(counts), _p(out),
-                 _p(gamma), n, h, w, c, tw, th, int(lrelu), int(bool(flags & 8)), _stream()),
+                 _p(gamma), n, h, w, c, tw, th, int(lrelu), int(up), _stream()),
                 nbytes=float((xr.numel() + out.numel() * (2 if train else 1)) * (1.0 - frac) * x.element_size()))
         ctx.cfg = (h, w, c)
         ctx.lrelu, ctx.off, ctx.dbig, ctx.batch, ctx.relay = lrelu, off, dbig, bool(batch), bool(relay)
@@ -646,7 +651,6 @@ class SpadeFusedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, g_relay=None):
         x, label, w_sh, w_gb, actv, gamma, out, style, stats = ctx.saved_tensors
-        nn_ = (None,) * 8
         if g is None:
             return (g_relay,) + (None,) * 16
         dx, dgb, dstyle = _modulate_grads(ctx, g, g_relay, x, gamma, out, style, stats)
@@ -655,10 +659,10 @@ class SpadeFusedFn(torch.autograd.Function):
 
 
 def spade_fused_supported(x, nh, flags=0):
-    """Does s2e_spade_conv_modulate take this layer (x: (N,h,w,C) NHWC, nh = mlp_shared's width; flags & 8: x is the
+    """Does s2e_spade_conv_modulate take this layer (x: (N,h,w,C) NHWC, nh = mlp_shared's width; SPADE_X_HALF: x is the
     half-resolution tensor of a folded upsampling)?"""
     n, h, w, c = x.shape
-    if flags & 8:
+    if flags & SPADE_X_HALF:
         h, w = 2 * h, 2 * w
     if switches.FUSED_OFF:
         return False

@@ -61,7 +61,8 @@ def mf16_on():
 def duo_takes_fused(N, H, W, C_, nh, flags, tw, th):
     """The rule of s2e_spade_conv_modulate_duo (csrc/conv_duo.hip:882-888): whether the duo kernel runs a fused launch that
     s2e_spade_conv_modulate has planned with tw x th rectangles (else conv_patch.hip's fused kernel runs it)."""
-    if duo_min_items() <= 0 or nh % 32 != 0 or C_ % 64 != 0 or (flags & 1):
+    from seg2eye_amd._lib import SPADE_ANY_TILES
+    if duo_min_items() <= 0 or nh % 32 != 0 or C_ % 64 != 0 or (flags & SPADE_ANY_TILES):
         return False
     if not (tw == 16 and th == 16 and H % 16 == 0 and W % 16 == 0):           # duo_rect_ok
         return False
@@ -428,7 +429,7 @@ NH = 128
 def run_fused(group, N, H, W, C_, lrelu_on, up, banked, with_gamma, with_bias, dev, seed, lists=False):
     L, lb = lib()
     from seg2eye_amd import ops
-    flags = 8 if up else 0
+    flags = L.SPADE_X_HALF if up else 0
     g = torch.Generator().manual_seed(seed)
     actv = torch.relu(rnd((N, H, W, NH), g)).to(torch.bfloat16)
     w = rnd((2 * C_, NH, 3, 3), g, (NH * 9) ** -0.5)

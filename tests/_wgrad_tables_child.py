@@ -104,7 +104,7 @@ def _tables():
                 assert small[a % len(small)] == small[b % len(small)]
                 t[b] = t[b][:9] + (t[a][9], t[a][10] if t[a][10] is not None else t[b][10])
         T['gen_chunk%d' % n_jobs] = t
-    # WF_MAX_JOBS = 24: 25 flat jobs (4x4 stride 1 / stride 2), one huge among tiny ones, some dw shared (the flags & 8 rule)
+    # WF_MAX_JOBS = 24: 25 flat jobs (4x4 stride 1 / stride 2), one huge among tiny ones, some dw shared (the flat kernel's single-owner bit, 8 of its own flags)
     t = [J(16, 129, 129, 64, 128, 4, 2, 2, 5, dw=('fw0', 0), db=('fb0', 0))]
     for i in range(1, 25):
         t.append(J(1, 9, 9, 64, 128, 4, 2, 2, 5, dw=('fw%d' % i, 0), db=('fb%d' % i, 0)) if i % 2 else

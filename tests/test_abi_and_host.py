@@ -625,6 +625,15 @@ def _ctypes_class(t):
     return table[t]
 
 
+def test_mirrored_constants_are_the_headers():
+    """The fused SPADE launch's flag bits (and the replica count of the uniform sums) in _lib against the header's #defines."""
+    from seg2eye_amd import _lib
+    defs = {k: int(v) for k, v in re.findall(r'(?m)^#define\s+S2E_(\w+)\s+(\d+)\s*$', _header_text())}
+    for name in ('SPADE_ANY_TILES', 'SPADE_DENSE', 'SPADE_ANY_RECTS', 'SPADE_X_HALF', 'UNI_REPLICAS'):
+        assert getattr(_lib, name) == defs[name], name
+    assert (_lib.SPADE_ANY_TILES, _lib.SPADE_DENSE, _lib.SPADE_ANY_RECTS, _lib.SPADE_X_HALF) == (1, 2, 4, 8)
+
+
 def test_binding_agrees_with_the_header_in_arguments_return_types_and_structures():
     """_lib.SIGNATURES and the ctypes structures are a second copy of include/seg2eye_hip.h: compare them position by position --
     argument count, the class of every argument, the return class against the entry's kind, and every field of the job structures."""

@@ -2,7 +2,7 @@
 against fp64 references of the same bf16 operands, element by element (tests/_conv3x3_child.py has the references and the bound).
 
 Every case runs in a child process with the switches the library reads once per process: the duo kernel on small shapes
-(S2E_CONV_DUO=1, S2E_SPADE_FUSED_TILES=1: no `flags & 1`, which would route the fused launch past it), conv_patch.hip on the same shapes
+(S2E_CONV_DUO=1, S2E_SPADE_FUSED_TILES=1: no S2E_SPADE_ANY_TILES, which would route the fused launch past it), conv_patch.hip on the same shapes
 (S2E_CONV_DUO=0, S2E_CONV_PATCH=1), the 32x32x16 duo loop (S2E_DUO_MF16=0), the library's own thresholds at bench-like shapes, and the
 patch weight gradient (S2E_WGRAD_PATCH=1, with and without S2E_DETERMINISTIC=1).  Each child prints the kernel every case ran in and its
 work items relative to the duo kernel's persistent grid (cap = 2 x CUs)."""

@@ -84,9 +84,10 @@ def test_check_close_fails_on_nan_and_outliers():
 
 def test_plan_mirrors(monkeypatch):
     assert [T.wgrad_slab(16, 64), T.wgrad_slab(16, 96), T.wgrad_slab(16, 48), T.wgrad_slab(32, 32)] == [64, 32, 16, 32]
+    from seg2eye_amd._lib import SPADE_ANY_TILES
     monkeypatch.setenv('S2E_CONV_DUO', '1')
     assert T.duo_takes_fused(1, 16, 16, 64, 128, 0, 16, 16)
-    assert not T.duo_takes_fused(1, 16, 16, 64, 128, 1, 16, 16)         # flags & 1 routes past the duo kernel
+    assert not T.duo_takes_fused(1, 16, 16, 64, 128, SPADE_ANY_TILES, 16, 16)         # routes past the duo kernel
     assert not T.duo_takes_fused(1, 16, 16, 64, 128, 0, 32, 8)
     monkeypatch.setenv('S2E_CONV_DUO', '0')
     assert not T.duo_takes_fused(1, 16, 16, 64, 128, 0, 16, 16)

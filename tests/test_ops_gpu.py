@@ -282,17 +282,17 @@ def test_spade_params_and_label_conv(cfg, dtype):
                                  # the partial-slab maps of test_spade_style_modulate: every row tail of the gamma-only form too
                                  (2, 33, 40, 33, 40, 64, True, False), (2, 40, 50, 40, 50, 64, True, True), (2, 36, 36, 36, 36, 64, False, True)])
 def test_spade_conv_modulate_fused(cfg, sparse, dtype):
-    """s2e_spade_conv_modulate (the [gamma | beta] conv with the modulation in its epilogue; flags=1 forces the fused kernel at
+    """s2e_spade_conv_modulate (the [gamma | beta] conv with the modulation in its epilogue; SPADE_ANY_TILES forces the fused kernel at
     any tile count) against the fp64 reference of SPADE_STYLE_Block.forward (normalization.py:184-192) and against the two-launch
     path, forward (no-grad: gamma never stored; with grad) and every gradient (s2e_modulate_bwd's gamma-only form).
-    sparse: the label-sparse form (flags 4 forces it at these small sizes) on clean nested-ellipse maps -- label-uniform
-    rectangles take gamma / beta from the per-class table, incl. the rectangles on the image border; dense: flags 2."""
-    from seg2eye_amd import ops
+    sparse: the label-sparse form (SPADE_ANY_RECTS forces it at these small sizes) on clean nested-ellipse maps -- label-uniform
+    rectangles take gamma / beta from the per-class table, incl. the rectangles on the image border; dense: SPADE_DENSE."""
+    from seg2eye_amd import ops, _lib as L
     from seg2eye_amd.synthetic import ellipse_labels
     N, H, W, h, w, C, lrelu, relay = cfg
     dev = _dev()
     lab = torch.from_numpy(ellipse_labels(N, H, W, 5)[:, 0]) if sparse else _labels(N, H, W, 5)
-    FL = 1 | (4 if sparse else 2)
+    FL = L.SPADE_ANY_TILES | (L.SPADE_ANY_RECTS if sparse else L.SPADE_DENSE)
     if sparse:                                           # the map must really have both kinds of rectangles
         rc = ops.label_rects(lab.to(dev), h, w, dtype, C, 128, FL)
         assert rc is not None
@@ -319,7 +319,7 @@ def test_spade_conv_modulate_fused(cfg, sparse, dtype):
     if lrelu:
         yr = F.leaky_relu(yr, 0.2)
     yr.backward(gy.double())
-    assert ops.spade_fused_supported(nhwc(x).to(dev), 128, flags=1)
+    assert ops.spade_fused_supported(nhwc(x).to(dev), 128, flags=L.SPADE_ANY_TILES)
     prm = [t.to(dev).requires_grad_(True) for t in (w_sh, b_sh, w_gb[:C].clone(), b_gb[:C].clone(), w_gb[C:].clone(), b_gb[C:].clone())]
     xg = nhwc(x).to(dev).requires_grad_(True)
     sg = style.to(dev).requires_grad_(True)
@@ -328,12 +328,12 @@ def test_spade_conv_modulate_fused(cfg, sparse, dtype):
         y0 = ops.spade_style_fused(xg, lab.to(dev), *prm, sg, st, lrelu, flags=FL)
     _close(nchw(y0), yr, dtype, what='fused out (no grad)')
     if h % 2 == 0 and w % 2 == 0:                         # (an odd map is not the output of a 2x upsampling)
-        # flags 8: x handed over at HALF resolution, the generator's nearest 2x upsampling folded into the launch's read of x
+        # SPADE_X_HALF: x handed over at HALF resolution, the generator's nearest 2x upsampling folded into the launch's read of x
         # (no-grad forward) -- the same bits as upsampling first
         xl = nhwc(_rnd((N, C, h // 2, w // 2), 48, dtype) * 1.1 - 0.1).to(dev)
         stl = ops.in_stats(xl)
         with torch.no_grad():
-            y_fold = ops.spade_style_fused(xl, lab.to(dev), *prm, sg, stl, lrelu, flags=FL | 8)
+            y_fold = ops.spade_style_fused(xl, lab.to(dev), *prm, sg, stl, lrelu, flags=FL | L.SPADE_X_HALF)
             y_mat = ops.spade_style_fused(ops.upsample2x(xl), lab.to(dev), *prm, sg, stl, lrelu, flags=FL)
         assert y_fold.shape == y_mat.shape == (N, h, w, C) and torch.equal(y_fold, y_mat)
         # ... and WITH gradients (the training forward): the same output bit for bit, and the gradient w.r.t. the half-resolution
@@ -345,7 +345,7 @@ def test_spade_conv_modulate_fused(cfg, sparse, dtype):
             xs = xl.clone().requires_grad_(True)
             prm2 = [t.detach().clone().requires_grad_(True) for t in prm]
             if fold:
-                yy = ops.spade_style_fused(xs, lab.to(dev), *prm2, sg.detach(), stl, lrelu, flags=FL | 8)
+                yy = ops.spade_style_fused(xs, lab.to(dev), *prm2, sg.detach(), stl, lrelu, flags=FL | L.SPADE_X_HALF)
             else:
                 yy = ops.spade_style_fused(ops.upsample2x(xs), lab.to(dev), *prm2, sg.detach(), stl, lrelu, flags=FL)
             yy.backward(gyl)

@@ -36,7 +36,7 @@ def main():
         def fused(g):
             L.check(L.lib().s2e_spade_conv_modulate(ops._dt(x), actv.data_ptr(), wp.data_ptr(), b.data_ptr(), x.data_ptr(), st.data_ptr(),
                                                     style.data_ptr(), 0, out.data_ptr(), g.data_ptr() if g is not None else None,
-                                                    N, h, h, C, nh, 1, 1, ops._stream()))
+                                                    N, h, h, C, nh, 1, L.SPADE_ANY_TILES, ops._stream()))
         t2 = timeit(two)
         tc = timeit(lambda: ops.conv2d_raw(actv, wp, b, None, None, (h, h, 2 * C), 3, 3, 1, 1, out=gb))
         tn = timeit(lambda: fused(None))

@@ -40,7 +40,7 @@ def digest(t):
 def run(root, out_path):
     sys.path.insert(0, os.path.abspath(root))
     import torch
-    from seg2eye_amd import ops
+    from seg2eye_amd import ops, _lib as L
     from seg2eye_amd.ops import spade as S
     from seg2eye_amd.ops.sink import GradSink
     from seg2eye_amd import distributed as sdist
@@ -111,7 +111,7 @@ def run(root, out_path):
             assert torch.equal(g_relay, keep) and dx.data_ptr() != g_relay.data_ptr()
             put(key + '/staged_relay', dx, dgb, dstyle)
             # the fused launch (gamma-only backward; flags 8: x at half resolution, the quad dx), where the layer is one it takes
-            if c % 64 or not ops.spade_fused_supported(x, 128, flags=1):
+            if c % 64 or not ops.spade_fused_supported(x, 128, flags=L.SPADE_ANY_TILES):
                 continue
             gen.manual_seed(7)
             lab = torch.randint(0, 4, (n, h, w), device=dev, generator=gen, dtype=torch.uint8)
@@ -126,7 +126,8 @@ def run(root, out_path):
                     xs = xin.clone().requires_grad_(True)
                     p2 = [t.clone().requires_grad_(True) for t in prm]
                     sg = style.clone().requires_grad_(True)
-                    y = ops.spade_style_fused(xs, lab, *p2, sg, st, True, relay=relay, flags=1 | 2 | (8 if fold else 0))
+                    y = ops.spade_style_fused(xs, lab, *p2, sg, st, True, relay=relay,
+                                              flags=L.SPADE_ANY_TILES | L.SPADE_DENSE | (L.SPADE_X_HALF if fold else 0))
                     if relay:
                         y, xa = y
                         torch.autograd.backward([y, xa], [gy, rnd(tuple(xin.shape), 15, dtype)])
