@@ -779,6 +779,36 @@ int s2e_mask_dist(const uint8_t* a, const uint8_t* b, int M, int K, long P, long
 int s2e_rank_topk_max_candidates(void);
 int s2e_rank_topk(const int32_t* dist, int M, int K, int k, const int32_t* exclude, int32_t* idx, int32_t* val, void* stream);
 
+/* ------------------------------------------------------------------ eye segmenter: loss, mask, confusion matrix
+ * The masks `style_rank --seg_file` reads come from a small encoder-decoder built on the convolutions above (networks/segmenter.py);
+ * these are its three memory-bound pieces.  logits: (N, H, W, C) NHWC of dtype, channel pitch C >= ncls, 1 <= ncls <= 16; channels at
+ * and past ncls may hold anything (NaN included) and influence nothing.  label: (N, H, W) uint8; a value >= ncls (255 is the documented
+ * "ignore") marks a pixel that is not counted and is never used as an index.  No float atomics: the same input gives the same bits.
+ *   s2e_seg_ce_fwd: loss[0] = sum_p w[l_p] (lse_p - z_{p,l_p}) / sum_p w[l_p] over the counted pixels, lse in fp32 with the maximum
+ *       subtracted -- F.cross_entropy(weight=w, ignore_index=..., reduction='mean') -- and denom[0] = sum_p w[l_p] for the backward;
+ *       a denominator of 0 gives loss 0.  weights: fp32 (ncls).  Two launches: per-workgroup fp64 partials into `workspace`
+ *       (s2e_seg_ce_workspace_bytes(N, H, W) bytes, 8-byte aligned), then one fold in index order.
+ *   s2e_seg_ce_bwd: dlogits[p][c] = gloss[0] w[l_p] (softmax_c(z_p) - [c == l_p]) / denom[0] in dtype, the softmax recomputed; +0 for
+ *       ignored pixels, for channels >= ncls, and everywhere when denom[0] is 0.  gloss, denom: one fp32 each, on the device.  One launch.
+ *   s2e_seg_argmax_u8: mask (N, Ho, Wo) uint8 = argmax_c of the ncls logits resized bilinearly in fp32 by the rule of
+ *       s2e_bilinear_resize_fwd (F.interpolate(mode='bilinear', align_corners=False): source coordinate (d + 0.5) in / out - 0.5,
+ *       clamped at 0); a tie goes to the lowest class; (Ho, Wo) == (h, w) is the plain argmax.  One launch, the resized logits are
+ *       never stored.
+ *   s2e_seg_confusion_u8: conf (ncls x ncls) int64, row = truth, column = pred, += the counts of the P pixel pairs; the caller zeroes
+ *       it before the first call.  A pair with either value >= ncls is skipped.  One launch: LDS counts per workgroup, then one 64-bit
+ *       integer atomic per non-zero cell.
+ * Before any launch, in this order: S2E_ERR_ARG on a null pointer (conf also: not 8-byte aligned), an unknown dtype, N, H, W (P) < 1;
+ * S2E_ERR_UNSUPPORTED on ncls outside 1..16; S2E_ERR_ARG on C < ncls; S2E_ERR_UNSUPPORTED on N H W > 2^31 - 1 (P > 2^31 - 1 per
+ * call: accumulate more with further calls); then s2e_seg_ce_fwd: S2E_ERR_ARG on a missing, short or misaligned workspace;
+ * s2e_seg_argmax_u8: S2E_ERR_ARG on Ho or Wo < 1, S2E_ERR_UNSUPPORTED on N Ho Wo > 2^31 - 1, N or Ho > 65535. */
+size_t s2e_seg_ce_workspace_bytes(int N, int H, int W);
+int s2e_seg_ce_fwd(int dtype, const void* logits, const uint8_t* label, const float* weights, int N, int H, int W, int C, int ncls,
+                   float* loss, float* denom, void* workspace, size_t workspace_bytes, void* stream);
+int s2e_seg_ce_bwd(int dtype, const void* logits, const uint8_t* label, const float* weights, const float* denom, const float* gloss,
+                   int N, int H, int W, int C, int ncls, void* dlogits, void* stream);
+int s2e_seg_argmax_u8(int dtype, const void* logits, int N, int h, int w, int C, int ncls, int Ho, int Wo, uint8_t* mask, void* stream);
+int s2e_seg_confusion_u8(const uint8_t* pred, const uint8_t* truth, long P, int ncls, int64_t* conf, void* stream);
+
 /* ------------------------------------------------------------------ side-by-side validation panels
  * The reference's visualize_sidebyside (util/visualizer.py:131-166) for a batch of n samples, as three launches on the caller's
  * stream with no host synchronisation between them: out[i] = [ style | label | target_original | fake | heat ], five h x w cells of

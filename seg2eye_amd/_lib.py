@@ -196,6 +196,11 @@ SIGNATURES = {
     's2e_mask_dist': (STATUS, [_vp, _vp, _i, _i, _l, _l, _i, _i, _vp, _vp]),
     's2e_rank_topk_max_candidates': (VALUE, []),
     's2e_rank_topk': (STATUS, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    's2e_seg_ce_workspace_bytes': (SIZE, [_i, _i, _i]),
+    's2e_seg_ce_fwd': (STATUS, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
+    's2e_seg_ce_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    's2e_seg_argmax_u8': (STATUS, [_i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    's2e_seg_confusion_u8': (STATUS, [_vp, _vp, _l, _i, _vp, _vp]),
     's2e_bilinear_resize_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_bilinear_resize_bwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_upsample2x_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),

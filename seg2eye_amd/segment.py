@@ -1,0 +1,246 @@
+"""The eye segmenter: train it on an OpenEDS store's labelled frames, score it, and write the masks `style_rank --seg_file`
+reads -- the step between `prepare_openeds` and `style_rank` of the chain  prepare_openeds -> segment -> style_rank -> train -> test.
+
+The generative and sequence frames of the `train` and `validation` splits are unlabelled; `style_rank` compares them through masks it
+expects under /{subset}/{user}/{labels_pred_gen, labels_pred_seq} uint8 (n, 640, 400).  The store holds what such masks can be learned
+from: every person's labelled frames (`images_ss` / `labels_ss`).
+
+    python -m seg2eye_amd.segment train   --dataroot openeds.h5 --name seg --niter 20
+    python -m seg2eye_amd.segment eval    --dataroot openeds.h5 --name seg --dataset_key validation
+    python -m seg2eye_amd.segment predict --dataroot openeds.h5 --name seg --dataset_key train --out masks.h5
+
+Frames go to the device as uint8 and are resized there (`ops.resize_bicubic_u8` to --seg_hw, fp32 in [-1, 1]; labels by
+`ops.resize_nearest_u8`; the horizontal flip of `train` is those ops' flip byte).  The network (networks/segmenter.py: EyeSegNet) gives
+logits at --seg_hw; the loss is `ops.seg_cross_entropy`, a mask is `ops.seg_argmax_u8` of the logits resized to the frame's own size,
+the score is mIoU (the OpenEDS segmentation metric) from `ops.seg_confusion`, accumulated on the device and read back once.
+
+The three commands are plain functions too: `train_segmenter`, `evaluate`, `predict_masks`.  The ops are looked up when called."""
+import argparse
+import types
+
+import numpy as np
+import torch
+
+PRED_KEYS = ('images_gen', 'images_seq')
+
+
+def pred_name(image_key):
+    """'images_gen' -> 'labels_pred_gen': the name style_rank reads the masks of an image key under."""
+    return image_key.replace('images_', 'labels_pred_', 1)
+
+
+def seg_options(**kw):
+    """The options EyeSegNet, the checkpoint names and the functions below read; keyword arguments override the defaults."""
+    o = dict(nsf=32, seg_hw=(320, 200), label_nc=4, compute_dtype='bf16', batchSize=16, checkpoints_dir='./checkpoints', name='segmenter',
+             lr=1e-3, niter=20, class_weights=None, seed=0, no_flip=False, print_freq=50)
+    unknown = sorted(set(kw) - set(o))
+    if unknown:
+        raise TypeError('seg_options: unknown option(s) %s' % ', '.join(unknown))
+    o.update(kw)
+    o['seg_hw'] = tuple(int(v) for v in o['seg_hw'])
+    if len(o['seg_hw']) != 2 or o['seg_hw'][0] % 8 or o['seg_hw'][1] % 8 or min(o['seg_hw']) < 8:
+        raise ValueError('--seg_hw: H,W, both multiples of 8, expected, got %s' % (o['seg_hw'],))
+    return types.SimpleNamespace(**o)
+
+
+def build_network(opt, device='cuda'):
+    from .networks.segmenter import EyeSegNet
+    torch.manual_seed(int(opt.seed))
+    net = EyeSegNet(opt)
+    net.init_weights('kaiming')
+    return net.to(device)
+
+
+def _rows(dataset, idx):
+    """Rows `idx` of a store entry (a numpy array or an HDF5 dataset, which takes one row at a time in any order) as one uint8 array."""
+    return np.stack([np.asarray(dataset[int(i)], dtype=np.uint8) for i in idx])
+
+
+def _frames_to_input(frames, hw, flip, device):
+    """frames (n, 640, 400) uint8 host array -> (n, 1, h, w) fp32 in [-1, 1] on `device`."""
+    from .ops import preprocess as P
+    t = torch.from_numpy(np.ascontiguousarray(frames)).to(device)
+    return P.resize_bicubic_u8(t, hw[0], hw[1], flip).unsqueeze(1)
+
+
+def _no_flip(n, device):
+    return torch.zeros(n, dtype=torch.uint8, device=device)
+
+
+def labelled_samples(store, dataset_key):
+    """[(user, row)] of every labelled frame of a split, in the store's order."""
+    out = []
+    for user in store[dataset_key].keys():
+        g = store[dataset_key][user]
+        if 'images_ss' in g and 'labels_ss' in g:
+            out += [(user, i) for i in range(g['labels_ss'].shape[0])]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ eval
+def evaluate(net, store, dataset_key, opt, device='cuda', verbose=True):
+    """mIoU, per-class IoU and pixel accuracy of `net` on the labelled frames of a split, the masks taken at the frames' own size.
+    -> {'miou/<key>', 'iou/<key>/<c>', 'acc/<key>'}; the confusion matrix stays on the device until every batch is in."""
+    from .ops import segment as S
+    ncls = int(opt.label_nc)
+    conf = torch.zeros(ncls, ncls, dtype=torch.int64, device=device)
+    samples = labelled_samples(store, dataset_key)
+    if not samples:
+        raise ValueError("evaluate('%s'): the split has no labelled frames (images_ss / labels_ss)" % dataset_key)
+    with torch.no_grad():
+        for b0 in range(0, len(samples), int(opt.batchSize)):
+            batch = samples[b0:b0 + int(opt.batchSize)]
+            frames = np.stack([np.asarray(store[dataset_key][u]['images_ss'][i], dtype=np.uint8) for u, i in batch])
+            truth = np.stack([np.asarray(store[dataset_key][u]['labels_ss'][i], dtype=np.uint8) for u, i in batch])
+            logits = net(_frames_to_input(frames, opt.seg_hw, _no_flip(len(batch), device), device))
+            pred = S.seg_argmax_u8(logits, truth.shape[1], truth.shape[2])
+            S.seg_confusion(pred, torch.from_numpy(truth).to(device), ncls, out=conf)
+    scores = S.segment_scores(conf)
+    out = {'miou/%s' % dataset_key: scores['miou'], 'acc/%s' % dataset_key: scores['acc']}
+    out.update({'iou/%s/%d' % (dataset_key, c): float(v) for c, v in enumerate(scores['iou'])})
+    if verbose:
+        print(' '.join('%s %.4f' % (k, v) for k, v in out.items()))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ train
+def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True):
+    """Train on every labelled frame of /train, in a shuffled order seeded by opt.seed, for opt.niter epochs; after every epoch score
+    /validation (when the store has it) and save `<epoch>_net_S.pth` and `latest_net_S.pth`.  net: a network to go on from (default: a
+    new one).  -> (net, {'loss': [one float per step], 'scores': [one dict per epoch]})."""
+    from . import checkpoint
+    from .optim import FlatAdam
+    from .ops import preprocess as P, segment as S
+    if net is None:
+        net = build_network(opt, device)
+    samples = labelled_samples(store, 'train')
+    if not samples:
+        raise ValueError('train_segmenter: /train has no labelled frames (images_ss / labels_ss)')
+    ncls = int(opt.label_nc)
+    cw = [1.0] * ncls if opt.class_weights is None else [float(v) for v in opt.class_weights]
+    if len(cw) != ncls:
+        raise ValueError('--class_weights: %d values for %d classes' % (len(cw), ncls))
+    weights = torch.tensor(cw, dtype=torch.float32, device=device)
+    optimizer = FlatAdam(list(net.parameters()), lr=float(opt.lr), betas=(0.9, 0.999))
+    rng = np.random.RandomState(int(opt.seed))
+    bs = int(opt.batchSize)
+    losses, history, seen = [], {'loss': [], 'scores': []}, 0
+    for epoch in range(1, int(opt.niter) + 1):
+        order = rng.permutation(len(samples))
+        for b0 in range(0, len(order), bs):
+            batch = [samples[j] for j in order[b0:b0 + bs]]
+            frames = np.stack([np.asarray(store['train'][u]['images_ss'][i], dtype=np.uint8) for u, i in batch])
+            labels = np.stack([np.asarray(store['train'][u]['labels_ss'][i], dtype=np.uint8) for u, i in batch])
+            flip = _no_flip(len(batch), device) if opt.no_flip else torch.from_numpy((rng.rand(len(batch)) < 0.5).astype(np.uint8)).to(device)
+            x = _frames_to_input(frames, opt.seg_hw, flip, device)
+            y = P.resize_nearest_u8(torch.from_numpy(labels).to(device), opt.seg_hw[0], opt.seg_hw[1], flip)
+            optimizer.zero_grad()
+            loss = S.seg_cross_entropy(net(x), y, weights)
+            loss.backward()
+            optimizer.step()
+            losses.append(loss.detach())
+            if verbose and len(losses) - seen >= int(opt.print_freq):
+                recent = torch.stack(losses[seen:]).cpu().tolist()          # (one copy per print_freq steps)
+                history['loss'] += recent
+                seen = len(losses)
+                print('epoch %d step %d loss %.4f' % (epoch, seen, sum(recent) / len(recent)))
+        if 'validation' in store and labelled_samples(store, 'validation'):
+            history['scores'].append(evaluate(net, store, 'validation', opt, device, verbose))
+        if save:
+            checkpoint.save_network(net, 'S', epoch, opt)
+            checkpoint.save_network(net, 'S', 'latest', opt)
+    if len(losses) > seen:
+        history['loss'] += torch.stack(losses[seen:]).cpu().tolist()
+    return net, history
+
+
+# ------------------------------------------------------------------------------------------------ predict
+def predict_masks(net, store, dataset_key, opt, keys=PRED_KEYS, device='cuda'):
+    """-> {dataset_key: {user: {'labels_pred_gen': uint8 (n, 640, 400), 'labels_pred_seq': ...}}}: the mask of every row of the listed
+    image keys a person has, row-aligned with the images -- what `style_rank.rank_styles(..., seg_store=...)` takes and what
+    `prepare_openeds.save_store` writes for `style_rank --seg_file`."""
+    from .ops import segment as S
+    out = {}
+    bs = int(opt.batchSize)
+    with torch.no_grad():
+        for user in store[dataset_key].keys():
+            g = store[dataset_key][user]
+            out[user] = {}
+            for key in keys:
+                if key not in g:
+                    continue
+                n, H, W = g[key].shape
+                masks = np.zeros((n, H, W), dtype=np.uint8)
+                for r0 in range(0, n, bs):
+                    frames = _rows(g[key], range(r0, min(r0 + bs, n)))
+                    logits = net(_frames_to_input(frames, opt.seg_hw, _no_flip(len(frames), device), device))
+                    masks[r0:r0 + len(frames)] = S.seg_argmax_u8(logits, H, W).cpu().numpy()
+                out[user][pred_name(key)] = masks
+    return {dataset_key: out}
+
+
+# ------------------------------------------------------------------------------------------------ the command line
+def _open(path):
+    if path.endswith('.npz'):
+        from .prepare_openeds import load_store
+        return load_store(path)
+    import h5py
+    return h5py.File(path, 'r')
+
+
+def _load(opt, which_epoch, device):
+    from . import checkpoint
+    return checkpoint.load_network(build_network(opt, device), 'S', which_epoch, opt)
+
+
+def _csv(kind):
+    return lambda s: tuple(kind(v) for v in s.split(','))
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog='python -m seg2eye_amd.segment', description='Train, score and apply the eye segmenter (the masks of style_rank --seg_file).')
+    common = argparse.ArgumentParser(add_help=False)
+    common.add_argument('--dataroot', required=True, help='the store prepare_openeds wrote (.h5, or .npz without h5py)')
+    common.add_argument('--name', default='segmenter', help='the checkpoints live in <checkpoints_dir>/<name>')
+    common.add_argument('--checkpoints_dir', default='./checkpoints')
+    common.add_argument('--nsf', type=int, default=32, help='# of filters of the first conv layer (a multiple of 8)')
+    common.add_argument('--seg_hw', type=_csv(int), default=(320, 200), help='H,W the frames are resized to (multiples of 8)')
+    common.add_argument('--label_nc', type=int, default=4)
+    common.add_argument('--compute_dtype', default='bf16', choices=['bf16', 'fp32'])
+    common.add_argument('--batchSize', type=int, default=16)
+    sub = ap.add_subparsers(dest='command', required=True)
+    t = sub.add_parser('train', parents=[common], help='train on the labelled frames of /train')
+    t.add_argument('--niter', type=int, default=20, help='epochs')
+    t.add_argument('--lr', type=float, default=1e-3)
+    t.add_argument('--class_weights', type=_csv(float), default=None, help='one weight per class, e.g. 1,1,1,1')
+    t.add_argument('--seed', type=int, default=0)
+    t.add_argument('--no_flip', action='store_true', help='no horizontal flip of the training frames')
+    t.add_argument('--print_freq', type=int, default=50, help='steps between two lines of the running loss')
+    e = sub.add_parser('eval', parents=[common], help='mIoU of a checkpoint on the labelled frames of a split')
+    p = sub.add_parser('predict', parents=[common], help='write the masks of the unlabelled frames of a split')
+    for s in (e, p):
+        s.add_argument('--dataset_key', default='validation' if s is e else 'train', choices=['train', 'validation', 'test'])
+        s.add_argument('--which_epoch', default='latest')
+    p.add_argument('--out', required=True, help='the file style_rank --seg_file opens (HDF5; <out>.npz without h5py)')
+    p.add_argument('--keys', type=_csv(str), default=PRED_KEYS, help='image keys to segment, e.g. images_gen,images_seq')
+    return ap
+
+
+def main(argv=None):
+    a = vars(parser().parse_args(argv))
+    command, dataroot = a.pop('command'), a.pop('dataroot')
+    which_epoch, dataset_key, out, keys = a.pop('which_epoch', None), a.pop('dataset_key', None), a.pop('out', None), a.pop('keys', None)
+    opt = seg_options(**a)
+    store = _open(dataroot)
+    if command == 'train':
+        train_segmenter(store, opt)
+    elif command == 'eval':
+        return evaluate(_load(opt, which_epoch, 'cuda'), store, dataset_key, opt)
+    else:
+        from .prepare_openeds import save_store
+        masks = predict_masks(_load(opt, which_epoch, 'cuda'), store, dataset_key, opt, keys=keys)
+        print('masks of %d persons written to %s' % (len(masks[dataset_key]), save_store(masks, out)))
+
+
+if __name__ == '__main__':
+    main()

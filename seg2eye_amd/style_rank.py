@@ -14,11 +14,12 @@ when `use_seq` by `images_seq`, subset b's', whose indices are offset by the num
                         only where `seg_store` holds their masks
   'train', 'validation' the generative and sequence frames are unlabelled (as they were for the reference's authors): their masks come
                         from `seg_store`: /{subset}/{user}/{labels_pred_gen, labels_pred_seq} uint8 (n, 640, 400), row-aligned with
-                        the images, from any segmentation network
+                        the images -- what `python -m seg2eye_amd.segment predict` writes
 A candidate whose file name equals the target's is excluded (where the store names the candidates: `<images key>_filenames`), so a
 target is never its own style.  The distances (`ops.mask_distances`) and the selection (`ops.rank_topk`) run on the GPU; a person's
 candidates are uploaded in chunks of at most UPLOAD_BYTES.
 
+    python -m seg2eye_amd.segment predict --dataroot openeds.h5 --name seg --dataset_key train --out masks.h5
     python -m seg2eye_amd.style_rank --dataroot openeds.h5 --dataset_key train --seg_file masks.h5 --out style_refs.h5
 
 `save_refs` / `load_refs` mirror prepare_openeds.save_store / load_store: HDF5 when h5py is installed, else `.npz` with '/'-joined
@@ -159,7 +160,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description='Write the --style_ref ranking of an OpenEDS store.')
     ap.add_argument('--dataroot', required=True, help='the store prepare_openeds wrote (.h5, or .npz without h5py)')
     ap.add_argument('--dataset_key', default='train', choices=['train', 'validation', 'test'])
-    ap.add_argument('--seg_file', default=None, help='predicted masks of the unlabelled frames: /{subset}/{user}/{labels_pred_gen, labels_pred_seq}')
+    ap.add_argument('--seg_file', default=None, help='predicted masks of the unlabelled frames, /{subset}/{user}/{labels_pred_gen, labels_pred_seq}: the file '
+                                                     '`python -m seg2eye_amd.segment predict --out` writes')
     ap.add_argument('--top', type=int, default=100, help='entries kept per target (ref_randomN needs N)')
     ap.add_argument('--rank_metric', default='l2', choices=['l2', 'mismatch'])
     ap.add_argument('--no_seq', action='store_true', help='rank the generative frames only')
