@@ -144,6 +144,23 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// the fp64 form the loss and metric kernels take their per-workgroup partials with: the same xor butterfly, 32 down to
+// 1, the total in every lane.  The order of these adds is part of every result that goes through them.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// a 256-thread block's sum of v (fp64), valid in thread 0: the lanes by the butterfly above, then the four waves as
+// ((r0 + r1) + r2) + r3.  That order is part of the result: another association gives other bits.  red: four doubles of LDS; one
+// barrier.  (The butterfly is written out, not a call of wave_sum: through the call its users schedule one instruction elsewhere.)
+__device__ __forceinline__ double block_sum4(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
 
 // sum over the 64 lanes in six DPP adds (VALU only, unlike the ds_bpermute butterflies above); the total is valid in LANE 63 only
 __device__ __forceinline__ float wave_sum_last(float v) {
@@ -202,6 +219,15 @@ static inline int s2e_k_tile(int dtype) { return dtype == S2E_BF16 ? 64 : 32; } 
 // 256-thread blocks for n items of a grid-stride kernel, at most cap
 static inline int s2e_grid1d(long n, int cap = 8192) { const long b = (n + 255) / 256; return (int)(b < cap ? b : cap); }
 static inline int s2e_pow2_shift(int v) { for (int b = 0; b < 31; ++b) if ((1 << b) == v) return b; return -1; }   // log2 of a power of two, else -1
+// a caller's buffer (what: a string literal, "workspace") of `have` bytes where the launch needs `need`
+#define S2E_CHECK_BYTES(name, what, have, need) do { if ((have) < (need)) \
+    S2E_FAIL(S2E_ERR_ARG, "%s: " what " of %zu bytes, needs %zu", name, (size_t)(have), (size_t)(need)); } while (0)
+// N single-channel H x W images, one grid.y per image and 32-bit pixel indices over the batch
+static inline int s2e_check_image_batch(const char* name, int N, int H, int W) {
+    if (N > 65535 || (long)N * H * W >= (1L << 31))
+        S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: N=%d H=%d W=%d is beyond the launch limits (N <= 65535, N H W < 2^31)", name, N, H, W);
+    return S2E_OK;
+}
 
 // S2E_DETERMINISTIC=1 (read once per process): every gradient of the train step is summed in a fixed order -- the generic weight
 // gradient's partial tiles for every split launch, one reduction pass instead of several combined with float atomics, the patch

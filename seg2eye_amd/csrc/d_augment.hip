@@ -1,7 +1,7 @@
 // Differentiable augmentation of the discriminator's input: the (2N,H,W,8) [one-hot | image | 0] tensor of
 // s2e_onehot_nhwc's cpad == 8 path, written through a per-sample colour / translation / cutout transform.  HBM- and launch-bound:
 // one lane per pixel, the 8 channels as one (bf16) or two (fp32) 16-byte stores; the per-sample sums go through per-block fp64
-// partials (plain stores) that the consuming launch folds in a fixed order -- no atomics, the same input gives the same bits.
+// partials that the consuming launch folds.
 #include "common.h"
 
 constexpr int AUG_PPB = 2048;                             // pixels per partial-sum block: 8 per thread
@@ -33,14 +33,6 @@ __device__ __forceinline__ bool aug_visible(const AugRow& r, int y, int x, int H
     return inside && !cut;
 }
 
-// the block's sum of v (fp64), valid in thread 0: lanes by shuffles, then the four waves in order
-__device__ __forceinline__ double aug_block_sum(double v, double* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
 // sum of the P partials of image `img` in index order (fp64), the same value in every thread of the block
 __device__ __forceinline__ double aug_fold(const double* __restrict__ part, int img, int P, double* sh) {
     if (threadIdx.x == 0) {
@@ -67,7 +59,7 @@ __global__ __launch_bounds__(256) void aug_mean_kernel(const T* __restrict__ fak
         a += load1<T>(src + i);
         if (++k == 8) { s += (double)a; a = 0.f; k = 0; }
     }
-    s = aug_block_sum(s + (double)a, sh);
+    s = block_sum4(s + (double)a, sh);
     if (threadIdx.x == 0) part[(size_t)img * gridDim.x + blockIdx.x] = s;
 }
 
@@ -125,7 +117,7 @@ __global__ __launch_bounds__(256) void aug_gsum_kernel(const T* __restrict__ g, 
         if (aug_visible(r, y, x, H, W, sy, sx)) a += load1<T>(gs + (size_t)pix * 8);
         if (++k == 8) { s += (double)a; a = 0.f; k = 0; }
     }
-    s = aug_block_sum(s + (double)a, sh);
+    s = block_sum4(s + (double)a, sh);
     if (threadIdx.x == 0) part[(size_t)n * gridDim.x + blockIdx.x] = s;
 }
 

@@ -253,12 +253,12 @@ struct FfColFwd {
             }
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o, 64); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }
+        for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o, 64); mx = fmaxf(mx, __shfl_xor(mx, o, 64)); }     // (wave_sum's adds, interleaved with the max: apart, the kernel compiles to other code)
         if ((threadIdx.x & 63) == 0) { redd[threadIdx.x >> 6] = sum; redf[threadIdx.x >> 6] = mx; }
         __syncthreads();
         if (threadIdx.x == 0) {
             const size_t b = (size_t)img * gridDim.y * gridDim.x + (size_t)mt * gridDim.x + nt;
-            part[b] = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+            part[b] = (redd[0] + redd[1]) + (redd[2] + redd[3]);           // not block_sum4's ((r0 + r1) + r2) + r3, on purpose: changing it changes bits
             pmax[b] = fmaxf(fmaxf(redf[0], redf[1]), fmaxf(redf[2], redf[3]));
         }
     }
@@ -351,8 +351,6 @@ inline FflWs ffl_ws(int N, const FflGeom& g) {
     return w;
 }
 
-#define FF_CHECK_BYTES(what, have, need) do { if ((have) < (need)) S2E_FAIL(S2E_ERR_ARG, "%s: " what " of %zu bytes, needs %zu", name, (size_t)(have), (size_t)(need)); } while (0)
-
 int ffl_check_hw(const char* name, int H, int W) {
     if (H < 2 || W < 2 || H > FF_MAX || W > FF_MAX)
         S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: H=%d W=%d (2 to %d rows and columns expected)", name, H, W, FF_MAX);
@@ -364,10 +362,9 @@ int ffl_check(const char* name, int N, int H, int W, float alpha, size_t tables_
     if (!(alpha >= 0.f) || !__builtin_isfinite(alpha) || alpha > FF_MAX_ALPHA)
         S2E_FAIL(S2E_ERR_ARG, "%s: alpha=%g (a finite number in [0, %g] expected)", name, (double)alpha, (double)FF_MAX_ALPHA);
     if (const int rc = ffl_check_hw(name, H, W)) return rc;
-    if (N > 65535 || (long)N * H * W >= (1L << 31))
-        S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: N=%d H=%d W=%d is beyond the launch limits (N <= 65535, N H W < 2^31)", name, N, H, W);
-    FF_CHECK_BYTES("tables", tables_bytes, s2e_ffl_tables_bytes(H, W));
-    FF_CHECK_BYTES("workspace", ws_bytes, s2e_ffl_workspace_bytes(N, H, W));
+    if (const int rc = s2e_check_image_batch(name, N, H, W)) return rc;
+    S2E_CHECK_BYTES(name, "tables", tables_bytes, s2e_ffl_tables_bytes(H, W));
+    S2E_CHECK_BYTES(name, "workspace", ws_bytes, s2e_ffl_workspace_bytes(N, H, W));
     return S2E_OK;
 }
 
@@ -375,7 +372,7 @@ template <typename T>
 int ffl_fwd_launch(const char* name, const T* x, const T* y, int N, int H, int W, float alpha, const float* tables, size_t tables_bytes, float* ffl,
                    float* coef, float* spectrum, size_t spectrum_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
     if (const int rc = ffl_check(name, N, H, W, alpha, tables_bytes, ws_bytes)) return rc;
-    if (spectrum) FF_CHECK_BYTES("spectrum", spectrum_bytes, s2e_ffl_spectrum_bytes(N, H, W));
+    if (spectrum) S2E_CHECK_BYTES(name, "spectrum", spectrum_bytes, s2e_ffl_spectrum_bytes(N, H, W));
     const FflGeom g = ffl_geom(H, W);
     const FflWs w = ffl_ws(N, g);
     const float* ch = tables;
@@ -417,7 +414,7 @@ extern "C" int s2e_ffl_tables(int H, int W, float* tables, size_t tables_bytes, 
     const char* name = "s2e_ffl_tables";
     if (!tables) S2E_FAIL(S2E_ERR_ARG, "s2e_ffl_tables: bad argument");
     if (const int rc = ffl_check_hw(name, H, W)) return rc;
-    FF_CHECK_BYTES("tables", tables_bytes, s2e_ffl_tables_bytes(H, W));
+    S2E_CHECK_BYTES(name, "tables", tables_bytes, s2e_ffl_tables_bytes(H, W));
     const FflGeom g = ffl_geom(H, W);
     ffl_tables_kernel<<<s2e_grid1d((long)ffl_table_floats(g), 1024), 256, 0, (hipStream_t)stream>>>(tables, g);
     S2E_CHECK_LAUNCH("ffl_tables_kernel");

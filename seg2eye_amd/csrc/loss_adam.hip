@@ -340,17 +340,11 @@ extern "C" int s2e_adam_flat_ema_guarded(float* p, const float* g, float* m, flo
 
 // ---- the gradient guard (optim.FlatAdam(clip_norm=..., skip_nonfinite=...)): one pass over the gradient arena that yields its global
 // norm and the first non-finite element, and from them the coefficient the guarded Adam launches above apply (record layout and
-// rule: seg2eye_hip.h).  TWO launches and no atomics: a last-arriving block would need an agent-scope release in every block, which
-// writes back the XCD's L2 on this chip -- the split-K finish passes are separate launches for the same reason.
+// rule: seg2eye_hip.h).  Two launches, partials then their fold: DESIGN 8 #3.
 // The sum of squares is fp64 from the first product on: a finite gradient never overflows it (3e19^2 does overflow fp32), and the
 // rounding error of the whole sum stays below the one rounding of the result to fp32.
 struct GuardPartial { double sumsq; int first_bad; int pad; };      // one per block of the partial launch, in the caller's workspace
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ int wave_min_i32(int v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
@@ -360,7 +354,7 @@ __device__ __forceinline__ int wave_min_i32(int v) {
 __device__ __forceinline__ void guard_block_combine(double& s, int& bad) {
     __shared__ double red_s[4];
     __shared__ int red_b[4];
-    s = wave_sum_f64(s);
+    s = wave_sum(s);
     bad = wave_min_i32(bad);
     if ((threadIdx.x & 63) == 0) { red_s[threadIdx.x >> 6] = s; red_b[threadIdx.x >> 6] = bad; }
     __syncthreads();

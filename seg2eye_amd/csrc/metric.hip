@@ -15,7 +15,7 @@ namespace {
 __device__ __forceinline__ int to255(float x) { return (int)(((x + 1.f) * 255.f) / 2.f); }
 
 __device__ __forceinline__ unsigned long long block_sum_u64(unsigned long long v, unsigned long long* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);     // (common.h's butterfly, written out: through a shared u64 wave_sum the three error kernels compile to other code)
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) red[wave] = v;
     __syncthreads();

@@ -162,7 +162,7 @@ __global__ __launch_bounds__(256) void msssim_fwd_kernel(const T* __restrict__ x
             }
         }
     }
-    const double s = ssim_block_sum(acc, red);
+    const double s = block_sum4(acc, red);
     if (threadIdx.x == 0) part[(size_t)n * t.total + tile] = s;
 }
 
@@ -313,20 +313,16 @@ int ms_check(const char* name, int N, int H, int W, int levels, const float* wei
     if (Hl < SS_TAPS || Wl < SS_TAPS)
         S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: H=%d W=%d levels=%d (level %d is %d x %d: smaller than the 11 x 11 window, it has no position)", name, H, W,
                  levels, levels - 1, Hl, Wl);
-    if (N > 65535 || (long)N * H * W >= (1L << 31))
-        S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: N=%d H=%d W=%d is beyond the launch limits (N <= 65535, N H W < 2^31)", name, N, H, W);
-    return S2E_OK;
+    return s2e_check_image_batch(name, N, H, W);
 }
-
-#define MS_CHECK_BYTES(what, have, need) do { if ((have) < (need)) S2E_FAIL(S2E_ERR_ARG, "%s: " what " of %zu bytes, needs %zu", name, (size_t)(have), (size_t)(need)); } while (0)
 
 template <typename T>
 int msssim_fwd_launch(const char* name, const T* x, const T* y, int N, int H, int W, int levels, const float* weights, float* msssim, float* terms,
                       float* coef, float* maps, size_t maps_bytes, void* pyr, size_t pyr_bytes, void* ws, size_t ws_bytes, hipStream_t st) {
     if (const int rc = ms_check(name, N, H, W, levels, weights)) return rc;
-    MS_CHECK_BYTES("workspace", ws_bytes, s2e_msssim_workspace_bytes(N, H, W, levels));
-    MS_CHECK_BYTES("pyramid", pyr ? pyr_bytes : 0, s2e_msssim_pyramid_bytes(N, H, W, levels));
-    if (maps) MS_CHECK_BYTES("maps", maps_bytes, s2e_msssim_maps_bytes(N, H, W, levels));
+    S2E_CHECK_BYTES(name, "workspace", ws_bytes, s2e_msssim_workspace_bytes(N, H, W, levels));
+    S2E_CHECK_BYTES(name, "pyramid", pyr ? pyr_bytes : 0, s2e_msssim_pyramid_bytes(N, H, W, levels));
+    if (maps) S2E_CHECK_BYTES(name, "maps", maps_bytes, s2e_msssim_maps_bytes(N, H, W, levels));
     const MsGeom g = ms_geom(N, H, W, levels);
     const MsTable t = ms_table(g, true);
     MsWeights wt{};
@@ -385,7 +381,7 @@ extern "C" int s2e_msssim_bwd(int dtype, const void* x, const void* y, const voi
     if (const int rc = ms_check(name, N, H, W, levels, nullptr)) return rc;
     const size_t need = s2e_msssim_pyramid_bytes(N, H, W, levels) / 2;
     if (need && !pyramid) S2E_FAIL(S2E_ERR_ARG, "s2e_msssim_bwd: bad argument");
-    MS_CHECK_BYTES("gradient buffer", gbuf ? gbuf_bytes : 0, need);
+    S2E_CHECK_BYTES(name, "gradient buffer", gbuf ? gbuf_bytes : 0, need);
     const MsGeom g = ms_geom(N, H, W, levels);
     const MsTable t = ms_table(g, false);
     hipStream_t st = (hipStream_t)stream;

@@ -65,13 +65,6 @@ __device__ __forceinline__ void rg_load(const T* xs, const T* ys, const RgLabel&
     }
 }
 
-// the wave's sum of v in every lane, by a fixed butterfly
-__device__ __forceinline__ double rg_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------- forward: partial records
 // grid (blocks along the image, N).  part[n][block][c][3] = {count, sum |d|, sum d^2} of the block's pixels of class c < ncls.
 // d, |d| and d^2 are fp32 from the loaded values (exact integers for uint8); every sum over pixels is fp64.
@@ -110,7 +103,7 @@ __global__ __launch_bounds__(256) void region_part_kernel(const T* __restrict__ 
 #pragma unroll
     for (int c = 0; c < RG_MAXC; ++c) {
         if (c < ncls) {
-            const double t0 = rg_wave_sum(cnt[c]), t1 = rg_wave_sum(s1[c]), t2 = rg_wave_sum(s2[c]);
+            const double t0 = wave_sum(cnt[c]), t1 = wave_sum(s1[c]), t2 = wave_sum(s2[c]);
             if ((threadIdx.x & 63) == 0) { red[wave][c][0] = t0; red[wave][c][1] = t1; red[wave][c][2] = t2; }
         }
     }
@@ -213,8 +206,7 @@ template <typename T>
 int region_fwd_launch(const char* name, const T* x, const T* y, const uint8_t* label, int N, int H, int W, int Hl, int Wl, int ncls, int norm,
                       const float* weights, double* stats, float* loss, float* coef, void* ws, size_t ws_bytes, hipStream_t st) {
     if (const int rc = region_check_size(name, N, H, W, Hl, Wl, ncls)) return rc;
-    const size_t need = s2e_region_workspace_bytes(N, H, W, ncls);
-    if (ws_bytes < need) S2E_FAIL(S2E_ERR_ARG, "%s: workspace of %zu bytes, needs %zu", name, ws_bytes, need);
+    S2E_CHECK_BYTES(name, "workspace", ws_bytes, s2e_region_workspace_bytes(N, H, W, ncls));
     const int B = (int)rg_blocks((long)H * W);
     region_part_kernel<T><<<dim3(B, N), 256, 0, st>>>(x, y, label, (double*)ws, H, W, Hl, Wl, ncls, rg_small(H, W, Hl, Wl));
     S2E_CHECK_LAUNCH("region_part_kernel");

@@ -86,12 +86,6 @@ __device__ __forceinline__ float seg_softmax_terms(const float* z, int ncls, flo
     return s;
 }
 
-__device__ __forceinline__ double seg_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------- cross-entropy
 // grid (blocks <= SEG_CE_BLOCKS), 256 threads, a grid-stride walk of the P pixels.  part[2 b] = the workgroup's sum of w (lse - z_l),
 // part[2 b + 1] = its sum of w, over the pixels whose label is < ncls.
@@ -130,8 +124,8 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_ce_fwd_kernel(const T* __rest
             den += w;
         }
     }
-    num = seg_wave_sum(num);
-    den = seg_wave_sum(den);
+    num = wave_sum(num);
+    den = wave_sum(den);
     const int wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { red[0][wave] = num; red[1][wave] = den; }
     __syncthreads();

@@ -1,7 +1,7 @@
 // Structural similarity (SSIM, Wang et al. 2004) of two single-channel image batches and its gradient: an 11-tap
 // Gaussian window (sigma 1.5), "valid" placement, data range 1.  Separable: a workgroup stages one (T + 10)^2 tile in LDS, runs the
-// horizontal 11-tap pass into LDS and the vertical pass per output.  Two launches forward (tiles, then a fold of the per-tile fp64
-// partial sums in index order), one backward; no atomics, launch shapes from (N, H, W) alone, the same input gives the same bits.
+// horizontal 11-tap pass into LDS and the vertical pass per output.  Two launches forward (tiles, then the fold of the per-tile fp64
+// partials: DESIGN 8 #3), one backward; launch shapes from (N, H, W) alone.
 //
 // Cancellation.  sigma^2 = E[u^2] - mu^2 loses everything in fp32 on a bright flat region.  The variances and the covariance do not
 // change when a constant is subtracted from u and v, so every tile takes its moments about its own first pixel (cu, cv): the staged
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_kernel(const T* __restrict__ x, 
             }
         }
     }
-    const double s = ssim_block_sum(acc, red);
+    const double s = block_sum4(acc, red);
     if (threadIdx.x == 0) part[(size_t)n * gridDim.x + tile] = s;
 }
 
@@ -124,16 +124,14 @@ __global__ __launch_bounds__(256) void ssim_bwd_kernel(const T* __restrict__ x, 
 // the size checks every entry shares, after its own pointer checks: S2E_ERR_UNSUPPORTED
 int ssim_check_size(const char* name, int N, int H, int W) {
     if (H < SS_TAPS || W < SS_TAPS) S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: H=%d W=%d (an image smaller than the 11 x 11 window has no position)", name, H, W);
-    if (N > 65535 || (long)N * H * W >= (1L << 31) || ssim_tiles(H, W) >= (1L << 31))
-        S2E_FAIL(S2E_ERR_UNSUPPORTED, "%s: N=%d H=%d W=%d is beyond the launch limits (N <= 65535, N H W < 2^31)", name, N, H, W);
-    return S2E_OK;
+    return s2e_check_image_batch(name, N, H, W);           // (with N >= 1, N H W < 2^31 bounds the tiles of the grid.x too: tiles <= H W)
 }
 
 template <typename T>
 int ssim_fwd_launch(const char* name, const T* x, const T* y, int N, int H, int W, float* ssim, float* maps, void* ws, size_t ws_bytes,
                     hipStream_t st) {
     if (const int rc = ssim_check_size(name, N, H, W)) return rc;
-    if (ws_bytes < s2e_ssim_workspace_bytes(N, H, W)) S2E_FAIL(S2E_ERR_ARG, "%s: workspace of %zu bytes, needs %zu", name, ws_bytes, s2e_ssim_workspace_bytes(N, H, W));
+    S2E_CHECK_BYTES(name, "workspace", ws_bytes, s2e_ssim_workspace_bytes(N, H, W));
     const int Ho = H - SS_R, Wo = W - SS_R, tiles = (int)ssim_tiles(Ho, Wo);
     ssim_fwd_kernel<T><<<dim3(tiles, N), 256, 0, st>>>(x, y, ssim_window(), (double*)ws, maps, N, H, W, (int)ssim_tiles_x(Wo));
     S2E_CHECK_LAUNCH("ssim_fwd_kernel");

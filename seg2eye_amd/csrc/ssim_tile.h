@@ -1,5 +1,5 @@
-// What ssim.hip and msssim.hip share: the 11-tap window, the 16 x 32 tile, what a loaded number means, the block's
-// fp64 sum and the two separable passes over a staged (T + 10)^2 tile, forward (five products) and backward (three maps).  Every LDS pass
+// What ssim.hip and msssim.hip share: the 11-tap window, the 16 x 32 tile, what a loaded number means
+// and the two separable passes over a staged (T + 10)^2 tile, forward (five products) and backward (three maps).  Every LDS pass
 // has a half-wave on 32 consecutive words of one row: no bank conflicts.
 #pragma once
 #include "common.h"
@@ -25,15 +25,6 @@ template <> struct SsimIn<uint8_t> {
     static __device__ __forceinline__ float centre(float xc) { return xc / 255.f; }
     static __device__ __forceinline__ float delta(float x, float xc) { return (x - xc) / 255.f; }
 };
-
-// the block's sum of v (fp64), valid in thread 0: lanes by shuffles, then the four waves in order
-__device__ __forceinline__ double ssim_block_sum(double v, double* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // stage the 26 x 42 tile whose first pixel is (ty0, tx0) of two H x W images stored as X, in In's units, about (xc, yc): rows of 42
 // consecutive elements; past the image: zero, read by no valid output.  No barrier.

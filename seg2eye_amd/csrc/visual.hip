@@ -12,9 +12,8 @@
 //
 // Launch 1 reduces min / max of the four resized tensors, launch 2 max|fk - tg| with the norm branches decided on the device from
 // launch 1's values, launch 3 composes.  No host synchronisation or branch in between; each launch recomputes its bilinear samples
-// (four loads and a few fp64 operations).  fp64 min / max do not depend on the order, so the reduction is deterministic whatever its
-// tree: inside the workgroup, then one partial per workgroup in `ws`, which every workgroup of the next launch folds itself -- no
-// atomics, no last-arriver scheme, no fences.  Every value operation is a separate IEEE operation (no contraction), in the order the
+// (four loads and a few fp64 operations).  One partial per workgroup in `ws`, which every workgroup of the next launch folds itself
+// (DESIGN 8 #3); fp64 min / max do not depend on the order, so here the tree is not part of the result.  Every value operation is a separate IEEE operation (no contraction), in the order the
 // reference's torch / numpy calls perform them, so the bytes agree with the CPU restatement exactly.
 #include "common.h"
 #pragma clang fp contract(off)
