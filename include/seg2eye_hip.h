@@ -809,6 +809,50 @@ int s2e_seg_ce_bwd(int dtype, const void* logits, const uint8_t* label, const fl
 int s2e_seg_argmax_u8(int dtype, const void* logits, int N, int h, int w, int C, int ncls, int Ho, int Wo, uint8_t* mask, void* stream);
 int s2e_seg_confusion_u8(const uint8_t* pred, const uint8_t* truth, long P, int ncls, int64_t* conf, void* stream);
 
+/* ------------------------------------------------------------------ eye segmenter: distance maps and the boundary-aware loss
+ * logits, label and ncls as in the section above.  Everything is per image: distances never cross images and the frame edge is no
+ * boundary.  No atomics: the same input gives the same bits.
+ *   s2e_seg_dist_maps: for pixel p and class c let m be the smallest squared integer distance |p - q|^2 to a pixel q with l_q != c
+ *       when l_p == c (a label >= ncls is "not c" for every c), to a pixel q with l_q == c otherwise.  phi (N, H, W, ncls) fp32 =
+ *       1 - sqrtf(m) when l_p == c (+0 where the pixel touches another class), +sqrtf(m) otherwise, +0 for a class that is absent from
+ *       the image or fills it (Kervadec's one_hot2dist).  band (N, H, W) uint8, or NULL = 1 where l_p < ncls, the complement of its
+ *       class is not empty and its m <= radius^2 (decided on the integers), else 0.  Two launches: a column pass writes the vertical
+ *       distances as uint16 pairs into `workspace` (s2e_seg_dist_workspace_bytes(N, H, W, ncls) bytes, 4-byte aligned), a row pass
+ *       takes the minimum over the row.  rint(sqrtf(m)^2) == m over the whole supported range.
+ *       Before any launch, in this order: S2E_ERR_ARG on a null label, phi or workspace, a short or misaligned workspace (a shape
+ *       refused below needs 0 bytes), N, H or W < 1, radius < 0; S2E_ERR_UNSUPPORTED on ncls outside 1..16, H or W > 1024 (the uint16
+ *       distances and the exact-sqrt range), N > 65535 or N H W >= 2^31, N H W ncls >= 2^31.
+ *   s2e_seg_loss_fwd: with P the counted pixels, p the softmax over the first ncls channels (fp32, maximum subtracted), g the one-hot
+ *       of the label on P, b_p = 1 + edge_alpha band_p:
+ *         terms[0] CE      = sum_P w[l_p] b_p (lse_p - z_{p,l_p}) / sum_P w[l_p]                (0 when the denominator is 0)
+ *         terms[1] Dice    = mean over the images n with a counted pixel of 1 - 2 sum_c v I / sum_c v U, I_nc = sum p g,
+ *                            U_nc = sum (p + g), v_nc = 1 / G_nc^2 where G_nc = sum g > 0, else 0    (0 when there is no such image)
+ *         terms[2] Surface = sum_P sum_c p_{p,c} phi_{p,c} / (|P| ncls)                          (0 when lambda_surf is 0)
+ *         loss[0] = lambda_ce CE + lambda_dice Dice + lambda_surf Surface
+ *       phi may be NULL when lambda_surf is 0 and band when edge_alpha is 0; a term that is off reads nothing, so the call gives the
+ *       same bits with and without its input.  saved (N 2 ncls + 2 floats) takes, for the backward, per image and class
+ *       kI = -(lambda_dice / N_cnt) 2 v / D_n and kU = (lambda_dice / N_cnt) 2 A_n v / D_n^2 (A_n = sum_c v I, D_n = sum_c v U) at
+ *       saved[(n 2 + 0) ncls + c] and saved[(n 2 + 1) ncls + c], then 1 / sum_P w and 1 / (|P| ncls) (0 where the sum is 0).  Two
+ *       launches: grid.y = image, per-workgroup fp64 partials with plain stores into `workspace`
+ *       (s2e_seg_loss_workspace_bytes(N, H, W, ncls) bytes, 8-byte aligned), then one fold in index order.
+ *   s2e_seg_loss_bwd: with a_{p,c} = kI_nc [c == l_p] + kU_nc + lambda_surf saved_s phi_{p,c}:
+ *         dlogits[p][c] = gloss[0] (p_c (a_c - sum_k a_k p_k) + lambda_ce w[l_p] b_p (p_c - [c == l_p]) / sum w)
+ *       in dtype, the softmax recomputed; +0 for ignored pixels and for channels >= ncls.  One launch.
+ *       Both, before any launch, in this order: S2E_ERR_ARG on a null pointer other than phi and band, an unknown dtype, N, H, W < 1;
+ *       S2E_ERR_UNSUPPORTED on ncls outside 1..16; S2E_ERR_ARG on C < ncls; S2E_ERR_UNSUPPORTED on N H W > 2^31 - 1, N > 65535;
+ *       S2E_ERR_ARG on a negative or non-finite lambda or edge_alpha, on lambda_surf != 0 without phi, on edge_alpha != 0 without
+ *       band; then s2e_seg_loss_fwd: S2E_ERR_ARG on a missing, short or misaligned workspace. */
+size_t s2e_seg_dist_workspace_bytes(int N, int H, int W, int ncls);
+int s2e_seg_dist_maps(const uint8_t* label, int N, int H, int W, int ncls, int radius, float* phi, uint8_t* band, void* workspace,
+                      size_t workspace_bytes, void* stream);
+size_t s2e_seg_loss_workspace_bytes(int N, int H, int W, int ncls);
+int s2e_seg_loss_fwd(int dtype, const void* logits, const uint8_t* label, const float* weights, const float* phi, const uint8_t* band,
+                     int N, int H, int W, int C, int ncls, float lambda_ce, float lambda_dice, float lambda_surf, float edge_alpha,
+                     float* loss, float* terms, float* saved, void* workspace, size_t workspace_bytes, void* stream);
+int s2e_seg_loss_bwd(int dtype, const void* logits, const uint8_t* label, const float* weights, const float* phi, const uint8_t* band,
+                     const float* saved, const float* gloss, int N, int H, int W, int C, int ncls, float lambda_ce, float lambda_surf,
+                     float edge_alpha, void* dlogits, void* stream);
+
 /* ------------------------------------------------------------------ side-by-side validation panels
  * The reference's visualize_sidebyside (util/visualizer.py:131-166) for a batch of n samples, as three launches on the caller's
  * stream with no host synchronisation between them: out[i] = [ style | label | target_original | fake | heat ], five h x w cells of

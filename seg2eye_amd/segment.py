@@ -11,7 +11,7 @@ from: every person's labelled frames (`images_ss` / `labels_ss`).
 
 Frames go to the device as uint8 and are resized there (`ops.resize_bicubic_u8` to --seg_hw, fp32 in [-1, 1]; labels by
 `ops.resize_nearest_u8`; the horizontal flip of `train` is those ops' flip byte).  The network (networks/segmenter.py: EyeSegNet) gives
-logits at --seg_hw; the loss is `ops.seg_cross_entropy`, a mask is `ops.seg_argmax_u8` of the logits resized to the frame's own size,
+logits at --seg_hw; the loss is `ops.seg_cross_entropy` (or, with --lambda_dice / --lambda_surface / --edge_alpha, `ops.seg_loss`), a mask is `ops.seg_argmax_u8` of the logits resized to the frame's own size,
 the score is mIoU (the OpenEDS segmentation metric) from `ops.seg_confusion`, accumulated on the device and read back once.
 
 The three commands are plain functions too: `train_segmenter`, `evaluate`, `predict_masks`.  The ops are looked up when called."""
@@ -32,7 +32,8 @@ def pred_name(image_key):
 def seg_options(**kw):
     """The options EyeSegNet, the checkpoint names and the functions below read; keyword arguments override the defaults."""
     o = dict(nsf=32, seg_hw=(320, 200), label_nc=4, compute_dtype='bf16', batchSize=16, checkpoints_dir='./checkpoints', name='segmenter',
-             lr=1e-3, niter=20, class_weights=None, seed=0, no_flip=False, print_freq=50)
+             lr=1e-3, niter=20, class_weights=None, seed=0, no_flip=False, print_freq=50,
+             lambda_ce=1.0, lambda_dice=0.0, lambda_surface=0.0, edge_alpha=0.0, edge_radius=2)
     unknown = sorted(set(kw) - set(o))
     if unknown:
         raise TypeError('seg_options: unknown option(s) %s' % ', '.join(unknown))
@@ -107,7 +108,11 @@ def evaluate(net, store, dataset_key, opt, device='cuda', verbose=True):
 def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True):
     """Train on every labelled frame of /train, in a shuffled order seeded by opt.seed, for opt.niter epochs; after every epoch score
     /validation (when the store has it) and save `<epoch>_net_S.pth` and `latest_net_S.pth`.  net: a network to go on from (default: a
-    new one).  -> (net, {'loss': [one float per step], 'scores': [one dict per epoch]})."""
+    new one).  -> (net, {'loss': [one float per step], 'scores': [one dict per epoch]}).
+
+    With --lambda_dice, --lambda_surface or --edge_alpha set (or --lambda_ce off 1) the loss is `ops.seg_loss` on the
+    distance maps and boundary band `ops.seg_dist_maps` makes of the resized, flipped labels of the batch; the history then has
+    'terms': [[CE, Dice, Surface] per step] too, and the progress line shows their means."""
     from . import checkpoint
     from .optim import FlatAdam
     from .ops import preprocess as P, segment as S
@@ -124,7 +129,11 @@ def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True
     optimizer = FlatAdam(list(net.parameters()), lr=float(opt.lr), betas=(0.9, 0.999))
     rng = np.random.RandomState(int(opt.seed))
     bs = int(opt.batchSize)
-    losses, history, seen = [], {'loss': [], 'scores': []}, 0
+    lam = {k: float(getattr(opt, k)) for k in ('lambda_ce', 'lambda_dice', 'lambda_surface', 'edge_alpha')}
+    plain = lam == {'lambda_ce': 1.0, 'lambda_dice': 0.0, 'lambda_surface': 0.0, 'edge_alpha': 0.0}
+    losses, terms, history, seen = [], [], {'loss': [], 'scores': []}, 0
+    if not plain:
+        history['terms'] = []
     for epoch in range(1, int(opt.niter) + 1):
         order = rng.permutation(len(samples))
         for b0 in range(0, len(order), bs):
@@ -135,15 +144,27 @@ def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True
             x = _frames_to_input(frames, opt.seg_hw, flip, device)
             y = P.resize_nearest_u8(torch.from_numpy(labels).to(device), opt.seg_hw[0], opt.seg_hw[1], flip)
             optimizer.zero_grad()
-            loss = S.seg_cross_entropy(net(x), y, weights)
+            if plain:
+                loss = S.seg_cross_entropy(net(x), y, weights)
+            else:
+                phi = band = None
+                if lam['lambda_surface'] or lam['edge_alpha']:
+                    phi, band = S.seg_dist_maps(y, ncls, int(opt.edge_radius))
+                loss, t = S.seg_loss(net(x), y, weights, phi, band, **lam)
+                terms.append(t)
             loss.backward()
             optimizer.step()
             losses.append(loss.detach())
             if verbose and len(losses) - seen >= int(opt.print_freq):
                 recent = torch.stack(losses[seen:]).cpu().tolist()          # (one copy per print_freq steps)
                 history['loss'] += recent
+                line = 'epoch %d step %d loss %.4f' % (epoch, len(losses), sum(recent) / len(recent))
+                if not plain:
+                    recent_t = torch.stack(terms[seen:]).cpu()
+                    history['terms'] += recent_t.tolist()
+                    line += ' CE %.4f Dice %.4f Surface %.4f' % tuple(recent_t.mean(0).tolist())
                 seen = len(losses)
-                print('epoch %d step %d loss %.4f' % (epoch, seen, sum(recent) / len(recent)))
+                print(line)
         if 'validation' in store and labelled_samples(store, 'validation'):
             history['scores'].append(evaluate(net, store, 'validation', opt, device, verbose))
         if save:
@@ -151,6 +172,8 @@ def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True
             checkpoint.save_network(net, 'S', 'latest', opt)
     if len(losses) > seen:
         history['loss'] += torch.stack(losses[seen:]).cpu().tolist()
+        if not plain:
+            history['terms'] += torch.stack(terms[seen:]).cpu().tolist()
     return net, history
 
 
@@ -216,6 +239,11 @@ def parser():
     t.add_argument('--seed', type=int, default=0)
     t.add_argument('--no_flip', action='store_true', help='no horizontal flip of the training frames')
     t.add_argument('--print_freq', type=int, default=50, help='steps between two lines of the running loss')
+    t.add_argument('--lambda_ce', type=float, default=1.0, help='weight of the cross-entropy term')
+    t.add_argument('--lambda_dice', type=float, default=0.0, help='weight of the generalised Dice term (classes weighed by inverse squared area)')
+    t.add_argument('--lambda_surface', type=float, default=0.0, help='weight of the surface (boundary) term on signed distance maps')
+    t.add_argument('--edge_alpha', type=float, default=0.0, help='a pixel within --edge_radius of another class counts 1 + edge_alpha times in the cross-entropy')
+    t.add_argument('--edge_radius', type=int, default=2, help='width of the boundary band, in pixels of --seg_hw')
     e = sub.add_parser('eval', parents=[common], help='mIoU of a checkpoint on the labelled frames of a split')
     p = sub.add_parser('predict', parents=[common], help='write the masks of the unlabelled frames of a split')
     for s in (e, p):
