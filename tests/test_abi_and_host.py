@@ -206,6 +206,23 @@ def test_grad_block_map_is_host_only():
     assert L.s2e_weight_grads_batched(None, None, 0, 9, 0, None, None) == -1
 
 
+def test_per_layer_weight_grad_entries_refuse_more_than_64_taps():
+    """Like s2e_weight_grads_batched, the per-layer entries take at most 64 taps (the tile's LDS row) and say so before any launch:
+    -3 is S2E_ERR_UNSUPPORTED.  (P: a dummy non-null pointer, never dereferenced.)"""
+    from seg2eye_amd import _lib
+    L = _lib.lib()
+    P = 0x7000
+    assert L.s2e_weight_grads_batched(P, P, 1, 65, 0, None, None) == -3
+    assert L.s2e_last_error() == b's2e_weight_grads_batched: more than 64 taps'
+    for kh, kw in ((5, 13), (65, 1), (9, 9)):
+        assert L.s2e_unpack_weight_grad(P, P, 4, 64, kh, kw, 64, 0, None) == -3
+        assert L.s2e_last_error() == b's2e_unpack_weight_grad: more than 64 taps'
+        assert L.s2e_sn_weight_grad(P, P, P, P, P, P, P, 4, 64, kh, kw, 64, 1, None) == -3
+        assert L.s2e_last_error() == b's2e_sn_weight_grad: more than 64 taps'
+    assert L.s2e_unpack_weight_grad(None, P, 4, 64, 9, 9, 64, 0, None) == -1              # a bad argument wins over the size
+    assert L.s2e_sn_weight_grad(P, P, P, P, P, None, P, 4, 64, 9, 9, 64, 0, None) == -1
+
+
 def test_ops_refuse_cpu_tensors():
     from seg2eye_amd import ops, _lib, networks
     from seg2eye_amd.options import default_opt

@@ -3,12 +3,14 @@
 
     python tools/isa_diff.py [REV] [--allow-missing NAME ...]
 
-Both revisions of every build.SOURCES entry are compiled to device assembly with build.py's flags; the assembly
+Every build.SOURCES entry of each revision is compiled to device assembly with build.py's flags; the assembly
 is normalised (comments, .file/.ident, __hip_cuid_* lines, the zero-page symbol's name, per-file label numbers)
-and split per function symbol.  Prints the symbols that differ, are missing or are new; exit status 1 when there
-is one outside --allow-missing (a substring of the mangled name is enough).
+and split per function symbol.  Symbols are matched by name over all sources of a revision, so a kernel that moved
+to another file compares against itself.  Prints the symbols that differ, are missing or are new, with the file(s)
+they live in; exit status 1 when there is one outside --allow-missing (a substring of the mangled name is enough).
 """
 import argparse
+import ast
 import difflib
 import os
 import re
@@ -74,23 +76,29 @@ def main():
         os.makedirs(old)
         subprocess.check_call('git archive %s seg2eye_amd/csrc include | tar -x -C %s' % (args.rev, old),
                               shell=True, cwd=ROOT)
+        # the sources of REV are its own build.SOURCES; a symbol is matched by name over all of them, whichever file holds it
+        old_list = re.search(r'^SOURCES = (\[.*?\])', subprocess.check_output(
+            ['git', 'show', args.rev + ':seg2eye_amd/build.py'], cwd=ROOT).decode(), re.M | re.S).group(1)
         jobs = [(tree, src, os.path.join(tmp, '%s_%s.s' % (tag, src)))
-                for src in build.SOURCES for tag, tree in (('old', old), ('new', ROOT))]
+                for tag, tree, srcs in (('old', old, ast.literal_eval(old_list)), ('new', ROOT, build.SOURCES)) for src in srcs]
         with ThreadPoolExecutor(16) as ex:
             asm = list(ex.map(lambda j: compile_asm(*j), jobs))
+        a, b = {}, {}                                        # {symbol: (file, body)} at REV and now
+        for (tree, src, _), p in zip(jobs, asm):
+            (a if tree == old else b).update({name: (src, body) for name, body in (functions(p) if p else {}).items()})
         bad = 0
-        for i, src in enumerate(build.SOURCES):
-            a, b = (functions(p) if p else {} for p in asm[2 * i:2 * i + 2])
-            for name in sorted(set(a) | set(b)):
-                what = 'missing' if name not in b else 'new' if name not in a else 'differs' if a[name] != b[name] else None
-                if what is None:
-                    continue
-                allowed = what == 'missing' and any(x in name for x in args.allow_missing)
-                bad += not allowed
-                print('%-8s %s: %s%s' % (what, src, name, '  (allowed)' if allowed else ''))
-                if what == 'differs' and args.show:
-                    print('\n'.join(difflib.unified_diff(a[name], b[name], 'old', 'new', lineterm='', n=2)))
-            print('%s: %d symbols at %s, %d now' % (src, len(a), args.rev, len(b)), file=sys.stderr)
+        for name in sorted(set(a) | set(b), key=lambda n: ((a.get(n) or b[n])[0], n)):
+            what = 'missing' if name not in b else 'new' if name not in a else 'differs' if a[name][1] != b[name][1] else None
+            if what is None:
+                continue
+            allowed = what == 'missing' and any(x in name for x in args.allow_missing)
+            bad += not allowed
+            where = ' -> '.join(dict.fromkeys(m[name][0] for m in (a, b) if name in m))
+            print('%-8s %s: %s%s' % (what, where, name, '  (allowed)' if allowed else ''))
+            if what == 'differs' and args.show:
+                print('\n'.join(difflib.unified_diff(a[name][1], b[name][1], 'old', 'new', lineterm='', n=2)))
+        moved = sum(a[n][0] != b[n][0] for n in set(a) & set(b))
+        print('%d symbols at %s, %d now, %d in another file' % (len(a), args.rev, len(b), moved), file=sys.stderr)
     print('isa_diff vs %s: %s' % (args.rev, 'identical' if not bad else '%d difference(s)' % bad))
     return 1 if bad else 0
 
