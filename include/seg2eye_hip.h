@@ -853,6 +853,46 @@ int s2e_seg_loss_bwd(int dtype, const void* logits, const uint8_t* label, const 
                      const float* saved, const float* gloss, int N, int H, int W, int C, int ncls, float lambda_ce, float lambda_surf,
                      float edge_alpha, void* dlogits, void* stream);
 
+/* ------------------------------------------------------------------ residual refiner: input, loss, gradient, submission bytes
+ * The reference's last stage (refinenet/): the top-ranked frame of the same person plus a learned residual, clamped to [-1, 1].  These
+ * are the four memory-bound pieces around the network.  tmask, rimg, rmask, truth: (N, H, W) uint8 planes as the store holds them.
+ * flip: NULL (no flip) or N bytes, the convention of s2e_resize_bicubic_u8: flip[n] != 0 mirrors EVERY plane of image n horizontally --
+ * the pixel (y, x) of x / res / dres / out reads the planes at (y, W - 1 - x).  A frame is normalised in fp32 with two roundings,
+ *   norm(v) = fl(fl(v * fl(2 / 255)) - 1)      (refinenet/dataset.py:53-58 on a float32 array; never a fused multiply-add),
+ * in registers: no fp32 copy of a frame exists in memory, and a bf16 network's residual is added to the frame's exact fp32 value.
+ *   s2e_refine_input: x (N, H, W, C) NHWC of dtype, C >= 3: channel 0 = norm(levels[tmask]), 1 = norm(rimg), 2 = norm(levels[rmask]),
+ *       channels 3 .. C - 1 = +0; bf16 is one round-to-nearest-even of the fp32 value.  levels: ncls uint8 grey levels on the device
+ *       (the reference's class means as its uint8 array stores them: 125, 103, 76, 34); a label >= ncls takes level 0 and is never
+ *       used as an index (the reference leaves such a pixel uninitialised).  One launch.
+ *   s2e_refine_head_fwd: res (N, H, W, C) of dtype, C >= 1, channel 0 live (the others are never read).  Per pixel, in fp32,
+ *       p = clamp(fl(res + norm(rimg)), -1, 1), d = fl(p - norm(truth)); per image, in fp64, sumsq[n] = sum d^2 and
+ *       score[n] = 127.5 sqrt(sumsq[n]) / (H W)  (refinenet/model.py:52-57 per_image_score);
+ *       terms = { eds_loss = mean_n score[n],  l1 = sum |d| / (N H W),  1471 eds_loss }.  Two launches: grid.y = image, per-workgroup
+ *       fp64 partials with plain stores into `workspace` (s2e_refine_head_workspace_bytes(N, H, W) bytes, 8-byte aligned), then one
+ *       fold in index order.  No atomics: the same input gives the same bits.
+ *   s2e_refine_head_bwd: dres (N, H, W, C) of dtype; channel 0 =
+ *         m gloss[0] (lambda_eds 127.5 d / (N H W sqrt(sumsq[n])) + lambda_l1 sign(d) / (N H W)),
+ *       m = 1 where -1 <= fl(res + norm(rimg)) <= 1 (inclusive, as torch.clamp passes gradients), else 0; sign(0) = 0; the first term
+ *       is 0 for an image whose sumsq[n] is 0 (torch gives NaN there); channels 1 .. C - 1 = +0.  sumsq: what the forward wrote;
+ *       gloss: one fp32 on the device.  One launch, the prediction recomputed.
+ *   s2e_refine_predict_u8: out (N, H, W) uint8 = (uint8)fl(127.5 fl(p + 1)), TRUNCATED (refinenet/evaluate_refinenet.py:105), so a zero
+ *       residual gives back v - 1 for 47 of the 256 grey levels v.  One launch.
+ * Before any launch, in this order: S2E_ERR_ARG on a null pointer other than flip (workspace, sumsq also: not 8-byte aligned), an
+ * unknown dtype, N, H or W < 1, C below the minimum; S2E_ERR_UNSUPPORTED on H W > 2^30, N > 65535, N H W >= 2^31; then
+ * s2e_refine_input: S2E_ERR_UNSUPPORTED on ncls outside 1..16; s2e_refine_head_fwd: S2E_ERR_ARG on a short workspace (a shape refused
+ * above needs 0 bytes). */
+int s2e_refine_input(int dtype, const uint8_t* tmask, const uint8_t* rimg, const uint8_t* rmask, const uint8_t* flip,
+                     const uint8_t* levels, int ncls, int N, int H, int W, int C, void* x, void* stream);
+size_t s2e_refine_head_workspace_bytes(int N, int H, int W);
+int s2e_refine_head_fwd(int dtype, const void* res, int C, const uint8_t* rimg, const uint8_t* truth, const uint8_t* flip,
+                        int N, int H, int W, float* score, double* sumsq, float* terms, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int s2e_refine_head_bwd(int dtype, const void* res, int C, const uint8_t* rimg, const uint8_t* truth, const uint8_t* flip,
+                        int N, int H, int W, const double* sumsq, const float* gloss, float lambda_eds, float lambda_l1,
+                        void* dres, void* stream);
+int s2e_refine_predict_u8(int dtype, const void* res, int C, const uint8_t* rimg, const uint8_t* flip, int N, int H, int W,
+                          uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ side-by-side validation panels
  * The reference's visualize_sidebyside (util/visualizer.py:131-166) for a batch of n samples, as three launches on the caller's
  * stream with no host synchronisation between them: out[i] = [ style | label | target_original | fake | heat ], five h x w cells of

@@ -206,6 +206,11 @@ SIGNATURES = {
     's2e_seg_loss_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
     's2e_seg_loss_fwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     's2e_seg_loss_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    's2e_refine_input': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    's2e_refine_head_workspace_bytes': (SIZE, [_i, _i, _i]),
+    's2e_refine_head_fwd': (STATUS, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    's2e_refine_head_bwd': (STATUS, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp]),
+    's2e_refine_predict_u8': (STATUS, [_i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     's2e_bilinear_resize_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_bilinear_resize_bwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     's2e_upsample2x_fwd': (STATUS, [_i, _vp, _vp, _i, _i, _i, _i, _vp]),

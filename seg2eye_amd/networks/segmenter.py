@@ -16,37 +16,44 @@ from .base_network import BaseNetwork, compute_dtype_of
 
 
 class EyeSegNet(BaseNetwork):
+    FILTERS_OPTION = 'nsf'
+
     @staticmethod
     def modify_commandline_options(parser, is_train):
         parser.add_argument('--nsf', type=int, default=32, help='# of filters of the segmenter\'s first conv layer (a multiple of 8)')
         return parser
 
-    def __init__(self, opt):
+    def __init__(self, opt, in_nc=1, out_nc=None, filters=None):
+        """in_nc / out_nc / filters: the channels of the first conv's weight, of `out` and of e0 (default: 1, --label_nc, --nsf) -- what
+        EyeRefineNet (networks/refiner.py) builds the same body with."""
         super().__init__()
         self.opt = opt
         self.cdtype = compute_dtype_of(opt)
-        f = int(getattr(opt, 'nsf', 32))
+        f = int(getattr(opt, 'nsf', 32) if filters is None else filters)
         if f < 8 or f % 8:
-            raise ValueError('--nsf must be a positive multiple of 8, got %d' % f)
+            raise ValueError('--%s must be a positive multiple of 8, got %d' % (self.FILTERS_OPTION, f))
         self.label_nc = int(getattr(opt, 'label_nc', 4))
+        self.in_nc, self.out_nc = int(in_nc), int(self.label_nc if out_nc is None else out_nc)
 
         def conv(cin, cout):
             return nn.Conv2d(cin, cout, 3, padding=1)
-        self.e0, self.e1, self.e2, self.e3 = conv(1, f), conv(f, 2 * f), conv(2 * f, 4 * f), conv(4 * f, 8 * f)
+        self.e0, self.e1, self.e2, self.e3 = conv(self.in_nc, f), conv(f, 2 * f), conv(2 * f, 4 * f), conv(4 * f, 8 * f)
         self.b = conv(8 * f, 8 * f)
         self.d2, self.d1, self.d0 = conv(8 * f, 4 * f), conv(4 * f, 2 * f), conv(2 * f, f)
-        self.out = conv(f, self.label_nc)
+        self.out = conv(f, self.out_nc)
 
     def forward(self, x):
         """x: (N, 1, H, W) fp32 in [-1, 1], H and W multiples of 8 -> logits (N, H, W, label_nc) NHWC in the compute dtype."""
         self.require_gpu(x)
         if x.dim() != 4 or x.shape[1] != 1 or x.shape[2] % 8 or x.shape[3] % 8:
             raise ValueError('EyeSegNet takes (N, 1, H, W) with H and W multiples of 8, got %s' % (tuple(x.shape),))
+        return self.body(x.permute(0, 2, 3, 1).contiguous().to(self.cdtype))      # (N, H, W, 1): same memory order as NCHW
 
+    def body(self, h):
+        """h: (N, H, W, >= in_nc) NHWC in the compute dtype, H and W multiples of 8 -> (N, H, W, out_nc)."""
         def block(h, conv, stride=1, residual=None):
             return ops.instance_norm(ops.conv2d(h, conv.weight, conv.bias, residual, stride, 1), lrelu=True)
         with packing.network_scope(self, None):              # all weight packs of this forward: one launch
-            h = x.permute(0, 2, 3, 1).contiguous().to(self.cdtype)      # (N, H, W, 1): same memory order as NCHW
             e0 = block(h, self.e0)
             e1 = block(e0, self.e1, 2)
             e2 = block(e1, self.e2, 2)

@@ -1,5 +1,6 @@
 """The eye segmenter: train it on an OpenEDS store's labelled frames, score it, and write the masks `style_rank --seg_file`
-reads -- the step between `prepare_openeds` and `style_rank` of the chain  prepare_openeds -> segment -> style_rank -> train -> test.
+reads -- the step between `prepare_openeds` and `style_rank` of the chain  prepare_openeds -> segment -> style_rank -> train -> test
+(and -> refine, the residual refiner of seg2eye_amd/refine.py, which reads the same masks and rankings).
 
 The generative and sequence frames of the `train` and `validation` splits are unlabelled; `style_rank` compares them through masks it
 expects under /{subset}/{user}/{labels_pred_gen, labels_pred_seq} uint8 (n, 640, 400).  The store holds what such masks can be learned
