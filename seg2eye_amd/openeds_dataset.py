@@ -3,7 +3,8 @@ SURVEY 8 f4.  The data are licence-gated and h5py is not part of every image, so
 
     store[dataset_key][user][name]  ->  array-like with .shape and integer indexing
         names: images_ss, labels_ss, images_gen, images_seq, labels_gen   uint8 (n, 640, 400)
-               images_ss_filenames, labels_gen_filenames                  bytes (S13)
+               `<name>_filenames` of the targets                          bytes (S13)
+    (which of them a split uses, and how a ranking's entries map to rows: seg2eye_amd/openeds_store.py)
 
 `opt.dataroot` is opened with h5py when it is a path (ImportError with a pointer here if h5py is missing); tests and
 users without h5py pass a nested dict of numpy arrays (`OpenEDSDataset(opt, store=...)`).
@@ -23,6 +24,8 @@ import re
 import numpy as np
 import torch
 from PIL import Image
+
+from .openeds_store import candidate_row, clean_filename, split_keys
 
 
 def get_params(opt, size, rng=None):
@@ -75,10 +78,7 @@ class OpenEDSDataset(torch.utils.data.Dataset):
     def __init__(self, opt, store=None, style_refs=None, rng=None):
         self.opt = opt
         self.dataset_key = opt.dataset_key
-        # the keys of style images, labels and file names differ for the test set (openeds_dataset.py:44-52)
-        self.key_style_images = 'images_ss' if self.dataset_key == 'test' else 'images_gen'
-        self.label_key = 'labels_ss' if self.dataset_key != 'test' else 'labels_gen'
-        self.key_filenames = 'labels_gen_filenames' if self.dataset_key == 'test' else 'images_ss_filenames'
+        self.key_style_images, self.label_key, self.key_filenames = split_keys(self.dataset_key)
         self._store, self._path = store, None
         if store is None:
             self._path = opt.dataroot
@@ -129,9 +129,7 @@ class OpenEDSDataset(torch.utils.data.Dataset):
         if getattr(self.opt, 'device_preprocess', False):
             return self._raw_item(h5, user, idx, mask, params)
         mask_tensor = torch.from_numpy(np.ascontiguousarray(get_transform(self.opt, params, mask=True)(mask)))
-        filename = h5[user][self.key_filenames][idx]
-        filename = filename.decode('utf-8') if isinstance(filename, (bytes, np.bytes_)) else str(filename)
-        filename = re.sub(r'\.', '', filename)                  # some file names carry an additional dot
+        filename = clean_filename(h5[user][self.key_filenames][idx])
         transform_image = get_transform(self.opt, params)
         style, _, _ = self.get_style_images(user, self.opt.input_ns, transform_image, filename)
         out = {'label': mask_tensor, 'filename': filename, 'user': user, 'style_image': style}
@@ -147,9 +145,7 @@ class OpenEDSDataset(torch.utils.data.Dataset):
         style indices follow), so the same `rng` yields the same sample."""
         if self.opt.preprocess_mode != 'fixed':
             raise NotImplementedError("--device_preprocess restates preprocess_mode 'fixed' only (got '%s')" % self.opt.preprocess_mode)
-        filename = h5[user][self.key_filenames][idx]
-        filename = filename.decode('utf-8') if isinstance(filename, (bytes, np.bytes_)) else str(filename)
-        filename = re.sub(r'\.', '', filename)
+        filename = clean_filename(h5[user][self.key_filenames][idx])
         style, _, _ = self.get_style_images(user, self.opt.input_ns, None, filename)
         out = {'label_raw': torch.from_numpy(np.array(mask, dtype=np.uint8)), 'filename': filename, 'user': user, 'style_raw': style,
                'flip': bool(self.opt.isTrain and not self.opt.no_flip and params['flip'])}      # (what get_transform applies)
@@ -191,14 +187,10 @@ class OpenEDSDataset(torch.utils.data.Dataset):
         n_images = h5[user_id][self.key_style_images].shape[0]
         selected_idx, subsets = self._sample_style_idx(n_images, n, user_id=user_id, filename=filename)
         selected_idx = list(selected_idx)
-        subset_keys = {b'g': self.key_style_images, b's': 'images_seq'}
         imgs = []
-        for i, sel in enumerate(selected_idx):
-            key = subset_keys[bytes(subsets[i])] if subsets is not None else self.key_style_images
-            if key == 'images_seq':                              # sequence indices were appended behind the generative ones
-                sel = sel - n_images
-                selected_idx[i] = sel
-            imgs.append(np.asarray(h5[user_id][key][int(sel)]))
+        for i, sel in enumerate(selected_idx):                  # (a ranking without subsets lists rows of the first image key)
+            key, selected_idx[i] = candidate_row(h5[user_id], self.dataset_key, sel, subsets[i] if subsets is not None else b'g')
+            imgs.append(np.asarray(h5[user_id][key][int(selected_idx[i])]))
         if transform_image is None:                             # --device_preprocess: the raw frames (ns, 640, 400) uint8
             return torch.from_numpy(np.stack(imgs).astype(np.uint8, copy=False)), selected_idx, subsets
         tensors = [transform_image(Image.fromarray(im, mode='L')) for im in imgs]

@@ -19,6 +19,8 @@ import os
 import numpy as np
 from PIL import Image
 
+from .openeds_store import STORE_DEPTH, load_tree, save_tree
+
 
 class OpenEDSPreparator:
     FOLDER_SEMANTIC_SEGMENTATION = 'Semantic_Segmentation_Dataset'
@@ -105,27 +107,9 @@ class OpenEDSPreparator:
 
 def save_store(store, path):
     """HDF5 at `path` (one chunk per image like the reference) when h5py is installed, else `path + '.npz'`."""
-    try:
-        import h5py
-    except ImportError:
-        flat = {'%s/%s/%s' % (s, u, k): v for s, users in store.items() for u, d in users.items() for k, v in d.items()}
-        np.savez(path + '.npz', **flat)
-        return path + '.npz'
-    with h5py.File(path, 'w') as f:
-        for s, users in store.items():
-            gs = f.create_group(s)
-            for u, d in users.items():
-                g = gs.create_group(u)
-                for k, v in d.items():
-                    g.create_dataset(k, data=v, chunks=(1,) + v.shape[1:] if v.ndim == 3 else True)
-    return path
+    return save_tree(store, path, STORE_DEPTH, chunk_images=True)
 
 
 def load_store(path):
     """The nested mapping OpenEDSDataset(opt, store=...) takes, from the .npz save_store wrote."""
-    z = np.load(path)
-    store = {}
-    for key in z.files:
-        s, u, k = key.split('/')
-        store.setdefault(s, {}).setdefault(u, {})[k] = z[key]
-    return store
+    return load_tree(path, STORE_DEPTH)

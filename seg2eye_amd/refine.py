@@ -7,11 +7,10 @@ prepare_openeds -> segment -> style_rank -> refine.
     python -m seg2eye_amd.refine eval    --dataroot openeds.h5 --style_ref refs_val.h5 --seg_file masks_val.h5 --name refiner --dataset_key validation
     python -m seg2eye_amd.refine predict --dataroot openeds.h5 --style_ref refs_test.h5 --name refiner --dataset_key test --out submission/
 
-A TARGET is a row of the split's label key (`labels_ss`; `labels_gen` for 'test'), named as `style_rank.clean_filename` names it.  Its
-REFERENCE is an entry (index, subset) of the ranking `style_rank` wrote for that name, resolved by the convention
-`OpenEDSDataset.get_style_images` undoes: b'g' is row `index` of `images_gen` with the mask `labels_pred_gen` of --seg_file (for 'test':
-`images_ss` with the store's true `labels_ss`), b's' is row `index - n_gen` of `images_seq` with `labels_pred_seq`.  Training draws
-uniformly among the first --refine_top listed candidates; eval and predict take the first (the reference's `pick1`).
+A TARGET is a row of the split's label key, named by its cleaned file name.  Its REFERENCE is an entry (index, subset) of the ranking
+`style_rank` wrote for that name: a frame of the same person and that frame's mask.  Which keys a split uses, what the subset byte
+means and where a frame's mask lives is stated once, in seg2eye_amd/openeds_store.py (`split_keys`, `candidate_row`, `mask_source`).
+Training draws uniformly among the first --refine_top listed candidates; eval and predict take the first (the reference's `pick1`).
 
 Frames and masks go to the device as uint8 and stay uint8: `ops.refine_input` writes the network input, the network (networks/refiner.py:
 EyeRefineNet) gives the residual at the frames' own size, `ops.refine_loss` is the loss and `ops.refine_predict_u8` the submission bytes.
@@ -19,30 +18,25 @@ The score is the challenge's error of the uint8 predictions (`ops.openeds_error_
 for the unrefined reference frames: the baseline the refiner has to beat.
 
 The three commands are plain functions too: `train_refiner`, `evaluate`, `predict_frames`.  The ops are looked up when called."""
-import argparse
 import os
-import types
 
 import numpy as np
 import torch
 
-from .style_rank import clean_filename
+from . import openeds_store as O, stage
 
 INPUT_CHANNELS = 8                      # the network input's channel pitch: the three planes and structural zeros (16 bytes of bf16)
 SCALE = 1471                            # the Tester's scaling of the mean per-image error
+DEFAULTS = dict(nrf=32, label_nc=4, compute_dtype='bf16', batchSize=8, checkpoints_dir='./checkpoints', name='refiner', lr=1e-3, niter=20,
+                seed=0, no_flip=False, print_freq=50, lambda_eds=1.0, lambda_l1=0.0, refine_top=100)
 
 
 def refine_options(**kw):
     """The options EyeRefineNet, the checkpoint names and the functions below read; keyword arguments override the defaults."""
-    o = dict(nrf=32, label_nc=4, compute_dtype='bf16', batchSize=8, checkpoints_dir='./checkpoints', name='refiner', lr=1e-3, niter=20,
-             seed=0, no_flip=False, print_freq=50, lambda_eds=1.0, lambda_l1=0.0, refine_top=100)
-    unknown = sorted(set(kw) - set(o))
-    if unknown:
-        raise TypeError('refine_options: unknown option(s) %s' % ', '.join(unknown))
-    o.update(kw)
-    if int(o['refine_top']) < 1:
-        raise ValueError('--refine_top: at least 1 expected, got %s' % (o['refine_top'],))
-    return types.SimpleNamespace(**o)
+    o = stage.stage_options(DEFAULTS, kw, 'refine_options')
+    if int(o.refine_top) < 1:
+        raise ValueError('--refine_top: at least 1 expected, got %s' % (o.refine_top,))
+    return o
 
 
 def build_network(opt, device='cuda'):
@@ -60,7 +54,7 @@ def build_network(opt, device='cuda'):
 # ------------------------------------------------------------------------------------------------ the sampler (host only)
 def label_keys(dataset_key):
     """-> (the key of the target masks, the key of their file names), as style_rank.rank_styles names its targets."""
-    return ('labels_gen', 'labels_gen_filenames') if dataset_key == 'test' else ('labels_ss', 'images_ss_filenames')
+    return O.split_keys(dataset_key)[1:]
 
 
 def targets(store, dataset_key):
@@ -70,7 +64,7 @@ def targets(store, dataset_key):
     for user in store[dataset_key].keys():
         g = store[dataset_key][user]
         if label_key in g and names_key in g:
-            out += [(user, i, clean_filename(n)) for i, n in enumerate(np.asarray(g[names_key]))]
+            out += [(user, i, O.clean_filename(n)) for i, n in enumerate(np.asarray(g[names_key]))]
     return out
 
 
@@ -90,50 +84,40 @@ def pick_reference(store, seg_store, refs, dataset_key, user, fname, top=1, rng=
     pos = 0 if rng is None else int(rng.randint(0, min(int(top), len(index))))
     idx, sub = int(index[pos]), bytes(subset[pos])
     g = store[dataset_key][user]
-    first_key = 'images_ss' if dataset_key == 'test' else 'images_gen'
-    if sub == b'g':
-        image_key, row = first_key, idx
-    elif sub == b's':
-        image_key, row = 'images_seq', idx - (g[first_key].shape[0] if first_key in g else 0)
-    else:
-        raise ValueError('%s: candidate %d comes from an unknown subset %r (b\'g\' or b\'s\')' % (who, pos, sub))
+    try:
+        image_key, row = O.candidate_row(g, dataset_key, idx, sub)
+    except ValueError:
+        raise ValueError('%s: candidate %d comes from an unknown subset %r (b\'g\' or b\'s\')' % (who, pos, sub)) from None
     if image_key not in g or not 0 <= row < g[image_key].shape[0]:
         raise ValueError('%s: candidate %d is index %d of subset %r, row %d of %d %s' % (who, pos, idx, sub, row, g[image_key].shape[0] if image_key in g else 0, image_key))
-    if dataset_key == 'test' and sub == b'g':
-        holder, mask_key = g, 'labels_ss'
-    else:
-        mask_key = image_key.replace('images_', 'labels_pred_', 1)
-        try:
-            holder = seg_store[dataset_key][user]
-            holder[mask_key]
-        except (KeyError, TypeError):
-            raise ValueError('%s: the masks (--seg_file) hold no %s/%s/%s' % (who, dataset_key, user, mask_key)) from None
+    try:
+        seg_group = seg_store[dataset_key][user]
+    except (KeyError, TypeError):
+        seg_group = None
+    holder, mask_key = O.mask_source(g, seg_group, dataset_key, image_key)
+    if holder is None or mask_key not in holder:
+        raise ValueError('%s: the masks (--seg_file) hold no %s/%s/%s' % (who, dataset_key, user, mask_key))
     if holder[mask_key].shape[0] != g[image_key].shape[0]:
         raise ValueError('%s: %d masks %s for %d %s' % (who, holder[mask_key].shape[0], mask_key, g[image_key].shape[0], image_key))
     return image_key, row, holder, mask_key
 
 
-def _u8(a):
-    return np.asarray(a, dtype=np.uint8)
-
-
 def gather(store, dataset_key, batch, picks):
     """batch [(user, row, file name)], picks [pick_reference's result] -> uint8 host arrays (tmask, rimg, rmask, truth or None)."""
     label_key, _ = label_keys(dataset_key)
-    tmask = np.stack([_u8(store[dataset_key][u][label_key][int(i)]) for u, i, _ in batch])
-    rimg = np.stack([_u8(store[dataset_key][u][k][int(r)]) for (u, _, _), (k, r, _, _) in zip(batch, picks)])
-    rmask = np.stack([_u8(h[mk][int(r)]) for _, r, h, mk in picks])
-    truth = None if dataset_key == 'test' else np.stack([_u8(store[dataset_key][u]['images_ss'][int(i)]) for u, i, _ in batch])
+    tmask = O.rows_u8((store[dataset_key][u][label_key], i) for u, i, _ in batch)
+    rimg = O.rows_u8((store[dataset_key][u][k], r) for (u, _, _), (k, r, _, _) in zip(batch, picks))
+    rmask = O.rows_u8((h[mk], r) for _, r, h, mk in picks)
+    truth = None if dataset_key == 'test' else O.rows_u8((store[dataset_key][u]['images_ss'], i) for u, i, _ in batch)
     return tmask, rimg, rmask, truth
 
 
-def _to(device, *arrays):
-    return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in arrays]
-
-
-def _cdtype(opt):
+def _network_input(arrays, flip, opt, device):
+    """gather's arrays -> (rimg and truth (or None) on the device as uint8, the network input `ops.refine_input` makes of the planes)."""
     from .networks.base_network import compute_dtype_of
-    return compute_dtype_of(opt)
+    from .ops import refine as R
+    tmask, rimg, rmask, truth = stage.to_device(device, *arrays)
+    return rimg, truth, R.refine_input(tmask, rimg, rmask, flip, ncls=int(opt.label_nc), channels=INPUT_CHANNELS, dtype=compute_dtype_of(opt))
 
 
 def _first_batches(store, seg_store, refs, dataset_key, opt):
@@ -158,8 +142,7 @@ def evaluate(net, store, seg_store, refs, dataset_key, opt, device='cuda', verbo
     refined, nearest = [], []
     with torch.no_grad():
         for _, arrays in _first_batches(store, seg_store, refs, dataset_key, opt):
-            tmask, rimg, rmask, truth = _to(device, *arrays)
-            x = R.refine_input(tmask, rimg, rmask, None, ncls=int(opt.label_nc), channels=INPUT_CHANNELS, dtype=_cdtype(opt))
+            rimg, truth, x = _network_input(arrays, None, opt, device)
             refined.append(Q.openeds_error_u8(R.refine_predict_u8(net(x), rimg), truth))
             nearest.append(Q.openeds_error_u8(rimg, truth))
     out = {'openeds/%s' % dataset_key: float(torch.cat(refined).double().mean()) * SCALE,
@@ -176,48 +159,27 @@ def train_refiner(store, seg_store, refs, opt, net=None, device='cuda', save=Tru
     score /validation (when the store, the ranking and the masks have it) and save `<epoch>_net_R.pth` and `latest_net_R.pth`.
     net: a network to go on from (default: a new one).  -> (net, {'loss': [one float per step], 'terms': [[eds_loss, l1, 1471
     eds_loss] per step], 'scores': [one dict per epoch]}); the losses stay on the device between two progress lines."""
-    from . import checkpoint
-    from .optim import FlatAdam
     from .ops import refine as R
     if net is None:
         net = build_network(opt, device)
     samples = targets(store, 'train')
     if not samples:
         raise ValueError('train_refiner: /train has no target masks (labels_ss / images_ss_filenames)')
-    optimizer = FlatAdam(list(net.parameters()), lr=float(opt.lr), betas=(0.9, 0.999))
-    rng = np.random.RandomState(int(opt.seed))
-    bs, top, dtype = int(opt.batchSize), int(opt.refine_top), _cdtype(opt)
-    validate = all(s is not None and 'validation' in s for s in (store, refs, seg_store)) and bool(targets(store, 'validation'))
-    losses, terms, history, seen = [], [], {'loss': [], 'terms': [], 'scores': []}, 0
-    for epoch in range(1, int(opt.niter) + 1):
-        order = rng.permutation(len(samples))
-        for b0 in range(0, len(order), bs):
-            batch = [samples[j] for j in order[b0:b0 + bs]]
-            picks = [pick_reference(store, seg_store, refs, 'train', u, f, top, rng) for u, _, f in batch]
-            flip = None if opt.no_flip else torch.from_numpy((rng.rand(len(batch)) < 0.5).astype(np.uint8)).to(device)
-            tmask, rimg, rmask, truth = _to(device, *gather(store, 'train', batch, picks))
-            x = R.refine_input(tmask, rimg, rmask, flip, ncls=int(opt.label_nc), channels=INPUT_CHANNELS, dtype=dtype)
-            optimizer.zero_grad()
-            loss, t, _ = R.refine_loss(net(x), rimg, truth, flip, float(opt.lambda_eds), float(opt.lambda_l1))
-            loss.backward()
-            optimizer.step()
-            losses.append(loss.detach())
-            terms.append(t)
-            if verbose and len(losses) - seen >= int(opt.print_freq):
-                recent, recent_t = torch.stack(losses[seen:]).cpu().tolist(), torch.stack(terms[seen:]).cpu()      # (one copy per print_freq steps)
-                history['loss'] += recent
-                history['terms'] += recent_t.tolist()
-                seen = len(losses)
-                print('epoch %d step %d loss %.5f eds %.5f l1 %.5f score %.3f' % ((epoch, seen, sum(recent) / len(recent)) + tuple(recent_t.mean(0).tolist())))
-        if validate:
-            history['scores'].append(evaluate(net, store, seg_store, refs, 'validation', opt, device, verbose))
-        if save:
-            checkpoint.save_network(net, 'R', epoch, opt)
-            checkpoint.save_network(net, 'R', 'latest', opt)
-    if len(losses) > seen:
-        history['loss'] += torch.stack(losses[seen:]).cpu().tolist()
-        history['terms'] += torch.stack(terms[seen:]).cpu().tolist()
-    return net, history
+    scored = all(s is not None and 'validation' in s for s in (store, refs, seg_store)) and bool(targets(store, 'validation'))
+
+    def step(batch, rng, device):
+        picks = [pick_reference(store, seg_store, refs, 'train', u, f, int(opt.refine_top), rng) for u, _, f in batch]
+        flip = None if opt.no_flip else stage.draw_flip(rng, len(batch), device)
+        rimg, truth, x = _network_input(gather(store, 'train', batch, picks), flip, opt, device)
+        loss, terms, _ = R.refine_loss(net(x), rimg, truth, flip, float(opt.lambda_eds), float(opt.lambda_l1))
+        return loss, terms
+
+    def validate(net):
+        return evaluate(net, store, seg_store, refs, 'validation', opt, device, verbose) if scored else None
+
+    def line(epoch, steps, losses, terms):
+        return 'epoch %d step %d loss %.5f eds %.5f l1 %.5f score %.3f' % ((epoch, steps, sum(losses) / len(losses)) + tuple(terms.mean(0).tolist()))
+    return stage.train_epochs(net, samples, opt, 'R', step, validate, line, True, device, save, verbose)
 
 
 # ------------------------------------------------------------------------------------------------ predict
@@ -230,8 +192,7 @@ def predict_frames(net, store, seg_store, refs, dataset_key, opt, device='cuda',
         os.makedirs(out, exist_ok=True)
     with torch.no_grad():
         for batch, arrays in _first_batches(store, seg_store, refs, dataset_key, opt):
-            tmask, rimg, rmask, _ = _to(device, *arrays)
-            x = R.refine_input(tmask, rimg, rmask, None, ncls=int(opt.label_nc), channels=INPUT_CHANNELS, dtype=_cdtype(opt))
+            rimg, _, x = _network_input(arrays, None, opt, device)
             pred = R.refine_predict_u8(net(x), rimg).cpu().numpy()
             for (user, _, fname), p in zip(batch, pred):
                 frames.setdefault(user, {})[fname] = p
@@ -245,64 +206,17 @@ def predict_frames(net, store, seg_store, refs, dataset_key, opt, device='cuda',
 
 
 # ------------------------------------------------------------------------------------------------ the command line
-def _open_store(path):
-    if path.endswith('.npz'):
-        from .prepare_openeds import load_store
-        return load_store(path)
-    import h5py
-    return h5py.File(path, 'r')
-
-
-def _open_refs(path):
-    if path.endswith('.npz'):
-        from .style_rank import load_refs
-        return load_refs(path)
-    import h5py
-    return h5py.File(path, 'r')
-
-
-def _splits(paths, opener):
-    """The files of a comma-separated list as one mapping {split: ...}: style_rank and `segment predict` write one split per file."""
-    merged = {}
-    for p in (paths or '').split(','):
-        if p:
-            f = opener(p)
-            merged.update({k: f[k] for k in f.keys()})
-    return merged
-
-
-def _load(opt, which_epoch, device):
-    from . import checkpoint
-    return checkpoint.load_network(build_network(opt, device), 'R', which_epoch, opt)
-
-
 def parser():
-    ap = argparse.ArgumentParser(prog='python -m seg2eye_amd.refine', description='Train, score and apply the residual refiner: nearest frame plus a learned correction.')
-    common = argparse.ArgumentParser(add_help=False)
-    common.add_argument('--dataroot', required=True, help='the store prepare_openeds wrote (.h5, or .npz without h5py)')
-    common.add_argument('--style_ref', required=True, help='the ranking(s) style_rank wrote, one file per split, comma-separated')
-    common.add_argument('--seg_file', default=None, help='the masks `segment predict` wrote, one file per split, comma-separated (test needs none for its labelled frames)')
-    common.add_argument('--name', default='refiner', help='the checkpoints live in <checkpoints_dir>/<name>')
-    common.add_argument('--checkpoints_dir', default='./checkpoints')
-    common.add_argument('--nrf', type=int, default=32, help='# of filters of the first conv layer (a multiple of 8)')
-    common.add_argument('--label_nc', type=int, default=4)
-    common.add_argument('--compute_dtype', default='bf16', choices=['bf16', 'fp32'])
-    common.add_argument('--batchSize', type=int, default=8)
-    sub = ap.add_subparsers(dest='command', required=True)
-    t = sub.add_parser('train', parents=[common], help='train on the targets of /train')
-    t.add_argument('--niter', type=int, default=20, help='epochs')
-    t.add_argument('--lr', type=float, default=1e-3)
-    t.add_argument('--lambda_eds', type=float, default=1.0, help='weight of the challenge\'s error, the mean per-image 127.5 sqrt(sum d^2) / (H W)')
-    t.add_argument('--lambda_l1', type=float, default=0.0, help='weight of mean |d|')
-    t.add_argument('--refine_top', type=int, default=100, help='a training step draws its reference among the first N listed candidates')
-    t.add_argument('--seed', type=int, default=0)
-    t.add_argument('--no_flip', action='store_true', help='no horizontal flip of the training samples')
-    t.add_argument('--print_freq', type=int, default=50, help='steps between two lines of the running loss')
-    e = sub.add_parser('eval', parents=[common], help='the challenge\'s error of a checkpoint, and of the unrefined reference frames, on a split')
-    p = sub.add_parser('predict', parents=[common], help='write one .npy per target mask of a split')
-    for s in (e, p):
-        s.add_argument('--dataset_key', default='validation' if s is e else 'test', choices=['train', 'validation', 'test'])
-        s.add_argument('--which_epoch', default='latest')
+    ap, p = stage.stage_parser(
+        'python -m seg2eye_amd.refine', 'Train, score and apply the residual refiner: nearest frame plus a learned correction.', 'refiner', 8,
+        ('train on the targets of /train', 'the challenge\'s error of a checkpoint, and of the unrefined reference frames, on a split',
+         'write one .npy per target mask of a split'), 'samples', 'test',
+        inputs=[('--style_ref', dict(required=True, help='the ranking(s) style_rank wrote, one file per split, comma-separated')),
+                ('--seg_file', dict(default=None, help='the masks `segment predict` wrote, one file per split, comma-separated (test needs none for its labelled frames)'))],
+        net=[('--nrf', dict(type=int, default=32, help='# of filters of the first conv layer (a multiple of 8)'))],
+        train=[('--lambda_eds', dict(type=float, default=1.0, help='weight of the challenge\'s error, the mean per-image 127.5 sqrt(sum d^2) / (H W)')),
+               ('--lambda_l1', dict(type=float, default=0.0, help='weight of mean |d|')),
+               ('--refine_top', dict(type=int, default=100, help='a training step draws its reference among the first N listed candidates'))])
     p.add_argument('--out', required=True, help='the directory of the .npy files and pred_npy_list.txt')
     return ap
 
@@ -312,14 +226,16 @@ def main(argv=None):
     command, dataroot, style_ref, seg_file = a.pop('command'), a.pop('dataroot'), a.pop('style_ref'), a.pop('seg_file')
     which_epoch, dataset_key, out = a.pop('which_epoch', None), a.pop('dataset_key', None), a.pop('out', None)
     opt = refine_options(**a)
-    store, refs, seg_store = _open_store(dataroot), _splits(style_ref, _open_refs), _splits(seg_file, _open_store)
+    store, refs = O.open_tree(dataroot), O.merge_splits(style_ref, lambda path: O.open_tree(path, O.REFS_DEPTH))
+    seg_store = O.merge_splits(seg_file, O.open_tree)
     if command == 'train':
         train_refiner(store, seg_store, refs, opt)
-    elif command == 'eval':
-        return evaluate(_load(opt, which_epoch, 'cuda'), store, seg_store, refs, dataset_key, opt)
-    else:
-        frames = predict_frames(_load(opt, which_epoch, 'cuda'), store, seg_store, refs, dataset_key, opt, out=out)
-        print('%d frames of %d persons written to %s' % (sum(len(v) for v in frames.values()), len(frames), out))
+        return None
+    net = stage.load_network(build_network, 'R', opt, which_epoch, 'cuda')
+    if command == 'eval':
+        return evaluate(net, store, seg_store, refs, dataset_key, opt)
+    frames = predict_frames(net, store, seg_store, refs, dataset_key, opt, out=out)
+    print('%d frames of %d persons written to %s' % (sum(len(v) for v in frames.values()), len(frames), out))
 
 
 if __name__ == '__main__':

@@ -16,33 +16,25 @@ logits at --seg_hw; the loss is `ops.seg_cross_entropy` (or, with --lambda_dice 
 the score is mIoU (the OpenEDS segmentation metric) from `ops.seg_confusion`, accumulated on the device and read back once.
 
 The three commands are plain functions too: `train_segmenter`, `evaluate`, `predict_masks`.  The ops are looked up when called."""
-import argparse
-import types
-
 import numpy as np
 import torch
 
+from . import stage
+from .openeds_store import open_tree, pred_name, rows_u8
+
 PRED_KEYS = ('images_gen', 'images_seq')
-
-
-def pred_name(image_key):
-    """'images_gen' -> 'labels_pred_gen': the name style_rank reads the masks of an image key under."""
-    return image_key.replace('images_', 'labels_pred_', 1)
+DEFAULTS = dict(nsf=32, seg_hw=(320, 200), label_nc=4, compute_dtype='bf16', batchSize=16, checkpoints_dir='./checkpoints', name='segmenter',
+                lr=1e-3, niter=20, class_weights=None, seed=0, no_flip=False, print_freq=50,
+                lambda_ce=1.0, lambda_dice=0.0, lambda_surface=0.0, edge_alpha=0.0, edge_radius=2)
 
 
 def seg_options(**kw):
     """The options EyeSegNet, the checkpoint names and the functions below read; keyword arguments override the defaults."""
-    o = dict(nsf=32, seg_hw=(320, 200), label_nc=4, compute_dtype='bf16', batchSize=16, checkpoints_dir='./checkpoints', name='segmenter',
-             lr=1e-3, niter=20, class_weights=None, seed=0, no_flip=False, print_freq=50,
-             lambda_ce=1.0, lambda_dice=0.0, lambda_surface=0.0, edge_alpha=0.0, edge_radius=2)
-    unknown = sorted(set(kw) - set(o))
-    if unknown:
-        raise TypeError('seg_options: unknown option(s) %s' % ', '.join(unknown))
-    o.update(kw)
-    o['seg_hw'] = tuple(int(v) for v in o['seg_hw'])
-    if len(o['seg_hw']) != 2 or o['seg_hw'][0] % 8 or o['seg_hw'][1] % 8 or min(o['seg_hw']) < 8:
-        raise ValueError('--seg_hw: H,W, both multiples of 8, expected, got %s' % (o['seg_hw'],))
-    return types.SimpleNamespace(**o)
+    o = stage.stage_options(DEFAULTS, kw, 'seg_options')
+    o.seg_hw = tuple(int(v) for v in o.seg_hw)
+    if len(o.seg_hw) != 2 or o.seg_hw[0] % 8 or o.seg_hw[1] % 8 or min(o.seg_hw) < 8:
+        raise ValueError('--seg_hw: H,W, both multiples of 8, expected, got %s' % (o.seg_hw,))
+    return o
 
 
 def build_network(opt, device='cuda'):
@@ -53,16 +45,10 @@ def build_network(opt, device='cuda'):
     return net.to(device)
 
 
-def _rows(dataset, idx):
-    """Rows `idx` of a store entry (a numpy array or an HDF5 dataset, which takes one row at a time in any order) as one uint8 array."""
-    return np.stack([np.asarray(dataset[int(i)], dtype=np.uint8) for i in idx])
-
-
 def _frames_to_input(frames, hw, flip, device):
     """frames (n, 640, 400) uint8 host array -> (n, 1, h, w) fp32 in [-1, 1] on `device`."""
     from .ops import preprocess as P
-    t = torch.from_numpy(np.ascontiguousarray(frames)).to(device)
-    return P.resize_bicubic_u8(t, hw[0], hw[1], flip).unsqueeze(1)
+    return P.resize_bicubic_u8(stage.to_device(device, frames)[0], hw[0], hw[1], flip).unsqueeze(1)
 
 
 def _no_flip(n, device):
@@ -79,6 +65,11 @@ def labelled_samples(store, dataset_key):
     return out
 
 
+def _labelled_rows(store, dataset_key, key, batch):
+    """The rows of `key` ('images_ss' or 'labels_ss') of a batch of labelled_samples, stacked."""
+    return rows_u8((store[dataset_key][u][key], i) for u, i in batch)
+
+
 # ------------------------------------------------------------------------------------------------ eval
 def evaluate(net, store, dataset_key, opt, device='cuda', verbose=True):
     """mIoU, per-class IoU and pixel accuracy of `net` on the labelled frames of a split, the masks taken at the frames' own size.
@@ -92,9 +83,8 @@ def evaluate(net, store, dataset_key, opt, device='cuda', verbose=True):
     with torch.no_grad():
         for b0 in range(0, len(samples), int(opt.batchSize)):
             batch = samples[b0:b0 + int(opt.batchSize)]
-            frames = np.stack([np.asarray(store[dataset_key][u]['images_ss'][i], dtype=np.uint8) for u, i in batch])
-            truth = np.stack([np.asarray(store[dataset_key][u]['labels_ss'][i], dtype=np.uint8) for u, i in batch])
-            logits = net(_frames_to_input(frames, opt.seg_hw, _no_flip(len(batch), device), device))
+            truth = _labelled_rows(store, dataset_key, 'labels_ss', batch)
+            logits = net(_frames_to_input(_labelled_rows(store, dataset_key, 'images_ss', batch), opt.seg_hw, _no_flip(len(batch), device), device))
             pred = S.seg_argmax_u8(logits, truth.shape[1], truth.shape[2])
             S.seg_confusion(pred, torch.from_numpy(truth).to(device), ncls, out=conf)
     scores = S.segment_scores(conf)
@@ -114,8 +104,6 @@ def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True
     With --lambda_dice, --lambda_surface or --edge_alpha set (or --lambda_ce off 1) the loss is `ops.seg_loss` on the
     distance maps and boundary band `ops.seg_dist_maps` makes of the resized, flipped labels of the batch; the history then has
     'terms': [[CE, Dice, Surface] per step] too, and the progress line shows their means."""
-    from . import checkpoint
-    from .optim import FlatAdam
     from .ops import preprocess as P, segment as S
     if net is None:
         net = build_network(opt, device)
@@ -127,55 +115,28 @@ def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True
     if len(cw) != ncls:
         raise ValueError('--class_weights: %d values for %d classes' % (len(cw), ncls))
     weights = torch.tensor(cw, dtype=torch.float32, device=device)
-    optimizer = FlatAdam(list(net.parameters()), lr=float(opt.lr), betas=(0.9, 0.999))
-    rng = np.random.RandomState(int(opt.seed))
-    bs = int(opt.batchSize)
     lam = {k: float(getattr(opt, k)) for k in ('lambda_ce', 'lambda_dice', 'lambda_surface', 'edge_alpha')}
     plain = lam == {'lambda_ce': 1.0, 'lambda_dice': 0.0, 'lambda_surface': 0.0, 'edge_alpha': 0.0}
-    losses, terms, history, seen = [], [], {'loss': [], 'scores': []}, 0
-    if not plain:
-        history['terms'] = []
-    for epoch in range(1, int(opt.niter) + 1):
-        order = rng.permutation(len(samples))
-        for b0 in range(0, len(order), bs):
-            batch = [samples[j] for j in order[b0:b0 + bs]]
-            frames = np.stack([np.asarray(store['train'][u]['images_ss'][i], dtype=np.uint8) for u, i in batch])
-            labels = np.stack([np.asarray(store['train'][u]['labels_ss'][i], dtype=np.uint8) for u, i in batch])
-            flip = _no_flip(len(batch), device) if opt.no_flip else torch.from_numpy((rng.rand(len(batch)) < 0.5).astype(np.uint8)).to(device)
-            x = _frames_to_input(frames, opt.seg_hw, flip, device)
-            y = P.resize_nearest_u8(torch.from_numpy(labels).to(device), opt.seg_hw[0], opt.seg_hw[1], flip)
-            optimizer.zero_grad()
-            if plain:
-                loss = S.seg_cross_entropy(net(x), y, weights)
-            else:
-                phi = band = None
-                if lam['lambda_surface'] or lam['edge_alpha']:
-                    phi, band = S.seg_dist_maps(y, ncls, int(opt.edge_radius))
-                loss, t = S.seg_loss(net(x), y, weights, phi, band, **lam)
-                terms.append(t)
-            loss.backward()
-            optimizer.step()
-            losses.append(loss.detach())
-            if verbose and len(losses) - seen >= int(opt.print_freq):
-                recent = torch.stack(losses[seen:]).cpu().tolist()          # (one copy per print_freq steps)
-                history['loss'] += recent
-                line = 'epoch %d step %d loss %.4f' % (epoch, len(losses), sum(recent) / len(recent))
-                if not plain:
-                    recent_t = torch.stack(terms[seen:]).cpu()
-                    history['terms'] += recent_t.tolist()
-                    line += ' CE %.4f Dice %.4f Surface %.4f' % tuple(recent_t.mean(0).tolist())
-                seen = len(losses)
-                print(line)
+
+    def step(batch, rng, device):
+        flip = _no_flip(len(batch), device) if opt.no_flip else stage.draw_flip(rng, len(batch), device)
+        x = _frames_to_input(_labelled_rows(store, 'train', 'images_ss', batch), opt.seg_hw, flip, device)
+        y = P.resize_nearest_u8(stage.to_device(device, _labelled_rows(store, 'train', 'labels_ss', batch))[0], opt.seg_hw[0], opt.seg_hw[1], flip)
+        if plain:
+            return S.seg_cross_entropy(net(x), y, weights), None
+        phi = band = None
+        if lam['lambda_surface'] or lam['edge_alpha']:
+            phi, band = S.seg_dist_maps(y, ncls, int(opt.edge_radius))
+        return S.seg_loss(net(x), y, weights, phi, band, **lam)
+
+    def validate(net):
         if 'validation' in store and labelled_samples(store, 'validation'):
-            history['scores'].append(evaluate(net, store, 'validation', opt, device, verbose))
-        if save:
-            checkpoint.save_network(net, 'S', epoch, opt)
-            checkpoint.save_network(net, 'S', 'latest', opt)
-    if len(losses) > seen:
-        history['loss'] += torch.stack(losses[seen:]).cpu().tolist()
-        if not plain:
-            history['terms'] += torch.stack(terms[seen:]).cpu().tolist()
-    return net, history
+            return evaluate(net, store, 'validation', opt, device, verbose)
+
+    def line(epoch, steps, losses, terms):
+        text = 'epoch %d step %d loss %.4f' % (epoch, steps, sum(losses) / len(losses))
+        return text if plain else text + ' CE %.4f Dice %.4f Surface %.4f' % tuple(terms.mean(0).tolist())
+    return stage.train_epochs(net, samples, opt, 'S', step, validate, line, not plain, device, save, verbose)
 
 
 # ------------------------------------------------------------------------------------------------ predict
@@ -196,7 +157,7 @@ def predict_masks(net, store, dataset_key, opt, keys=PRED_KEYS, device='cuda'):
                 n, H, W = g[key].shape
                 masks = np.zeros((n, H, W), dtype=np.uint8)
                 for r0 in range(0, n, bs):
-                    frames = _rows(g[key], range(r0, min(r0 + bs, n)))
+                    frames = rows_u8((g[key], r) for r in range(r0, min(r0 + bs, n)))
                     logits = net(_frames_to_input(frames, opt.seg_hw, _no_flip(len(frames), device), device))
                     masks[r0:r0 + len(frames)] = S.seg_argmax_u8(logits, H, W).cpu().numpy()
                 out[user][pred_name(key)] = masks
@@ -204,52 +165,23 @@ def predict_masks(net, store, dataset_key, opt, keys=PRED_KEYS, device='cuda'):
 
 
 # ------------------------------------------------------------------------------------------------ the command line
-def _open(path):
-    if path.endswith('.npz'):
-        from .prepare_openeds import load_store
-        return load_store(path)
-    import h5py
-    return h5py.File(path, 'r')
-
-
-def _load(opt, which_epoch, device):
-    from . import checkpoint
-    return checkpoint.load_network(build_network(opt, device), 'S', which_epoch, opt)
-
-
 def _csv(kind):
     return lambda s: tuple(kind(v) for v in s.split(','))
 
 
 def parser():
-    ap = argparse.ArgumentParser(prog='python -m seg2eye_amd.segment', description='Train, score and apply the eye segmenter (the masks of style_rank --seg_file).')
-    common = argparse.ArgumentParser(add_help=False)
-    common.add_argument('--dataroot', required=True, help='the store prepare_openeds wrote (.h5, or .npz without h5py)')
-    common.add_argument('--name', default='segmenter', help='the checkpoints live in <checkpoints_dir>/<name>')
-    common.add_argument('--checkpoints_dir', default='./checkpoints')
-    common.add_argument('--nsf', type=int, default=32, help='# of filters of the first conv layer (a multiple of 8)')
-    common.add_argument('--seg_hw', type=_csv(int), default=(320, 200), help='H,W the frames are resized to (multiples of 8)')
-    common.add_argument('--label_nc', type=int, default=4)
-    common.add_argument('--compute_dtype', default='bf16', choices=['bf16', 'fp32'])
-    common.add_argument('--batchSize', type=int, default=16)
-    sub = ap.add_subparsers(dest='command', required=True)
-    t = sub.add_parser('train', parents=[common], help='train on the labelled frames of /train')
-    t.add_argument('--niter', type=int, default=20, help='epochs')
-    t.add_argument('--lr', type=float, default=1e-3)
-    t.add_argument('--class_weights', type=_csv(float), default=None, help='one weight per class, e.g. 1,1,1,1')
-    t.add_argument('--seed', type=int, default=0)
-    t.add_argument('--no_flip', action='store_true', help='no horizontal flip of the training frames')
-    t.add_argument('--print_freq', type=int, default=50, help='steps between two lines of the running loss')
-    t.add_argument('--lambda_ce', type=float, default=1.0, help='weight of the cross-entropy term')
-    t.add_argument('--lambda_dice', type=float, default=0.0, help='weight of the generalised Dice term (classes weighed by inverse squared area)')
-    t.add_argument('--lambda_surface', type=float, default=0.0, help='weight of the surface (boundary) term on signed distance maps')
-    t.add_argument('--edge_alpha', type=float, default=0.0, help='a pixel within --edge_radius of another class counts 1 + edge_alpha times in the cross-entropy')
-    t.add_argument('--edge_radius', type=int, default=2, help='width of the boundary band, in pixels of --seg_hw')
-    e = sub.add_parser('eval', parents=[common], help='mIoU of a checkpoint on the labelled frames of a split')
-    p = sub.add_parser('predict', parents=[common], help='write the masks of the unlabelled frames of a split')
-    for s in (e, p):
-        s.add_argument('--dataset_key', default='validation' if s is e else 'train', choices=['train', 'validation', 'test'])
-        s.add_argument('--which_epoch', default='latest')
+    ap, p = stage.stage_parser(
+        'python -m seg2eye_amd.segment', 'Train, score and apply the eye segmenter (the masks of style_rank --seg_file).', 'segmenter', 16,
+        ('train on the labelled frames of /train', 'mIoU of a checkpoint on the labelled frames of a split', 'write the masks of the unlabelled frames of a split'),
+        'frames', 'train',
+        net=[('--nsf', dict(type=int, default=32, help='# of filters of the first conv layer (a multiple of 8)')),
+             ('--seg_hw', dict(type=_csv(int), default=(320, 200), help='H,W the frames are resized to (multiples of 8)'))],
+        train=[('--class_weights', dict(type=_csv(float), default=None, help='one weight per class, e.g. 1,1,1,1'))],
+        train_last=[('--lambda_ce', dict(type=float, default=1.0, help='weight of the cross-entropy term')),
+                    ('--lambda_dice', dict(type=float, default=0.0, help='weight of the generalised Dice term (classes weighed by inverse squared area)')),
+                    ('--lambda_surface', dict(type=float, default=0.0, help='weight of the surface (boundary) term on signed distance maps')),
+                    ('--edge_alpha', dict(type=float, default=0.0, help='a pixel within --edge_radius of another class counts 1 + edge_alpha times in the cross-entropy')),
+                    ('--edge_radius', dict(type=int, default=2, help='width of the boundary band, in pixels of --seg_hw'))])
     p.add_argument('--out', required=True, help='the file style_rank --seg_file opens (HDF5; <out>.npz without h5py)')
     p.add_argument('--keys', type=_csv(str), default=PRED_KEYS, help='image keys to segment, e.g. images_gen,images_seq')
     return ap
@@ -260,15 +192,16 @@ def main(argv=None):
     command, dataroot = a.pop('command'), a.pop('dataroot')
     which_epoch, dataset_key, out, keys = a.pop('which_epoch', None), a.pop('dataset_key', None), a.pop('out', None), a.pop('keys', None)
     opt = seg_options(**a)
-    store = _open(dataroot)
+    store = open_tree(dataroot)
     if command == 'train':
         train_segmenter(store, opt)
-    elif command == 'eval':
-        return evaluate(_load(opt, which_epoch, 'cuda'), store, dataset_key, opt)
-    else:
-        from .prepare_openeds import save_store
-        masks = predict_masks(_load(opt, which_epoch, 'cuda'), store, dataset_key, opt, keys=keys)
-        print('masks of %d persons written to %s' % (len(masks[dataset_key]), save_store(masks, out)))
+        return None
+    net = stage.load_network(build_network, 'S', opt, which_epoch, 'cuda')
+    if command == 'eval':
+        return evaluate(net, store, dataset_key, opt)
+    from .prepare_openeds import save_store
+    masks = predict_masks(net, store, dataset_key, opt, keys=keys)
+    print('masks of %d persons written to %s' % (len(masks[dataset_key]), save_store(masks, out)))
 
 
 if __name__ == '__main__':

@@ -8,8 +8,9 @@ that writes one.  `rank_styles` writes the mapping `OpenEDSDataset(opt, style_re
 
 Per person: the TARGETS are the rows of the dataset's own label key (`labels_ss`; `labels_gen` for 'test'), named as the dataset names
 them (decoded, dots removed).  The CANDIDATES are the person's style images (`images_gen`; `images_ss` for 'test'), subset b'g', followed
-when `use_seq` by `images_seq`, subset b's', whose indices are offset by the number of the former -- the convention
-`OpenEDSDataset.get_style_images` undoes.  A candidate is compared through its segmentation mask:
+when `use_seq` by `images_seq`, subset b's', whose indices are offset by the number of the former: the order of
+`openeds_store.candidate_parts`, which `openeds_store.candidate_row` undoes for the dataset and the refiner.  A candidate is compared
+through its segmentation mask (`openeds_store.mask_source`):
   'test'                the style images are the labelled frames: their masks are the store's true `labels_ss`; the sequence frames join
                         only where `seg_store` holds their masks
   'train', 'validation' the generative and sequence frames are unlabelled (as they were for the reference's authors): their masks come
@@ -22,22 +23,17 @@ candidates are uploaded in chunks of at most UPLOAD_BYTES.
     python -m seg2eye_amd.segment predict --dataroot openeds.h5 --name seg --dataset_key train --out masks.h5
     python -m seg2eye_amd.style_rank --dataroot openeds.h5 --dataset_key train --seg_file masks.h5 --out style_refs.h5
 
-`save_refs` / `load_refs` mirror prepare_openeds.save_store / load_store: HDF5 when h5py is installed, else `.npz` with '/'-joined
-keys; the dataset reads a `--style_ref` that ends in `.npz` through `load_refs`."""
+`save_refs` / `load_refs` are openeds_store.save_tree / load_tree at the ranking's depth: HDF5 when h5py is installed, else `.npz` with
+'/'-joined keys; the dataset reads a `--style_ref` that ends in `.npz` through `load_refs`."""
 import argparse
-import re
 import warnings
 
 import numpy as np
 import torch
 
+from .openeds_store import REFS_DEPTH, candidate_parts, clean_filename, load_tree, mask_source, open_tree as _open, save_tree, split_keys
+
 UPLOAD_BYTES = 1 << 30                  # candidate masks on the device at a time
-
-
-def clean_filename(name):
-    """A stored file name as OpenEDSDataset.__getitem__ makes it: decoded, dots removed."""
-    name = name.decode('utf-8') if isinstance(name, (bytes, np.bytes_)) else str(name)
-    return re.sub(r'\.', '', name)
 
 
 def _names(group, key):
@@ -45,26 +41,23 @@ def _names(group, key):
 
 
 def _candidates(store, seg_store, dataset_key, user, use_seq):
-    """-> [(subset byte, masks (n, H, W) array-like, cleaned names or None)], the generative / labelled frames first."""
-    g = store[dataset_key][user]
-    if dataset_key == 'test':
-        if 'labels_ss' not in g:
-            raise ValueError("rank_styles('test'): %s has no labels_ss -- the masks of its style images (images_ss)" % user)
-        parts = [(b'g', g['labels_ss'], _names(g, 'images_ss_filenames'))]
-        seg = None if seg_store is None else seg_store[dataset_key][user]
-        if use_seq and seg is not None and 'labels_pred_seq' in seg:
-            parts.append((b's', seg['labels_pred_seq'], _names(g, 'images_seq_filenames')))
-        return parts
-    if seg_store is None:
+    """-> [(subset byte, masks (n, H, W) array-like, cleaned names or None)] in the order of openeds_store.candidate_parts.  The test
+    split's sequence frames join only where seg_store holds their masks; in the other splits every part needs its predicted masks."""
+    g, test = store[dataset_key][user], dataset_key == 'test'
+    if test and 'labels_ss' not in g:
+        raise ValueError("rank_styles('test'): %s has no labels_ss -- the masks of its style images (images_ss)" % user)
+    if not test and seg_store is None:
         raise ValueError("rank_styles('%s'): the generative and sequence frames of this split are unlabelled -- pass seg_store, the "
                          "masks a segmentation network predicts for them: /%s/<user>/{labels_pred_gen, labels_pred_seq} uint8 "
                          "(n, 640, 400), row-aligned with images_gen / images_seq" % (dataset_key, dataset_key))
-    seg = seg_store[dataset_key][user]
-    parts = [(b'g', seg['labels_pred_gen'], _names(g, 'images_gen_filenames'))]
-    if use_seq:
-        parts.append((b's', seg['labels_pred_seq'], _names(g, 'images_seq_filenames')))
-    for (_, masks, _), key in zip(parts, ('images_gen', 'images_seq')):
-        if masks.shape[0] != g[key].shape[0]:
+    seg = None if seg_store is None else seg_store[dataset_key][user]
+    parts = []
+    for subset, image_key in candidate_parts(dataset_key, use_seq):
+        holder, mask_key = mask_source(g, seg, dataset_key, image_key)
+        if not test or (holder is not None and mask_key in holder):
+            parts.append((subset, holder[mask_key], _names(g, image_key + '_filenames')))
+    for (_, masks, _), (_, key) in zip(parts, candidate_parts(dataset_key, use_seq)):
+        if not test and masks.shape[0] != g[key].shape[0]:
             raise ValueError('%s/%s: %d predicted masks for %d %s' % (dataset_key, user, masks.shape[0], g[key].shape[0], key))
     return parts
 
@@ -84,8 +77,7 @@ def _distances(targets, parts, ncls, metric, device):
 
 def rank_styles(store, dataset_key, seg_store=None, top=100, metric='l2', use_seq=True, ncls=4, device='cuda'):
     from .ops import rank as R
-    label_key = 'labels_ss' if dataset_key != 'test' else 'labels_gen'
-    key_filenames = 'labels_gen_filenames' if dataset_key == 'test' else 'images_ss_filenames'
+    _, label_key, key_filenames = split_keys(dataset_key)
     out, short = {}, []
     for user in store[dataset_key].keys():
         g = store[dataset_key][user]
@@ -121,39 +113,12 @@ def rank_styles(store, dataset_key, seg_store=None, top=100, metric='l2', use_se
 # ------------------------------------------------------------------------------------------------ the file
 def save_refs(refs, path):
     """HDF5 at `path` when h5py is installed, else `path + '.npz'` with '/'-joined keys (as prepare_openeds.save_store).  -> the path written."""
-    try:
-        import h5py
-    except ImportError:
-        flat = {'%s/%s/%s/%s' % (s, u, f, k): v for s, users in refs.items() for u, files in users.items() for f, e in files.items()
-                for k, v in e.items()}
-        np.savez(path + '.npz', **flat)
-        return path + '.npz'
-    with h5py.File(path, 'w') as f:
-        for s, users in refs.items():
-            for u, files in users.items():
-                for name, e in files.items():
-                    g = f.require_group('%s/%s/%s' % (s, u, name))
-                    for k, v in e.items():
-                        g.create_dataset(k, data=v)
-    return path
+    return save_tree(refs, path, REFS_DEPTH)
 
 
 def load_refs(path):
     """The nested mapping OpenEDSDataset(opt, style_refs=...) takes, from the .npz save_refs wrote."""
-    z = np.load(path)
-    refs = {}
-    for key in z.files:
-        s, u, f, k = key.split('/')
-        refs.setdefault(s, {}).setdefault(u, {}).setdefault(f, {})[k] = z[key]
-    return refs
-
-
-def _open(path):
-    if path.endswith('.npz'):
-        from .prepare_openeds import load_store
-        return load_store(path)
-    import h5py
-    return h5py.File(path, 'r')
+    return load_tree(path, REFS_DEPTH)
 
 
 def main(argv=None):
