@@ -853,6 +853,36 @@ int s2e_seg_loss_bwd(int dtype, const void* logits, const uint8_t* label, const 
                      const float* saved, const float* gloss, int N, int H, int W, int C, int ncls, float lambda_ce, float lambda_surf,
                      float edge_alpha, void* dlogits, void* stream);
 
+/* ------------------------------------------------------------------ mask cleaner: connected components, nearest-class fill
+ * labels: (N, H, W) uint8, 1 <= ncls <= 16, conn 4 or 8.  Everything is per image: nothing crosses images and the frame edge joins
+ * nothing.  The rule:
+ *   components  pixels of one label c < ncls that are conn-adjacent form a component; a pixel with a label >= ncls (255 is the
+ *       documented "ignore") belongs to none and is never used as an index.  A component's id is the smallest linear index y W + x
+ *       among its pixels -- a property of the map, not of the algorithm.
+ *   kept        modes[c]: 0 (all) every component of class c is kept; 1 (largest) only the one of largest area, among equal areas
+ *       the one with the smallest id; 2 (border) those that hold a pixel of the image's first or last row or column.
+ *   fill        every pixel that is not kept -- of a removed component or with a label >= ncls -- becomes argmin over c of (d^2_c, c),
+ *       compared lexicographically, d^2_c the smallest squared integer distance to a kept pixel of class c, over the classes that
+ *       keep a pixel in this image: a tie goes to the lower class.  Kept pixels do not change; an image that keeps no pixel comes
+ *       back unchanged.
+ *   stats       (N, ncls, 4) int32, or NULL: per image and class the components found, the pixels before, the pixels removed, the
+ *       pixels after (before - removed + filled in).
+ *   s2e_mask_components: comp (N, H, W) int32 = the id of the pixel's component, -1 for a label >= ncls.  Three launches on `comp`
+ *       itself: union-find per 32 x 32 tile in LDS, a min-union along the tile borders, a flatten; one tile per image skips the second.
+ *   s2e_mask_clean: out (N, H, W) uint8.  Seven launches (six for one tile per image): those three, the per-class decision, the kept
+ *       map, and the column and row pass of s2e_seg_dist_maps' scheme, the row pass only where a row has a pixel that is not kept.
+ *       workspace: s2e_mask_clean_workspace_bytes(N, H, W, ncls) bytes, 8-byte aligned.  modes is a HOST pointer to ncls bytes, read
+ *       before the first launch, so that a bad byte is refused here and not met by a kernel.
+ * No workgroup waits for another; ids are minima, areas integer sums, the ties are ruled above: two calls give the same bytes.
+ * Before any launch, in this order: S2E_ERR_ARG on a null labels, out, comp, modes or workspace, on a short workspace or one that is
+ * not 8-byte aligned (a shape refused below needs 0 bytes), on N, H or W < 1, on conn other than 4 and 8; S2E_ERR_UNSUPPORTED on ncls
+ * outside 1..16; S2E_ERR_ARG on a mode byte above 2; S2E_ERR_UNSUPPORTED on H or W > 1024 (the uint16 distances, as in
+ * s2e_seg_dist_maps), on N > 65535 or N H W >= 2^31. */
+size_t s2e_mask_clean_workspace_bytes(int N, int H, int W, int ncls);
+int s2e_mask_components(const uint8_t* labels, int N, int H, int W, int ncls, int conn, int32_t* comp, void* stream);
+int s2e_mask_clean(const uint8_t* labels, int N, int H, int W, int ncls, int conn, const uint8_t* modes, uint8_t* out, int32_t* stats,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ residual refiner: input, loss, gradient, submission bytes
  * The reference's last stage (refinenet/): the top-ranked frame of the same person plus a learned residual, clamped to [-1, 1].  These
  * are the four memory-bound pieces around the network.  tmask, rimg, rmask, truth: (N, H, W) uint8 planes as the store holds them.

@@ -23,6 +23,7 @@ NORM_ACCUMULATE_DX = 0x100
 LOSS_NEG_MEAN, LOSS_HINGE_REAL, LOSS_HINGE_FAKE, LOSS_L1, LOSS_L1_NANGRAD = 0, 1, 2, 3, 4
 REGION_L1, REGION_L2 = 0, 1
 RANK_L2, RANK_MISMATCH = 0, 1
+MASK_ALL, MASK_LARGEST, MASK_BORDER = 0, 1, 2          # the mode bytes of s2e_mask_clean
 
 
 class ConvDesc(C.Structure):
@@ -206,6 +207,9 @@ SIGNATURES = {
     's2e_seg_loss_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
     's2e_seg_loss_fwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     's2e_seg_loss_bwd': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    's2e_mask_clean_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_mask_components': (STATUS, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    's2e_mask_clean': (STATUS, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     's2e_refine_input': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     's2e_refine_head_workspace_bytes': (SIZE, [_i, _i, _i]),
     's2e_refine_head_fwd': (STATUS, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),

@@ -13,14 +13,10 @@
 //                store fp64 partials with plain stores; one workgroup folds them in index order and writes loss, terms and saved.
 // s2e_seg_loss_bwd   one launch, the softmax recomputed; the per-image Dice coefficients come from `saved`.
 #include "seg_pixel.h"
+#include "seg_dist.h"
 
 namespace {
 
-constexpr int DIST_MAX_SIDE = 1024;                          // H and W at most: uint16 distances, and rint(sqrtf(m)^2) == m up to 2 * 1023^2
-constexpr int DIST_COL_THREADS = 64;                         // one wave per column-pass workgroup: N ncls ceil(W / 64) workgroups
-constexpr int DIST_COL_DEPTH = 32;                           // rows of a lane whose loads are in flight together: the walk is a chain of load latencies
-constexpr uint32_t DIST_NONE16 = 0xFFFFu;
-constexpr uint32_t DIST_NONE = 0x40000000u;                  // a squared distance no pixel has; (x - x')^2 added to it does not wrap
 constexpr int LOSS_BLOCKS = 512;                             // workgroups of the loss forward at most, over all images: two per CU
 constexpr int LOSS_DEPTH = 2;                                // pixels of a lane whose loads are in flight together in the forward
 constexpr int LOSS_HEAD = 4;                                 // partials ahead of the per-class ones: CE numerator, sum w, |P|, surface numerator
@@ -43,7 +39,7 @@ __global__ __launch_bounds__(DIST_COL_THREADS) void seg_dist_col_kernel(const ui
             const int y = y0 + u;
             if (y < H) {
                 if (l[u] == c) in = y; else out = y;
-                col[y * pitch] = (in < 0 ? DIST_NONE16 : (uint32_t)(y - in)) | (out < 0 ? DIST_NONE16 : (uint32_t)(y - out)) << 16;
+                col[y * pitch] = dist_to_last(y, in) | dist_to_last(y, out) << 16;
             }
         }
     }
@@ -62,8 +58,8 @@ __global__ __launch_bounds__(DIST_COL_THREADS) void seg_dist_col_kernel(const ui
             const int y = y0 - u;
             if (y >= 0) {
                 if (l[u] == c) in = y; else out = y;
-                const uint32_t di = min(v[u] & 0xFFFFu, in < 0 ? DIST_NONE16 : (uint32_t)(in - y));
-                const uint32_t dn = min(v[u] >> 16, out < 0 ? DIST_NONE16 : (uint32_t)(out - y));
+                const uint32_t di = min(v[u] & 0xFFFFu, dist_to_last(y, in));
+                const uint32_t dn = min(v[u] >> 16, dist_to_last(y, out));
                 col[y * pitch] = di | dn << 16;
             }
         }
@@ -86,8 +82,8 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_dist_row_kernel(const uint8_t
             uint32_t a = DIST_NONE, b = DIST_NONE;
             if (c0 + j < ncls) {
                 const uint32_t v = wrow[(size_t)(c0 + j) * W + xs], gi = v & 0xFFFFu, go = v >> 16;
-                a = gi == DIST_NONE16 ? DIST_NONE : gi * gi;
-                b = go == DIST_NONE16 ? DIST_NONE : go * go;
+                a = dist_sq16(gi);
+                b = dist_sq16(go);
             }
             ((uint32_t*)s_in)[4 * xs + j] = a;
             s_out[xs][j] = b;
@@ -396,7 +392,7 @@ extern "C" int s2e_seg_dist_maps(const uint8_t* label, int N, int H, int W, int 
     S2E_CHECK_LAUNCH("seg_dist_col_kernel");
     const long r = radius < 2048 ? radius : 2048;                        // (r^2 beyond 2 * 1023^2 already takes every pixel that has a distance)
     const int vec = ncls == 4 && ((uintptr_t)phi & 15) == 0;            // a pixel's four phi as one 16-byte store
-    const int row_threads = W >= SEG_THREADS ? SEG_THREADS : ceil_div(W, 64) * 64;
+    const int row_threads = dist_row_threads(W, SEG_THREADS);
     seg_dist_row_kernel<<<dim3(H, N), row_threads, 0, st>>>(label, (const uint32_t*)workspace, H, W, ncls, (uint32_t)(r * r), vec, phi, band);
     S2E_CHECK_LAUNCH("seg_dist_row_kernel");
     return S2E_OK;

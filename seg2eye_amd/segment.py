@@ -1,5 +1,5 @@
 """The eye segmenter: train it on an OpenEDS store's labelled frames, score it, and write the masks `style_rank --seg_file`
-reads -- the step between `prepare_openeds` and `style_rank` of the chain  prepare_openeds -> segment -> style_rank -> train -> test
+reads -- the step between `prepare_openeds` and `style_rank` of the chain  prepare_openeds -> segment -> mask_clean -> style_rank -> train -> test
 (and -> refine, the residual refiner of seg2eye_amd/refine.py, which reads the same masks and rankings).
 
 The generative and sequence frames of the `train` and `validation` splits are unlabelled; `style_rank` compares them through masks it
@@ -140,10 +140,11 @@ def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True
 
 
 # ------------------------------------------------------------------------------------------------ predict
-def predict_masks(net, store, dataset_key, opt, keys=PRED_KEYS, device='cuda'):
+def predict_masks(net, store, dataset_key, opt, keys=PRED_KEYS, device='cuda', clean=None):
     """-> {dataset_key: {user: {'labels_pred_gen': uint8 (n, 640, 400), 'labels_pred_seq': ...}}}: the mask of every row of the listed
     image keys a person has, row-aligned with the images -- what `style_rank.rank_styles(..., seg_store=...)` takes and what
-    `prepare_openeds.save_store` writes for `style_rank --seg_file`."""
+    `prepare_openeds.save_store` writes for `style_rank --seg_file`.  clean: None, or a `mask_clean.MaskRule`: every batch of masks is
+    cleaned by it before it leaves the device."""
     from .ops import segment as S
     out = {}
     bs = int(opt.batchSize)
@@ -159,7 +160,8 @@ def predict_masks(net, store, dataset_key, opt, keys=PRED_KEYS, device='cuda'):
                 for r0 in range(0, n, bs):
                     frames = rows_u8((g[key], r) for r in range(r0, min(r0 + bs, n)))
                     logits = net(_frames_to_input(frames, opt.seg_hw, _no_flip(len(frames), device), device))
-                    masks[r0:r0 + len(frames)] = S.seg_argmax_u8(logits, H, W).cpu().numpy()
+                    batch = S.seg_argmax_u8(logits, H, W)
+                    masks[r0:r0 + len(frames)] = (batch if clean is None else clean(batch)).cpu().numpy()
                 out[user][pred_name(key)] = masks
     return {dataset_key: out}
 
