@@ -883,6 +883,41 @@ int s2e_mask_components(const uint8_t* labels, int N, int H, int W, int ncls, in
 int s2e_mask_clean(const uint8_t* labels, int N, int H, int W, int ncls, int conn, const uint8_t* modes, uint8_t* out, int32_t* stats,
                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------ eye geometry: rim moments and the repaint from conics
+ * labels: (N, H, W) uint8, 1 <= ncls <= 16, H and W at most 1024.  Everything is per image: nothing crosses images, and a pixel of the
+ * frame's edge has no neighbour beyond it.  Every result is an integer or a copy.  The rules:
+ *   curves      curve k, 0 <= k < K <= 4, is a pair of class sets (in_sets[k], out_sets[k]), bit c = class c.  Both arrays are HOST
+ *       pointers to K uint16, read before the first launch, so that a bad set is refused here and not met by a kernel: a set must not
+ *       be empty, the two must not overlap, and neither may name a class >= ncls.  For the OpenEDS classes (0 skin, 1 sclera, 2 iris,
+ *       3 pupil) the limbus is in {2, 3} out {1} and the pupil's edge in {3} out {2}: where a lid covers the iris or the pupil there
+ *       is no rim pixel.
+ *   rim pixel   a pixel whose label l < ncls is in in_sets[k] and one of whose four neighbours inside the frame has a label l' < ncls
+ *       in out_sets[k].  A label >= ncls (255 is the documented "ignore") is in no set and is never used as an index.
+ *   s2e_rim_moments: rim (N, K, 18) int64, 8-byte aligned.  Over the rim pixels (x, y) of curve k in image n:
+ *         rim[0] = n, their number;  rim[1] = ox = floor((2 sum x + n) / (2 n)),  rim[2] = oy likewise (0, 0 when n = 0);
+ *         rim[3 + m] = sum (x - ox)^i (y - oy)^j for i + j <= 4, by degree and then by j:
+ *           m = 0: (0,0)   1: (1,0)  2: (0,1)   3: (2,0)  4: (1,1)  5: (0,2)   6: (3,0)  7: (2,1)  8: (1,2)  9: (0,3)
+ *               10: (4,0)  11: (3,1)  12: (2,2)  13: (1,3)  14: (0,4)
+ *       With H, W <= 1024, |x - ox| <= 1023: a term is below 2^40 and a sum of at most 2^20 of them below 2^60.  The origin needs the
+ *       whole image before a centred sum can start: three launches -- the first moments and the centred sums as per-workgroup integer
+ *       partials with plain stores into `workspace` (s2e_rim_moments_workspace_bytes(N, H, W, K) bytes, 8-byte aligned), then one fold.
+ *       No workgroup waits for another and no launch reads a line it writes.
+ *   s2e_ellipse_paint: out (N, H, W) uint8, another buffer than labels.  conic (N, K, 6) double = (A, B, C, D, E, F) of curve k about
+ *       origin (N, K, 2) int32 = (ox, oy); valid (N, K) uint8; all three on the device.  paint: a HOST pointer to K class bytes; keep:
+ *       a class set (bit c = class c); base: a class.  An image with any valid byte 0 comes back unchanged.  Otherwise a pixel whose
+ *       label is >= ncls or in keep is unchanged; every other pixel becomes base and then, for k ascending, paint[k] where Q_k <= 0,
+ *         Q_k = ((((A u) u + (B u) v) + (C v) v) + D u) + E v) + F,   u = (double)(x - ox), v = (double)(y - oy),
+ *       in fp64, every product and sum rounded once and none fused; a NaN compares false.  One launch, one lane per four pixels.
+ * Before any launch, in this order: S2E_ERR_ARG on a null pointer, on a short workspace or a workspace, rim or conic that is not 8-byte
+ * aligned (origin: 4-byte; a shape refused below needs 0 bytes), on N, H or W < 1; S2E_ERR_UNSUPPORTED on K outside 1..4, on ncls outside
+ * 1..16; S2E_ERR_ARG on a curve whose sets are empty, overlap or name a class >= ncls, on paint[k] or base >= ncls;
+ * S2E_ERR_UNSUPPORTED on H or W > 1024 (the int64 bound above), on N > 65535 or N H W >= 2^31. */
+size_t s2e_rim_moments_workspace_bytes(int N, int H, int W, int K);
+int s2e_rim_moments(const uint8_t* labels, int N, int H, int W, int ncls, int K, const uint16_t* in_sets, const uint16_t* out_sets,
+                    int64_t* rim, void* workspace, size_t workspace_bytes, void* stream);
+int s2e_ellipse_paint(const uint8_t* labels, int N, int H, int W, int ncls, int K, const double* conic, const int32_t* origin,
+                      const uint8_t* valid, const uint8_t* paint, int keep, int base, uint8_t* out, void* stream);
+
 /* ------------------------------------------------------------------ residual refiner: input, loss, gradient, submission bytes
  * The reference's last stage (refinenet/): the top-ranked frame of the same person plus a learned residual, clamped to [-1, 1].  These
  * are the four memory-bound pieces around the network.  tmask, rimg, rmask, truth: (N, H, W) uint8 planes as the store holds them.

@@ -210,6 +210,9 @@ SIGNATURES = {
     's2e_mask_clean_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
     's2e_mask_components': (STATUS, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
     's2e_mask_clean': (STATUS, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    's2e_rim_moments_workspace_bytes': (SIZE, [_i, _i, _i, _i]),
+    's2e_rim_moments': (STATUS, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    's2e_ellipse_paint': (STATUS, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     's2e_refine_input': (STATUS, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     's2e_refine_head_workspace_bytes': (SIZE, [_i, _i, _i]),
     's2e_refine_head_fwd': (STATUS, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
