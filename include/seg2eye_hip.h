@@ -1002,6 +1002,29 @@ int s2e_resize_bicubic_u8(const uint8_t* src, const uint8_t* flip, int M, int H,
 int s2e_resize_nearest_u8(const uint8_t* src, const uint8_t* flip, int M, int H, int W, int Ho, int Wo,
                           const int32_t* ys, const int32_t* xs, uint8_t* out, void* stream);
 
+/* ------------------------------------------------------------------ paired augmentation of frames and label maps
+ * One launch warps M pairs of uint8 planes (M, H, W) -- a frame and its label map -- by one affine transform per pair, draws line
+ * occluders on the frame and sends the frame through a table.  Integers throughout (64-bit where a product may pass 32), so that a
+ * numpy restatement gives the same bits (tests/_seg_augment_ref.py).  For pair m and OUTPUT pixel (x, y):
+ *   source   affine (M, 6) int32 = A0 .. A5 in Q16 (65536 = 1.0): sx = A0 x + A1 y + A2, sy = A3 x + A4 y + A5, then sx clamped to
+ *            [0, (W - 1) << 16] and sy to [0, (H - 1) << 16]: the edge is replicated, for the frame and the label map alike
+ *   label    out_lab = lab[m][(sy + 0x8000) >> 16][(sx + 0x8000) >> 16]
+ *   frame    x0 = sx >> 16, fx = (sx & 0xffff) >> 8, x1 = min(x0 + 1, W - 1), the same for y; with pYX = img[m][yY][xX]
+ *            v = ((p00 (256 - fx) + p01 fx) (256 - fy) + (p10 (256 - fx) + p11 fx) fy + 0x8000) >> 16
+ *   lines    lines (M, L, 6) int32 = (x0, y0, x1, y1, width, value) per line, in OUTPUT coordinates, the frame only, a later line
+ *            over an earlier one.  The end points are clamped to [-4096, 8191], width to [0, 255], value is taken & 255.  With
+ *            dx = x1 - x0, dy = y1 - y0, len2 = dx^2 + dy^2, t = (x - x0) dx + (y - y0) dy, c = (x - x0) dy - (y - y0) dx the pixel is
+ *            covered iff width >= 1, len2 > 0, 0 <= t <= len2 and 4 c^2 <= width^2 len2; a covered pixel takes v = value
+ *   output   out_f32 = lut_f32[m][v], out_u8 = lut_u8[m][v]   (lut_f32 (M, 256) float, lut_u8 (M, 256) uint8)
+ * Any int32 coefficients and line entries are in bounds: the launcher cannot read them, the kernel clamps.  img with out_f32 and out_u8
+ * may be NULL (labels only), or lab with out_lab (frames only); each of out_f32 and out_u8 may be NULL on its own, with its table.
+ * Before any launch, in this order: S2E_ERR_ARG on a NULL affine, on no output at all, on an image output without img, on out_lab
+ * without lab, on M, H or W < 1, on L < 0 or L > 0 without lines, on out_f32 without lut_f32 or out_u8 without lut_u8, on affine, lines,
+ * lut_f32 or out_f32 off 4-byte alignment, on an output pointer equal to an input pointer; S2E_ERR_UNSUPPORTED on H or W > 4096, on
+ * L > 8.  Planes of any other alignment and width work: outputs off 16 / 4 / 4 bytes or W % 4 != 0 take element stores. */
+int s2e_augment_pairs(const uint8_t* img, const uint8_t* lab, int M, int H, int W, const int32_t* affine, const int32_t* lines, int L,
+                      const float* lut_f32, const uint8_t* lut_u8, float* out_f32, uint8_t* out_u8, uint8_t* out_lab, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -245,6 +245,7 @@ SIGNATURES = {
     's2e_shard_sum': (STATUS, [_i, _vp, _vp, _i, _l, _vp]),
     's2e_resize_bicubic_u8': (STATUS, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     's2e_resize_nearest_u8': (STATUS, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    's2e_augment_pairs': (STATUS, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     's2e_sidebyside_ws_bytes': (COUNT, [_i, _i, _i]),
     's2e_sidebyside_u8': (STATUS, [_i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _l, _vp, _vp, _vp, _vp]),
 }

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'lib', 'libseg2eye_hip.so')
-SOURCES = ['conv_igemm.hip', 'conv_wgrad.hip', 'norm_modulate.hip', 'label_ops.hip', 'loss_adam.hip', 'spectral.hip', 'weight_pack.hip', 'weight_grad.hip', 'conv_small.hip', 'conv_c8.hip', 'conv_patch.hip', 'conv_duo.hip', 'conv_plane.hip', 'conv_stream.hip', 'conv_wgrad_patch.hip', 'conv_wgrad_batch.hip', 'conv_wgrad_flat.hip', 'metric.hip', 'style_fc.hip', 'spade_sparse_bwd.hip', 'preprocess.hip', 'visual.hip', 'd_augment.hip', 'ssim.hip', 'region.hip', 'msssim.hip', 'ffl.hip', 'style_rank.hip', 'segment.hip', 'seg_loss.hip', 'refine.hip', 'mask_clean.hip', 'eye_geometry.hip']
+SOURCES = ['conv_igemm.hip', 'conv_wgrad.hip', 'norm_modulate.hip', 'label_ops.hip', 'loss_adam.hip', 'spectral.hip', 'weight_pack.hip', 'weight_grad.hip', 'conv_small.hip', 'conv_c8.hip', 'conv_patch.hip', 'conv_duo.hip', 'conv_plane.hip', 'conv_stream.hip', 'conv_wgrad_patch.hip', 'conv_wgrad_batch.hip', 'conv_wgrad_flat.hip', 'metric.hip', 'style_fc.hip', 'spade_sparse_bwd.hip', 'preprocess.hip', 'visual.hip', 'd_augment.hip', 'ssim.hip', 'region.hip', 'msssim.hip', 'ffl.hip', 'style_rank.hip', 'segment.hip', 'seg_loss.hip', 'refine.hip', 'mask_clean.hip', 'eye_geometry.hip', 'seg_augment.hip']
 
 
 def _hipcc():

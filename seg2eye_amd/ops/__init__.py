@@ -21,15 +21,16 @@ One module per family (round 5; `ops.<name>` keeps resolving for every name, pri
   refine    the residual refiner: the network input of three uint8 planes, the loss on the challenge's error, the uint8 prediction
   mask_clean  the mask cleaner: connected components of label maps and the nearest-class fill (`ops.mask_clean` is the module)
   geometry  eye geometry: the integer moments of a mask's rim pixels (`rim_moments`) and the repaint from fitted conics (`ellipse_paint`)
+  augment   the segmenter's paired augmentation: frames and label maps warped by one transform per pair (`augment_pairs`), `AugmentRule`
   switches  the experiment switches (environment)"""
 from . import switches                                   # noqa: F401
-from . import core, sink, conv, spade, resample, losses, preprocess, visual, rank, segment, refine, mask_clean, geometry  # noqa: F401
+from . import core, sink, conv, spade, resample, losses, preprocess, visual, rank, segment, refine, mask_clean, geometry, augment  # noqa: F401
 from .._lib import (NORM_SPADE_STYLE_BATCH, NORM_ACCUMULATE_DX, ConvDesc, ACT_NONE, ACT_LRELU, ACT_TANH, AUX_NONE, AUX_RELU_MASK,      # noqa: F401
                     AUX_LRELU_GRAD, NORM_SPADE_STYLE, NORM_PLAIN_IN, LOSS_NEG_MEAN, LOSS_HINGE_REAL, LOSS_HINGE_FAKE, LOSS_L1)
 from .. import _lib as L                                 # noqa: F401
 
-for _m in (core, sink, conv, spade, resample, losses, preprocess, visual, rank, segment, refine, mask_clean, geometry):
+for _m in (core, sink, conv, spade, resample, losses, preprocess, visual, rank, segment, refine, mask_clean, geometry, augment):
     for _k, _v in vars(_m).items():
-        if not _k.startswith('__') and _k not in ('switches', 'core', 'sink', 'conv', 'spade', 'resample', 'losses', 'preprocess', 'visual', 'rank', 'segment', 'refine', 'mask_clean', 'geometry'):
+        if not _k.startswith('__') and _k not in ('switches', 'core', 'sink', 'conv', 'spade', 'resample', 'losses', 'preprocess', 'visual', 'rank', 'segment', 'refine', 'mask_clean', 'geometry', 'augment'):
             globals().setdefault(_k, _v)
 del _m, _k, _v

@@ -15,7 +15,8 @@ Frames go to the device as uint8 and are resized there (`ops.resize_bicubic_u8` 
 logits at --seg_hw; the loss is `ops.seg_cross_entropy` (or, with --lambda_dice / --lambda_surface / --edge_alpha, `ops.seg_loss`), a mask is `ops.seg_argmax_u8` of the logits resized to the frame's own size,
 the score is mIoU (the OpenEDS segmentation metric) from `ops.seg_confusion`, accumulated on the device and read back once.
 
-The three commands are plain functions too: `train_segmenter`, `evaluate`, `predict_masks`.  The ops are looked up when called."""
+The three commands are plain functions too: `train_segmenter`, `evaluate`, `predict_masks`.  The ops are looked up when called.
+`python -m seg2eye_amd.seg_augment train` is `train` on augmented data (`train_segmenter(..., augment=rule)`)."""
 import numpy as np
 import torch
 
@@ -96,15 +97,18 @@ def evaluate(net, store, dataset_key, opt, device='cuda', verbose=True):
 
 
 # ------------------------------------------------------------------------------------------------ train
-def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True):
+def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True, augment=None):
     """Train on every labelled frame of /train, in a shuffled order seeded by opt.seed, for opt.niter epochs; after every epoch score
     /validation (when the store has it) and save `<epoch>_net_S.pth` and `latest_net_S.pth`.  net: a network to go on from (default: a
     new one).  -> (net, {'loss': [one float per step], 'scores': [one dict per epoch]}).
 
     With --lambda_dice, --lambda_surface or --edge_alpha set (or --lambda_ce off 1) the loss is `ops.seg_loss` on the
     distance maps and boundary band `ops.seg_dist_maps` makes of the resized, flipped labels of the batch; the history then has
-    'terms': [[CE, Dice, Surface] per step] too, and the progress line shows their means."""
-    from .ops import preprocess as P, segment as S
+    'terms': [[CE, Dice, Surface] per step] too, and the progress line shows their means.
+
+    augment: None, or an `ops.AugmentRule`.  A step then draws, behind the flip, `augment.draw(rng, len(batch),
+    *opt.seg_hw)`, and the network and the loss get `ops.augment_pairs` of the resized, flipped uint8 frames and labels."""
+    from .ops import augment as A, preprocess as P, segment as S
     if net is None:
         net = build_network(opt, device)
     samples = labelled_samples(store, 'train')
@@ -120,8 +124,15 @@ def train_segmenter(store, opt, net=None, device='cuda', save=True, verbose=True
 
     def step(batch, rng, device):
         flip = _no_flip(len(batch), device) if opt.no_flip else stage.draw_flip(rng, len(batch), device)
-        x = _frames_to_input(_labelled_rows(store, 'train', 'images_ss', batch), opt.seg_hw, flip, device)
+        if augment is None:
+            x = _frames_to_input(_labelled_rows(store, 'train', 'images_ss', batch), opt.seg_hw, flip, device)
+        else:
+            params = augment.draw(rng, len(batch), *opt.seg_hw)
+            _, x_u8 = P.resize_bicubic_u8(stage.to_device(device, _labelled_rows(store, 'train', 'images_ss', batch))[0], opt.seg_hw[0], opt.seg_hw[1], flip, return_u8=True)
         y = P.resize_nearest_u8(stage.to_device(device, _labelled_rows(store, 'train', 'labels_ss', batch))[0], opt.seg_hw[0], opt.seg_hw[1], flip)
+        if augment is not None:
+            x, _, y = A.augment_pairs(x_u8, y, params)
+            x = x.unsqueeze(1)
         if plain:
             return S.seg_cross_entropy(net(x), y, weights), None
         phi = band = None
@@ -171,19 +182,23 @@ def _csv(kind):
     return lambda s: tuple(kind(v) for v in s.split(','))
 
 
-def parser():
-    ap, p = stage.stage_parser(
-        'python -m seg2eye_amd.segment', 'Train, score and apply the eye segmenter (the masks of style_rank --seg_file).', 'segmenter', 16,
-        ('train on the labelled frames of /train', 'mIoU of a checkpoint on the labelled frames of a split', 'write the masks of the unlabelled frames of a split'),
-        'frames', 'train',
-        net=[('--nsf', dict(type=int, default=32, help='# of filters of the first conv layer (a multiple of 8)')),
-             ('--seg_hw', dict(type=_csv(int), default=(320, 200), help='H,W the frames are resized to (multiples of 8)'))],
-        train=[('--class_weights', dict(type=_csv(float), default=None, help='one weight per class, e.g. 1,1,1,1'))],
-        train_last=[('--lambda_ce', dict(type=float, default=1.0, help='weight of the cross-entropy term')),
+# the stage's own flags, where stage.stage_parser lists them (seg_augment's `train` takes the same)
+FLIP_WHAT = 'frames'
+NET_FLAGS = [('--nsf', dict(type=int, default=32, help='# of filters of the first conv layer (a multiple of 8)')),
+             ('--seg_hw', dict(type=_csv(int), default=(320, 200), help='H,W the frames are resized to (multiples of 8)'))]
+TRAIN_FLAGS = [('--class_weights', dict(type=_csv(float), default=None, help='one weight per class, e.g. 1,1,1,1'))]
+TRAIN_LAST_FLAGS = [('--lambda_ce', dict(type=float, default=1.0, help='weight of the cross-entropy term')),
                     ('--lambda_dice', dict(type=float, default=0.0, help='weight of the generalised Dice term (classes weighed by inverse squared area)')),
                     ('--lambda_surface', dict(type=float, default=0.0, help='weight of the surface (boundary) term on signed distance maps')),
                     ('--edge_alpha', dict(type=float, default=0.0, help='a pixel within --edge_radius of another class counts 1 + edge_alpha times in the cross-entropy')),
-                    ('--edge_radius', dict(type=int, default=2, help='width of the boundary band, in pixels of --seg_hw'))])
+                    ('--edge_radius', dict(type=int, default=2, help='width of the boundary band, in pixels of --seg_hw'))]
+
+
+def parser():
+    ap, p = stage.stage_parser(
+        'python -m seg2eye_amd.segment', 'Train, score and apply the eye segmenter (the masks of style_rank --seg_file).', DEFAULTS['name'], DEFAULTS['batchSize'],
+        ('train on the labelled frames of /train', 'mIoU of a checkpoint on the labelled frames of a split', 'write the masks of the unlabelled frames of a split'),
+        FLIP_WHAT, 'train', net=NET_FLAGS, train=TRAIN_FLAGS, train_last=TRAIN_LAST_FLAGS)
     p.add_argument('--out', required=True, help='the file style_rank --seg_file opens (HDF5; <out>.npz without h5py)')
     p.add_argument('--keys', type=_csv(str), default=PRED_KEYS, help='image keys to segment, e.g. images_gen,images_seq')
     return ap

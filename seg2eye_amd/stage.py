@@ -79,32 +79,45 @@ def train_epochs(net, samples, opt, tag, step, validate, line, has_terms, device
 
 
 # ------------------------------------------------------------------------------------------------ the command line
+def add_flags(p, flags):
+    """A stage's own flags, [(flag, add_argument's keywords)], onto a parser."""
+    for flag, kw in flags:
+        p.add_argument(flag, **kw)
+
+
+def add_common_flags(p, name, batch_size, inputs=(), net=()):
+    """The flags every command of a stage takes; `inputs` sit behind --dataroot, `net` behind --checkpoints_dir."""
+    p.add_argument('--dataroot', required=True, help='the store prepare_openeds wrote (.h5, or .npz without h5py)')
+    add_flags(p, inputs)
+    p.add_argument('--name', default=name, help='the checkpoints live in <checkpoints_dir>/<name>')
+    p.add_argument('--checkpoints_dir', default='./checkpoints')
+    add_flags(p, net)
+    p.add_argument('--label_nc', type=int, default=4)
+    p.add_argument('--compute_dtype', default='bf16', choices=['bf16', 'fp32'])
+    p.add_argument('--batchSize', type=int, default=batch_size)
+
+
+def add_train_flags(p, flip_what, train=(), train_last=()):
+    """The flags of a stage's `train` behind the common ones; `train` sit behind --lr, `train_last` behind --print_freq."""
+    p.add_argument('--niter', type=int, default=20, help='epochs')
+    p.add_argument('--lr', type=float, default=1e-3)
+    add_flags(p, train)
+    p.add_argument('--seed', type=int, default=0)
+    p.add_argument('--no_flip', action='store_true', help='no horizontal flip of the training %s' % flip_what)
+    p.add_argument('--print_freq', type=int, default=50, help='steps between two lines of the running loss')
+    add_flags(p, train_last)
+
+
 def stage_parser(prog, description, name, batch_size, helps, flip_what, predict_split, inputs=(), net=(), train=(), train_last=()):
     """The train / eval / predict command line of a stage -> (parser, the predict subparser, for the stage's output flags).  helps: the
     help lines of the three.  The stage's own flags come as [(flag, add_argument's keywords)] and sit where the help has always listed
     them: `inputs` behind --dataroot, `net` behind --checkpoints_dir, `train` behind --lr, `train_last` behind --print_freq."""
-    def add(p, flags):
-        for flag, kw in flags:
-            p.add_argument(flag, **kw)
     ap = argparse.ArgumentParser(prog=prog, description=description)
     common = argparse.ArgumentParser(add_help=False)
-    common.add_argument('--dataroot', required=True, help='the store prepare_openeds wrote (.h5, or .npz without h5py)')
-    add(common, inputs)
-    common.add_argument('--name', default=name, help='the checkpoints live in <checkpoints_dir>/<name>')
-    common.add_argument('--checkpoints_dir', default='./checkpoints')
-    add(common, net)
-    common.add_argument('--label_nc', type=int, default=4)
-    common.add_argument('--compute_dtype', default='bf16', choices=['bf16', 'fp32'])
-    common.add_argument('--batchSize', type=int, default=batch_size)
+    add_common_flags(common, name, batch_size, inputs, net)
     sub = ap.add_subparsers(dest='command', required=True)
     t = sub.add_parser('train', parents=[common], help=helps[0])
-    t.add_argument('--niter', type=int, default=20, help='epochs')
-    t.add_argument('--lr', type=float, default=1e-3)
-    add(t, train)
-    t.add_argument('--seed', type=int, default=0)
-    t.add_argument('--no_flip', action='store_true', help='no horizontal flip of the training %s' % flip_what)
-    t.add_argument('--print_freq', type=int, default=50, help='steps between two lines of the running loss')
-    add(t, train_last)
+    add_train_flags(t, flip_what, train, train_last)
     e = sub.add_parser('eval', parents=[common], help=helps[1])
     p = sub.add_parser('predict', parents=[common], help=helps[2])
     for s in (e, p):
